@@ -3,19 +3,30 @@
 path (render + colour/eikonal loss + backward + Adam) on synthetic DTU-scan24-shaped rays.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full              (+ every secondary measurement, see below)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR  (+ the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...      (no launcher: bench.py starts the N ranks itself through torch.distributed.run)
 
 Workload (BASELINE.json configs[1]): 512 rays x 128 samples per GPU (64 coarse + 64 hierarchical in
 4 rounds, no outside samples); arithmetic: fp32 EMULATED on the 16-bit matrix pipe (`--precision bf16x3`, the default; `fp32`
-= the exact v_mfma_f32_32x32x2_f32 kernels, also timed here as the secondary `fp32_exact` leg).  With N GPUs the global
+= the exact v_mfma_f32_32x32x2_f32 kernels, also timed by `--full` as the secondary `fp32_exact` leg).  With N GPUs the global
 batch is 512*N rays, ray-sharded, one packed loss all-reduce + one gradient all-reduce per step (weak scaling);
 `--scaling strong --global-rays 4096` (BASELINE configs[3]) fixes the global batch and gives every rank 4096 / N rays.
-The timed region is `--windows` (5) windows of `--steps` steps each, every window bracketed by barrier + synchronize and
-reduced with MAX over ranks; `ms_per_step` is the MEDIAN window, `window_ms` lists them all.
+The timed region is exactly `--steps` steps, split into `--windows` (5, at most one per step) windows of as equal a size as
+possible, every window bracketed by barrier + synchronize and reduced with MAX over ranks; `ms_per_step` is the per-step
+time of the MEDIAN window, `window_ms` lists them all.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the line -- nothing else runs on
+the GPU.  `--dump-outputs DIR` then writes what the last timed step computed (rank 0): the loss, every tensor of the
+step's render output, and every parameter and gradient of the five networks after the step's Adam update,
+as DIR/<name>.npy (float32; float64 arrays stay float64), 64 MB at most in all (beyond that, every large array is
+replaced by a fixed seeded sample of its elements).  The inputs are seeded: with the same arguments two builds compute
+on identical rays and weights.  `--full` adds the secondary objects, each measured after the timed windows
+(`--no-power`, `--no-forward-only`, `--no-roofline`, `--no-fp32-leg`, `--no-cpu-baseline` drop single ones):
+  power        -- socket power / shader clock of this rank's card while the step replays for ~1 s.
+  forward_only -- render + loss under no_grad, same batch and bracketing.
   roofline     -- the dominant kernel class of the step (the fused layer-chain kernel `mlp_chain_kernel`): flops its
                   launches execute / their summed duration, measured with HIP events on the launch stream during one extra
                   instrumented step.  Default mode "bf16x3" (fp32 emulated on the 16-bit matrix pipe: three fp16 MFMA products per
@@ -26,9 +37,10 @@ Prints ONE JSON line (rank 0).  Extra objects:
                   PMC passes over this command (profiles/r06_traffic_mlp_chain_<mode>.json, see `traffic_stale`).
   roofline_composite -- the fused sample+composite kernels against the 8 TB/s HBM roof
                   (48 B/sample + 68 B/ray forward, 84 B/sample + 68 B/ray backward).
+  fp32_exact   -- the same step with the exact fp32 kernels (bf16x3 runs on one GPU).
   cpu_baseline -- the reference's own classes (oracle/_ref/reference_tree, kind "reference"; the oracle's port when that
                   tree is absent) timed on this host's cores, one pinned thread per physical core, on a bounded sample of
-                  the same workload.
+                  the same workload; with it `psnr_vs_ref`, the HIP path's colours against the oracle's.
 """
 import argparse
 import json
@@ -414,6 +426,39 @@ def _self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, step_out, tr):
+    """`--dump-outputs`: what the last timed step handed its caller -- the loss and every tensor of the render output --
+    and the state it left behind, every parameter and gradient of the five networks after the Adam update, as
+    <path>/<name>.npy (float64 stays float64, everything else is written as float32).  Beyond DUMP_LIMIT_BYTES in all,
+    every array larger than an equal share of the limit is replaced by a fixed sample of its flattened elements (the
+    sample's seed is the array's name, so it does not depend on the other arrays)."""
+    import zlib
+    import numpy as np
+    loss, out = step_out
+    arrays = {"loss": loss}
+    arrays.update({"out_" + k: v for k, v in sorted(out.items()) if torch.is_tensor(v)})
+    for m_name, m in tr.modules().items():
+        for n, p in m.named_parameters():
+            arrays[f"param_{m_name}.{n}"] = p
+            if p.grad is not None:
+                arrays[f"grad_{m_name}.{n}"] = p.grad
+    torch.cuda.synchronize()
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+            for k, v in arrays.items()}
+    if sum(a.nbytes for a in host.values()) > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // len(host)
+        for k, a in host.items():
+            if a.nbytes > share:
+                rng = np.random.default_rng(zlib.crc32(k.encode()))
+                host[k] = a.reshape(-1)[np.sort(rng.choice(a.size, share // a.itemsize, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -425,10 +470,16 @@ def main():
                     help="weak (default): --rays-per-gpu rays on every rank; strong: --global-rays rays in total, "
                          "global / N per rank (default for the dtu_scan118_4096x128 workload, BASELINE configs[3])")
     ap.add_argument("--global-rays", type=int, default=0, help="strong scaling: rays of the whole job (default: the workload's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the secondary objects (power, forward_only, roofline, "
+                         "roofline_composite, fp32_exact, cpu_baseline / psnr_vs_ref); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, render output, parameters and gradients after the "
+                         "update) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (rank 0)")
     ap.add_argument("--no-power", action="store_true", help="skip the ~1 s power / shader-clock sampling window after the timed region")
     ap.add_argument("--windows", type=int, default=5,
-                    help="timed windows of --steps steps each; ms_per_step is the median window (box-to-box and "
-                         "window-to-window spread of a 0.1 s region is ~3 %%)")
+                    help="the --steps timed steps are split into this many windows (at most one per step); ms_per_step "
+                         "is the median window (box-to-box and window-to-window spread of a 0.1 s region is ~3 %%)")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the secondary exact-fp32 timing leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -443,6 +494,10 @@ def main():
                          "MFMA); fp32 = the exact v_mfma_f32_32x32x2_f32 kernels (also timed as the `fp32_exact` leg); "
                          "mixed16 = BASELINE config 5 (16-bit MFMA operands, fp32 accumulate) -- never the headline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:              # a plain run: the headline only
+        args.no_power = args.no_forward_only = args.no_roofline = args.no_fp32_leg = args.no_cpu_baseline = True
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU through
     # torch.distributed.run on 127.0.0.1) and relay them -- rank 0 of the child job prints the JSON line.  Under a launcher
@@ -551,13 +606,19 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
-    def timed_window(fn, steps):
-        """EXACTLY `steps` steps bracketed by barrier + synchronize on both sides; -> seconds, MAX over ranks"""
+    last = {}
+
+    def timed_window(fn, steps, keep=False):
+        """EXACTLY `steps` steps bracketed by barrier + synchronize on both sides; -> seconds, MAX over ranks.  `keep`: what
+        the last step returned is kept in `last["out"]`."""
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            fn()
+        for i in range(steps):
+            if keep and i == steps - 1:
+                last["out"] = fn()
+            else:
+                fn()
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
@@ -570,20 +631,25 @@ def main():
         return dtw
 
     nd.collective_counts(reset=True)
-    n_win = max(1, args.windows)
-    wins = [timed_window(run_step, args.steps) for _ in range(n_win)]
+    # the --steps timed steps, split into n_win windows whose sizes differ by at most one step
+    n_win = max(1, min(args.windows, args.steps))
+    sizes = [args.steps // n_win + (1 if i < args.steps % n_win else 0) for i in range(n_win)]
+    keep = bool(args.dump_outputs) and rank == 0
+    wins = [timed_window(run_step, n, keep) / n for n in sizes]   # seconds per step of each window
     coll = nd.collective_counts()
-    dt = sorted(wins)[len(wins) // 2]                      # the median window
-    ms_per_step = dt / args.steps * 1e3
-    value = world * rays_per_gpu * s_core / (dt / args.steps)
+    step_s = sorted(wins)[len(wins) // 2]                  # the median window
+    ms_per_step = step_s * 1e3
+    value = world * rays_per_gpu * s_core / step_s
     if use_graph and coll_eager is not None:               # replays issue the collectives from inside the graph
-        coll = {k: v * args.steps * n_win for k, v in coll_eager.items()}
+        coll = {k: v * args.steps for k, v in coll_eager.items()}
+    if keep:
+        dump_outputs(args.dump_outputs, last["out"], tr)
 
     result = {
         "metric": "ray-samples/sec (train step)", "value": value, "unit": "ray-samples/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
         "scaling": scaling, "vs_baseline": None,
-        "window_ms": [w / args.steps * 1e3 for w in wins], "windows": n_win,
+        "window_ms": [w * 1e3 for w in wins], "windows": n_win, "window_steps": sizes,
         "dtype": dtype_string(args.precision),
         "data": "synthetic",
         "config": {"workload": args.workload, "rays_per_gpu": rays_per_gpu, "global_rays": rays_per_gpu * world,
@@ -603,14 +669,14 @@ def main():
                                                          "backend, or the capture failed)" if world > 1 and args.graph else ""))},
         # data-parallel exchange of the timed region (neuraludf_amd/dist.py): packed loss sums + gradient bucket
         "rccl_ranks": world if backend == "nccl" else 0, "dist_backend": backend if world > 1 else None,
-        "collectives_per_step": {k: v / (args.steps * n_win) for k, v in coll.items()} if world > 1 else None,
+        "collectives_per_step": {k: v / args.steps for k, v in coll.items()} if world > 1 else None,
         "gradient_message_floats": (tr.bucket.last_message_floats if world > 1 else None),
     }
 
     # ---- socket power and shader clock under the same replayed step (outside the timed windows; every rank steps, rank 0 samples)
     if not args.no_power:
         try:
-            n_pw = max(args.steps, int(1.0 / max(dt / args.steps, 1e-4)))       # (dt is the max over ranks: the same everywhere)
+            n_pw = max(args.steps, int(1.0 / max(step_s, 1e-4)))       # (step_s is the max over ranks: the same everywhere)
             if rank == 0:
                 with _PowerSampler(device=dev.index or 0) as ps:
                     timed_window(run_step, n_pw)
@@ -622,20 +688,20 @@ def main():
 
     # ---- forward only ("also forward-only ray-samples/s"): the same batch rendered without autograd, all
     # ranks (the ray-sharded render holds a collective), same bracketing
-    with torch.no_grad():
-        for _ in range(0 if args.no_forward_only else 2):
-            tr.loss(batch, **({"blend": step_kw["blend"]} if step_kw else {}))
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(0 if args.no_forward_only else args.steps):
-            tr.loss(batch, **({"blend": step_kw["blend"]} if step_kw else {}))
-        torch.cuda.synchronize()
-        barrier()
-        torch.cuda.synchronize()
-        dtf = (time.perf_counter() - t0) / args.steps
     if not args.no_forward_only:
+        with torch.no_grad():
+            for _ in range(2):
+                tr.loss(batch, **({"blend": step_kw["blend"]} if step_kw else {}))
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                tr.loss(batch, **({"blend": step_kw["blend"]} if step_kw else {}))
+            torch.cuda.synchronize()
+            barrier()
+            torch.cuda.synchronize()
+            dtf = (time.perf_counter() - t0) / args.steps
         result["forward_only"] = {"value": world * rays_per_gpu * s_core / dtf, "unit": "ray-samples/s", "ms": dtf * 1e3,
                                   "what": "render + loss under no_grad, rank-local clock"}
 

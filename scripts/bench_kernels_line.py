@@ -1,4 +1,4 @@
-"""print the per-kernel lines of a bench.py JSON line (stdin)"""
+"""print the per-kernel lines of a `bench.py --full` JSON line (stdin)"""
 import json, sys
 for line in sys.stdin:
     line = line.strip()

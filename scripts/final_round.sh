@@ -8,10 +8,10 @@ O=$R/gpurun_out/final; rm -rf $O; mkdir -p $O
 cd $R
 timeout 1200 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.log
 timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err
-timeout 300 python bench.py --workload "dtu_shipped_512x114+32" --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_shipped.json 2>> $O/bench.err
-timeout 300 python bench.py --workload garment_blend_1024x128 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_blend.json 2>> $O/bench.err
-timeout 300 python bench.py --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_mixed16.json 2>> $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --workload "dtu_shipped_512x114+32" --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_shipped.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload garment_blend_1024x128 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_blend.json 2>> $O/bench.err
+timeout 300 python bench.py --full --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_mixed16.json 2>> $O/bench.err
 python scripts/composite_sizes.py > $O/composite_sizes.txt 2>&1
 python scripts/hbm_calib.py >> $O/composite_sizes.txt 2>&1
 for w in dtu_scan24_512x128 garment_blend_1024x128; do

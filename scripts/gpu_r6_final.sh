@@ -8,25 +8,25 @@ O=$R/gpurun_out/r6final; rm -rf $O; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider --durations=10 > $O/pytest_gpu.log 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.log
 timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err
-timeout 300 python bench.py --graph 0 --no-cpu-baseline > $O/bench_eager.json 2>> $O/bench.err
-timeout 300 python bench.py --rays-per-gpu 256 --no-cpu-baseline --no-roofline > $O/bench_256.json 2>> $O/bench.err
-timeout 300 python bench.py --rays-per-gpu 256 --graph 0 --no-cpu-baseline --no-roofline > $O/bench_256_eager.json 2>> $O/bench.err
-timeout 300 python bench.py --precision fp32 --no-cpu-baseline > $O/bench_fp32_exact.json 2>> $O/bench.err
-timeout 300 python bench.py --precision mixed16 --no-cpu-baseline > $O/bench_mixed16.json 2>> $O/bench.err
-timeout 300 python bench.py --workload "dtu_shipped_512x114+32" --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_shipped.json 2>> $O/bench.err
-timeout 300 python bench.py --workload garment_blend_1024x128 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_blend.json 2>> $O/bench.err
-timeout 300 python bench.py --workload dtu_scan24_1024x256 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_bf16x3.json 2>> $O/bench.err
-timeout 300 python bench.py --workload dtu_scan24_1024x256 --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_mixed16.json 2>> $O/bench.err
-NUDF_EX_FLY=0 timeout 300 python bench.py --workload dtu_scan24_1024x256 --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_mixed16_exstored.json 2>> $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --graph 0 --no-cpu-baseline > $O/bench_eager.json 2>> $O/bench.err
+timeout 300 python bench.py --full --rays-per-gpu 256 --no-cpu-baseline --no-roofline > $O/bench_256.json 2>> $O/bench.err
+timeout 300 python bench.py --full --rays-per-gpu 256 --graph 0 --no-cpu-baseline --no-roofline > $O/bench_256_eager.json 2>> $O/bench.err
+timeout 300 python bench.py --full --precision fp32 --no-cpu-baseline > $O/bench_fp32_exact.json 2>> $O/bench.err
+timeout 300 python bench.py --full --precision mixed16 --no-cpu-baseline > $O/bench_mixed16.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload "dtu_shipped_512x114+32" --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_shipped.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload garment_blend_1024x128 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_blend.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload dtu_scan24_1024x256 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_bf16x3.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload dtu_scan24_1024x256 --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_mixed16.json 2>> $O/bench.err
+NUDF_EX_FLY=0 timeout 300 python bench.py --full --workload dtu_scan24_1024x256 --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_mixed16_exstored.json 2>> $O/bench.err
 # round-6 A/B legs at the headline: six bf16 products on the forward-order sweeps (round 5's arithmetic), the stored second-order
 # term, bf16x3 weight-gradient GEMMs, bf16x3 backward sweeps
-NUDF_FWD_F16X2=0 timeout 300 python bench.py --no-cpu-baseline --no-fp32-leg > $O/bench_fwd_bf16x3.json 2>> $O/bench.err
-NUDF_EX_FLY=0 timeout 300 python bench.py --no-cpu-baseline --no-fp32-leg > $O/bench_exstored.json 2>> $O/bench.err
-NUDF_TN_F16X2=0 timeout 300 python bench.py --no-cpu-baseline --no-fp32-leg > $O/bench_tn_bf16x3.json 2>> $O/bench.err
-NUDF_BWD_F16X2=0 timeout 300 python bench.py --no-cpu-baseline --no-fp32-leg > $O/bench_bwd_bf16x3.json 2>> $O/bench.err
-timeout 300 python bench.py --no-cpu-baseline --no-fp32-leg > $O/bench_again.json 2>> $O/bench.err
-timeout 300 python bench.py --workload dtu_scan118_4096x128 --steps 5 --warmup 2 --windows 3 --no-cpu-baseline --no-fp32-leg > $O/bench_strong4096.json 2>> $O/bench.err
+NUDF_FWD_F16X2=0 timeout 300 python bench.py --full --no-cpu-baseline --no-fp32-leg > $O/bench_fwd_bf16x3.json 2>> $O/bench.err
+NUDF_EX_FLY=0 timeout 300 python bench.py --full --no-cpu-baseline --no-fp32-leg > $O/bench_exstored.json 2>> $O/bench.err
+NUDF_TN_F16X2=0 timeout 300 python bench.py --full --no-cpu-baseline --no-fp32-leg > $O/bench_tn_bf16x3.json 2>> $O/bench.err
+NUDF_BWD_F16X2=0 timeout 300 python bench.py --full --no-cpu-baseline --no-fp32-leg > $O/bench_bwd_bf16x3.json 2>> $O/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline --no-fp32-leg > $O/bench_again.json 2>> $O/bench.err
+timeout 300 python bench.py --full --workload dtu_scan118_4096x128 --steps 5 --warmup 2 --windows 3 --no-cpu-baseline --no-fp32-leg > $O/bench_strong4096.json 2>> $O/bench.err
 # rocprofv3 kernel trace + stats of the default command (same build, same flags)
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-roofline --no-forward-only --no-fp32-leg > $O/prof_bench.log 2>&1)
 find $O/prof -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;

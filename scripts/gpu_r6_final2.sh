@@ -6,9 +6,9 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r6final; mkdir -p $O
 cd $R
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err
-timeout 300 python bench.py --workload dtu_scan24_1024x256 --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_mixed16.json 2>> $O/bench_final.err
-timeout 300 python bench.py --workload garment_blend_1024x128 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_blend.json 2>> $O/bench_final.err
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+timeout 300 python bench.py --full --workload dtu_scan24_1024x256 --precision mixed16 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cfg5_mixed16.json 2>> $O/bench_final.err
+timeout 300 python bench.py --full --workload garment_blend_1024x128 --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_blend.json 2>> $O/bench_final.err
 python - <<'PY'
 import json, os
 O = os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/r6final/"

@@ -126,7 +126,7 @@ def test_bench_two_rank_flow():
     backend: the run completes (no rank-0-only collective), prints one JSON line, counts both ranks' rays."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = _run([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays-per-gpu", "64"],
+    r = _run([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rays-per-gpu", "64", "--full"],
              {"NUDF_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -168,7 +168,7 @@ def test_bench_two_rank_strong_scaling_flow():
     rays once, and carries the windowed timing."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = _run([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "3", "--scaling",
+    r = _run([os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "3", "--scaling",
               "strong", "--global-rays", "128"], {"NUDF_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -137,17 +137,27 @@ def test_idr_camera_file(tmp_path):
 
 
 def test_checkpoint_interchange_with_reference_modules(tmp_path):
-    """a checkpoint written from the REFERENCE modules + torch Adam loads into the drop-in modules + FusedAdam
-    (and back) with identical tensors; file name / key layout as exp_runner_blending.py:486-498."""
-    from refload import have_reference, load_reference
-    if not have_reference():
-        pytest.skip("reference tree not present")
-    from common import build_modules
+    """a checkpoint written from modules with the REFERENCE's layout + torch Adam loads into the drop-in modules + FusedAdam
+    (and back) with identical tensors; file name / key layout as exp_runner_blending.py:486-498.  The reference's layout --
+    state-dict keys, parameter order (the optimizer state's indices) and seed-0 values -- is its own, recorded in
+    tests/golden/ref_vs_reference.npz (tests/golden/make_golden_vs_reference.py); seeded drop-in modules that match it
+    exactly stand in for the reference's classes."""
+    from common import build_modules, checksum
     from neuraludf_amd.models import fields as nf
     from neuraludf_amd.optim import FusedAdam
-    rf, _, _ = load_reference()
-    ref = build_modules(rf, seed=0)
+    gold = np.load(os.path.join(HERE, "golden", "ref_vs_reference.npz"))
     order = ["udf", "var", "color", "beta", "nerf"]
+
+    def as_reference(mods):
+        for k in order:
+            m = mods[k]
+            assert list(m.state_dict()) == [str(n) for n in gold[f"layout_{k}_keys"]], k
+            assert [n for n, _ in m.named_parameters()] == [str(n) for n in gold[f"layout_{k}_params"]], k
+        return mods
+    ref = as_reference(build_modules(nf, seed=0))
+    for k in order:
+        w = float(gold[f"layout_{k}_wsum"])
+        assert abs(checksum(ref[k].state_dict()) - w) < 1e-6 * max(1.0, abs(w)), k
 
     def groups(m):
         return [{"params": list(m["udf"].parameters()), "lr": 1e-4},
@@ -182,7 +192,7 @@ def test_checkpoint_interchange_with_reference_modules(tmp_path):
         assert float(sa["state"][i]["step"]) == float(sb["state"][i]["step"])
     # and back: written from the drop-in side, read by the reference side
     path2 = ck.save_checkpoint(str(tmp_path), 2000, mine["nerf"], mine["udf"], mine["var"], mine["color"], mine["beta"], opt2)
-    ref2 = build_modules(rf, seed=2)
+    ref2 = as_reference(build_modules(nf, seed=2))
     opt3 = torch.optim.Adam(groups(ref2), lr=5e-4)
     assert ck.load_checkpoint(path2, ref2["nerf"], ref2["udf"], ref2["var"], ref2["color"], ref2["beta"], opt3,
                               is_finetune=True) == 0

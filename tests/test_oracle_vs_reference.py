@@ -1,101 +1,92 @@
-"""Pin the oracle against the reference code itself (runs only where /root/reference exists,
-i.e. in the build container; the committed goldens cover the same ground elsewhere)."""
+"""Pin the oracle against the reference code itself: the reference side of every comparison is its own output, recorded
+in tests/golden/ref_vs_reference*.npz by tests/golden/make_golden_vs_reference.py (the generator runs the reference; this
+file runs anywhere).  The weights are rebuilt through the drop-in modules' seeded constructors and proven to be the
+fixture's by checksum."""
+import contextlib
+import io
+import os
+
+import numpy as np
 import pytest
 import torch
 
-from common import CONF, build_modules, perturb_, state_dicts, oracle_nets
-from refload import have_reference, load_reference
+from common import build_modules, checksum, perturb_, state_dicts, oracle_nets
 from neuraludf_amd import synth
 from oracle import udf_oracle as O
 
-pytestmark = pytest.mark.skipif(not have_reference(), reason="reference tree not mounted")
+import importlib.util
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+_spec = importlib.util.spec_from_file_location("make_golden_vs_reference",
+                                               os.path.join(HERE, "golden", "make_golden_vs_reference.py"))
+G = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(G)        # the cases (constants only: the generator's main() is not run)
 
 
 def _maxrel(a, b):
+    a, b = torch.as_tensor(a), torch.as_tensor(b)
     return float((a - b).abs().max() / b.abs().max().clamp(min=1.0))
 
 
 @pytest.fixture(scope="module")
-def ref():
-    rf, rr, rl = load_reference()
-    mods = perturb_(build_modules(rf, seed=0))
-    return rf, rr, rl, mods
+def gold():
+    return np.load(os.path.join(HERE, "golden", "ref_vs_reference.npz"))
 
 
-def _renderer(rr, mods, **kw):
-    return rr.UDFRendererBlending(mods["nerf"], mods["udf"], mods["var"], mods["color"], mods["beta"], **kw)
+@pytest.fixture(scope="module")
+def sds(gold):
+    from neuraludf_amd.models import fields
+    sds = state_dicts(perturb_(build_modules(fields, seed=0)))
+    for k, sd in sds.items():        # the reference's seeded weights, rebuilt
+        w = float(gold["wsum_" + k])
+        assert abs(checksum(sd) - w) < 1e-6 * max(1.0, abs(w)), k
+    return sds
 
 
-@pytest.mark.parametrize("case", ["classical_bg", "mix", "flat"])
-def test_render_matches_reference(ref, case):
-    rf, rr, rl, mods = ref
-    scene = synth.make_scene("tiny")
-    rays = synth.make_rays(scene, 0, 48, seed=5)
-    if case == "classical_bg":
-        kw = dict(n_samples=32, n_importance=20, n_outside=8, up_sample_steps=5, perturb=1.0)
-    elif case == "mix":
-        kw = dict(n_samples=32, n_importance=24, n_outside=0, up_sample_steps=5, perturb=1.0,
-                  upsampling_type="mix", use_norm_grad_for_cosine=True)
-    else:
-        kw = dict(n_samples=32, n_importance=0, n_outside=0, up_sample_steps=1, perturb=1.0)
-    r = _renderer(rr, mods, **kw)
-    out_ref = r.render(rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=0.7,
-                       perturb_overwrite=0, flip_saturation=0.9)
+def _rays():
+    return synth.make_rays(synth.make_scene("tiny"), 0, 48, seed=5)
+
+
+@pytest.mark.parametrize("case", list(G.RENDER_CASES))
+def test_render_matches_reference(gold, sds, case):
+    rays = _rays()
+    kw = G.RENDER_CASES[case]
     cfg = O.RenderCfg(n_samples=kw["n_samples"], n_importance=kw["n_importance"], n_outside=kw["n_outside"],
                       up_sample_steps=kw["up_sample_steps"], upsampling_type=kw.get("upsampling_type", "classical"),
                       use_norm_grad_for_cosine=kw.get("use_norm_grad_for_cosine", False))
-    nets = oracle_nets(state_dicts(mods), requires_grad=True)
+    nets = oracle_nets(sds, requires_grad=True)
     out = O.render(nets, cfg, rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=0.7,
                    flip_saturation=0.9)
-    for k in ["z_vals", "color", "color_base", "weights", "depth", "udf", "gradients", "normals", "vis_prob",
-              "alpha", "weight_sum", "weight_sum_fg_bg", "gradient_error", "gradient_error_near_surface",
-              "sparse_error", "true_cos", "alpha_occ"]:
-        assert _maxrel(out[k].detach(), out_ref[k].detach()) < 2e-6, k
+    for k in G.RENDER_KEYS:
+        assert _maxrel(out[k].detach(), torch.from_numpy(gold[f"render_{case}_out_{k}"])) < 2e-6, k
 
     # parameter gradients of a runner-like loss
-    def loss_of(o):
-        return ((o["color"] - rays["true_rgb"]).abs().mean() + 0.5 * (o["color_base"] - rays["true_rgb"]).abs().mean()
-                + 0.1 * o["gradient_error"] + 0.01 * o["gradient_error_near_surface"] + 0.001 * o["sparse_error"])
-
-    for m in mods.values():
-        m.zero_grad()
-    loss_of(out_ref).backward()
-    loss_of(out).backward()
-    for net, key in [("udf", "udf"), ("color", "color"), ("var", "var"), ("beta", "beta")]:
-        for (n, p) in mods[net].named_parameters():
-            if p.grad is None:
-                continue
-            g = getattr(nets, key)[n].grad
-            assert g is not None, n
-            assert _maxrel(g, p.grad) < 5e-5, (net, n)
-    if kw["n_outside"] > 0:
-        for (n, p) in mods["nerf"].named_parameters():
-            assert _maxrel(nets.nerf[n].grad, p.grad) < 5e-5, n
+    G.runner_loss(out, rays["true_rgb"]).backward()
+    ref = G.dequantize(np.load(os.path.join(HERE, "golden", f"ref_vs_reference_grads_{case}.npz")))
+    nets_with_grads = {k.split("_", 1)[0] for k in ref}
+    assert {"udf", "color", "var", "beta"} <= nets_with_grads
+    assert ("nerf" in nets_with_grads) == (kw["n_outside"] > 0)
+    for k, entry in ref.items():
+        net, n = k.split("_", 1)
+        g = getattr(nets, net)[n].grad
+        assert g is not None, k
+        G.assert_quantized(g, entry, G.RENDER_GRAD_TOL, k)     # max|g - ref| / max(1, max|ref|) < 5e-5
 
 
-@pytest.mark.parametrize("case", ["classical_bg", "flat"])
-def test_jittered_sampling_matches_reference(ref, case):
+@pytest.mark.parametrize("case", G.JITTER_CASES)
+def test_jittered_sampling_matches_reference(gold, sds, case):
     """perturb = 1 (what every training step -- and bench.py's timed step -- runs): the reference draws `t_rand - 0.5`
     for the coarse z and a stratified `lower + (upper - lower) * rand` for the outside samples from the default generator
-    (udf_renderer_blending.py:617-627).  Replaying the same draws into the oracle's `t_rand` / `t_rand_out` inputs must give
-    the reference's samples and colours."""
-    rf, rr, rl, mods = ref
-    scene = synth.make_scene("tiny")
-    rays = synth.make_rays(scene, 0, 48, seed=5)
-    if case == "classical_bg":
-        kw = dict(n_samples=32, n_importance=20, n_outside=8, up_sample_steps=5, perturb=1.0)
-    else:
-        kw = dict(n_samples=32, n_importance=0, n_outside=0, up_sample_steps=1, perturb=1.0)
-    r = _renderer(rr, mods, **kw)
-    torch.manual_seed(77)
-    out_ref = r.render(rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=0.7,
-                       perturb_overwrite=-1, flip_saturation=0.9)
+    (udf_renderer_blending.py:617-627), after torch.manual_seed(77).  Replaying the same draws into the oracle's `t_rand` /
+    `t_rand_out` inputs must give the reference's samples and colours."""
+    rays = _rays()
+    kw = G.RENDER_CASES[case]
     torch.manual_seed(77)                      # the same draws, in the reference's order and shapes
     t_rand = torch.rand([48, 1]) - 0.5
     t_out = torch.rand([kw["n_outside"]]) if kw["n_outside"] > 0 else None
     cfg = O.RenderCfg(n_samples=kw["n_samples"], n_importance=kw["n_importance"], n_outside=kw["n_outside"],
                       up_sample_steps=kw["up_sample_steps"])
-    nets = oracle_nets(state_dicts(mods))
+    nets = oracle_nets(sds)
     with torch.no_grad():
         out = O.render(nets, cfg, rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=0.7,
                        flip_saturation=0.9, t_rand=t_rand, t_rand_out=t_out)
@@ -103,61 +94,49 @@ def test_jittered_sampling_matches_reference(ref, case):
         plain = O.render(nets, cfg, rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=0.7,
                          flip_saturation=0.9)
     assert float((plain["z_vals"] - out["z_vals"]).abs().max()) > 1e-3
-    for k in ["z_vals", "color", "color_base", "weights", "depth", "udf", "weight_sum", "weight_sum_fg_bg"]:
-        assert _maxrel(out[k].detach(), out_ref[k].detach()) < 2e-6, k
+    for k in G.JITTER_KEYS:
+        assert _maxrel(out[k].detach(), torch.from_numpy(gold[f"jitter_{case}_out_{k}"])) < 2e-6, k
 
 
-def test_analytic_gradient(ref):
-    rf, rr, rl, mods = ref
-    x = torch.randn(257, 3) * 0.6
-    nets = oracle_nets(state_dicts(mods))
-    g_ref = mods["udf"].gradient(x.clone()).squeeze(1).detach()
+def test_analytic_gradient(gold, sds):
+    x = torch.from_numpy(gold["agrad_x"])
+    g_ref = torch.from_numpy(gold["agrad_g"])
+    nets = oracle_nets(sds)
     g1 = O.udf_gradient(nets.udf, x, create_graph=False)
     g2 = O.udf_gradient_analytic(nets.udf, x)
     assert _maxrel(g1, g_ref) < 1e-6
     assert _maxrel(g2, g_ref) < 2e-5
 
 
-def test_blending_and_loss_match_reference(ref):
-    rf, rr, rl, mods = ref
-    scene = synth.make_scene("tiny")
-    rays = synth.make_rays(scene, 0, 24, seed=9, margin=6)
-    src = synth.make_source_views(scene, 0, 8)
-    r = _renderer(rr, mods, n_samples=24, n_importance=12, n_outside=0, up_sample_steps=3, perturb=1.0,
-                  upsampling_type="mix", use_norm_grad_for_cosine=True, h_patch_size=3)
-    out_ref = r.render(rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=1.0,
-                       perturb_overwrite=0, flip_saturation=1.0, color_maps=src["color_maps"], w2cs=src["w2cs"],
-                       intrinsics=src["intrinsics"], query_c2w=src["query_c2w"], rays_uv=rays["rays_uv"].clone())
+def test_blending_and_loss_match_reference(gold, sds):
+    rays, src = G.blend_inputs()
     cfg = O.RenderCfg(n_samples=24, n_importance=12, n_outside=0, up_sample_steps=3, upsampling_type="mix",
                       use_norm_grad_for_cosine=True, h_patch_size=3)
-    nets = oracle_nets(state_dicts(mods))
+    nets = oracle_nets(sds)
     blend = dict(color_maps=src["color_maps"], w2cs=src["w2cs"], intrinsics=src["intrinsics"],
                  query_c2w=src["query_c2w"], rays_uv=rays["rays_uv"].clone())
     out = O.render(nets, cfg, rays["rays_o"], rays["rays_d"], rays["near"], rays["far"], cos_anneal_ratio=1.0,
                    flip_saturation=1.0, blend=blend)
+    ref = {k: torch.from_numpy(gold["blend_out_" + k]) for k in G.BLEND_KEYS}
     for k in ["color", "color_pixel", "patch_colors", "patch_mask", "weights"]:
-        assert _maxrel(out[k].detach(), out_ref[k].detach()) < 5e-6, k
+        assert _maxrel(out[k].detach(), ref[k]) < 5e-6, k
 
-    g = torch.Generator().manual_seed(3)
-    gt_patch = torch.rand(24, 49, 3, generator=g)
-    pmask = (out_ref["patch_mask"].detach() > 0.3).reshape(-1, 1)
-    crit = rl.ColorLoss(color_base_weight=1.0, color_weight=1.0, color_pixel_weight=0.5, color_patch_weight=0.2,
-                        pixel_loss_type="l1", patch_loss_type="ssim", h_patch_size=3)
-    l_ref = crit(out_ref["color_base"], out_ref["color"], rays["true_rgb"], out_ref["color_pixel"], rays["mask"],
-                 out_ref["patch_colors"], gt_patch, pmask.clone())
+    gt_patch = torch.rand(24, 49, 3, generator=torch.Generator().manual_seed(3))
+    pmask = (ref["patch_mask"] > 0.3).reshape(-1, 1)
     l = O.color_loss(1.0, 1.0, 0.5, 0.2, 3, out["color_base"], out["color"], rays["true_rgb"], out["color_pixel"],
                      rays["mask"], out["patch_colors"], gt_patch, pmask.clone())
-    for k in l_ref:
-        assert abs(float(l[k]) - float(l_ref[k])) < 1e-5 * max(1.0, abs(float(l_ref[k]))), k
+    keys = [k[len("blend_closs_"):] for k in gold.files if k.startswith("blend_closs_")]
+    assert "loss" in keys
+    for k in keys:
+        l_ref = float(gold["blend_closs_" + k])
+        assert abs(float(l[k]) - l_ref) < 1e-5 * max(1.0, abs(l_ref)), k
 
 
-@pytest.mark.parametrize("kind", ["l1", "ssd", "ncc", "ssim"])
-def test_patch_loss_types_match_reference(ref, kind):
+@pytest.mark.parametrize("kind", G.PATCH_KINDS)
+def test_patch_loss_types_match_reference(gold, kind):
     """the oracle's restatement of every ColorPatchLoss error type (loss/loss.py:56-84, loss/patch_metric.py:44-67)
     against the reference class, values and gradients w.r.t. the predicted patches."""
-    rl = ref[2] if len(ref) > 2 else None
-    import importlib
-    rl = rl or importlib.import_module("loss.loss")
+    ref = G.dequantize(gold, "patch_grad_")
     g = torch.Generator().manual_seed(17)
     for hps in (3, 5):
         npx = (2 * hps + 1) ** 2
@@ -165,65 +144,53 @@ def test_patch_loss_types_match_reference(ref, kind):
         pred = torch.rand(N, npx, 3, generator=g)
         gt = (pred + 0.1 * torch.randn(N, npx, 3, generator=g)).clamp(0, 1)
         mask = torch.rand(N, 1, generator=g) > 0.2
-        crit = rl.ColorPatchLoss(kind, hps)
-        p1 = pred.clone().requires_grad_(True)
-        l_ref = crit(p1, gt, mask.clone())
-        l_ref.backward()
+        l_ref = float(gold[f"patch_{kind}_{hps}_loss"])
         p2 = pred.clone().requires_grad_(True)
         l = O.patch_loss(p2, gt, mask.clone(), hps, kind=kind)
         l.backward()
-        assert abs(float(l) - float(l_ref)) < 1e-5 * max(1.0, abs(float(l_ref))), (kind, hps)
-        assert _maxrel(p2.grad, p1.grad) < 1e-4, (kind, hps)
+        assert abs(float(l) - l_ref) < 1e-5 * max(1.0, abs(l_ref)), (kind, hps)
+        G.assert_quantized(p2.grad, ref[f"{kind}_{hps}"], G.PATCH_GRAD_TOL, (kind, hps))     # max rel. 1e-4
 
 
-RN_CASES = [dict(mode="idr", d_in=12, multires_view=4, squeeze_out=True, blending_cand_views=0),
-            dict(mode="no_normal", d_in=6, multires_view=4, squeeze_out=True, blending_cand_views=10),
-            dict(mode="no_view_dir", d_in=9, multires_view=0, squeeze_out=False, blending_cand_views=0)]
+def _assert_reference_state_dict(gold, prefix, sd):
+    """the same keys, in the same order, and bit for bit the same tensors (sha-256 of dtype, shape and bytes) as the
+    reference class's seeded state_dict"""
+    assert list(sd) == [str(k) for k in gold[f"{prefix}_keys"]]
+    for (k, v), d in zip(sd.items(), gold[f"{prefix}_digests"]):
+        assert G.digest(v) == str(d), k
 
 
-@pytest.mark.parametrize("case", RN_CASES, ids=[c["mode"] for c in RN_CASES])
-def test_plain_rendering_network_matches_reference(ref, case):
+@pytest.mark.parametrize("case", G.RN_CASES, ids=[c["mode"] for c in G.RN_CASES])
+def test_plain_rendering_network_matches_reference(gold, case):
     """oracle restatement of RenderingNetwork (fields.py:325-397; unused by the runner, kept for the call surface)
-    against the reference class, and the drop-in class's state_dict layout against the reference's."""
-    rf = ref[0]
+    against the reference class's outputs, and the drop-in class's seeded state_dict against the reference's."""
     from neuraludf_amd.models import fields as nf
     kw = dict(d_feature=64, d_out=3, d_hidden=48, n_layers=3, weight_norm=True, **case)
     torch.manual_seed(3)
-    net = rf.RenderingNetwork(**kw)
-    torch.manual_seed(3)
-    mine = nf.RenderingNetwork(**kw)
-    sd, sd2 = net.state_dict(), mine.state_dict()
-    assert list(sd) == list(sd2) and all(torch.equal(sd[k], sd2[k]) for k in sd)
+    sd = nf.RenderingNetwork(**kw).state_dict()
+    _assert_reference_state_dict(gold, "rn_" + case["mode"], sd)        # so `sd` IS the reference's seeded weights
     g = torch.Generator().manual_seed(1)
     P = 50
     pts, nrm, dirs = (torch.randn(P, 3, generator=g) for _ in range(3))
     feat = torch.randn(P, 64, generator=g)
-    out = net(pts, nrm, dirs, feat)
-    color, extra = O.rendering_forward({k: v.detach() for k, v in sd.items()}, pts, nrm, dirs, feat, mode=case["mode"],
-                                       multires_view=case["multires_view"], squeeze_out=case["squeeze_out"])
+    color, extra = O.rendering_forward(sd, pts, nrm, dirs, feat, mode=case["mode"], multires_view=case["multires_view"],
+                                       squeeze_out=case["squeeze_out"])
+    out0 = torch.from_numpy(gold[f"rn_{case['mode']}_out0"])
+    assert _maxrel(color, out0) < 1e-6
     if case["blending_cand_views"] > 0:
-        assert _maxrel(color, out[0].detach()) < 1e-6 and _maxrel(extra, out[1].detach()) < 1e-6
+        assert _maxrel(extra, torch.from_numpy(gold[f"rn_{case['mode']}_out1"])) < 1e-6
     else:
-        assert _maxrel(color, out.detach()) < 1e-6 and extra.shape[1] == 0
+        assert extra.shape[1] == 0 and f"rn_{case['mode']}_out1" not in gold.files
 
 
 @pytest.mark.parametrize("inside_outside", [False, True])
-def test_sdf_network_initialises_like_the_reference(ref, inside_outside):
+def test_sdf_network_initialises_like_the_reference(gold, inside_outside):
     """SDFNetwork (fields.py:10-112, dead code in the runner but part of the module's surface): same parameter names, order and
     seeded values as the reference class, both camera conventions of the geometric initialisation."""
-    import contextlib
-    import io
     from neuraludf_amd.models import fields
-    rf = ref[0]
-    kw = dict(d_in=3, d_out=257, d_hidden=64, n_layers=5, skip_in=(3,), multires=4, bias=0.6, scale=1.5, geometric_init=True,
-              weight_norm=True, inside_outside=inside_outside)
     torch.manual_seed(3)
     with contextlib.redirect_stdout(io.StringIO()):
-        a = rf.SDFNetwork(**kw)
-    torch.manual_seed(3)
-    b = fields.SDFNetwork(**kw)
-    sa, sb = a.state_dict(), b.state_dict()
-    assert list(sa.keys()) == list(sb.keys())
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
-    a.load_state_dict(b.state_dict())
+        b = fields.SDFNetwork(**G.SDF_KW, inside_outside=inside_outside)
+    sb = b.state_dict()
+    _assert_reference_state_dict(gold, f"sdf_{int(inside_outside)}", sb)
+    b.load_state_dict({k: v.clone() for k, v in sb.items()})
