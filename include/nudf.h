@@ -817,6 +817,44 @@ typedef struct NudfRayBatch {
 } NudfRayBatch;
 int nudf_gen_ray_batch(const NudfRayBatch* args, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * MeshUDF open-surface extraction from a dense UDF grid (MeshUDF, Guillard et al. 2022): replaces the Cython mesher
+ * custom_mc/_marching_cubes_lewiner_cy.pyx udf_mc_lewiner (:1115-) that extract_mesh.py get_mesh_udf_fast (:169-354)
+ * calls from Runner.extract_udf_mesh (exp_runner_blending.py:763-800).  Pseudo-signs are chosen per cell with no
+ * propagation between cells (the reference's serial sign-propagation queue is not reproduced): corner r = the corner of
+ * largest U (lowest index on ties) is `+`, corner c is `+` iff dot(G_r, G_c) >= 0 in float64.  A cell is active when the
+ * fp32 mean of its 8 corner values is < mean_thr and their max is <= max_thr (pyx :1157-1158).  The 256-case table is
+ * generated by neuraludf_amd/mc_tables.py (csrc/mc_tables.inc).  Three launches; the scans and compactions between them
+ * are the caller's (deterministic integer prefix sums).  Grid: N^3 points x-major, lin(i, j, k) = (i N + j) N + k;
+ * cell (i, j, k) < N - 1 has lowest corner lin(i, j, k) and compact index (i (N-1) + j) (N-1) + k; edge id
+ * 3 lin(lower end) + axis.  3 <= N <= 1024.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfMeshUDF {
+  const float* U;            /* [N, N, N] UDF values                                                                 */
+  const float* G;            /* [N, N, N, 3] UDF gradients (read at the corners of active cells only)                */
+  const float* axes;         /* [3, N] grid coordinate of each index, per axis                                      */
+  uint8_t* cell_case;        /* [(N-1)^3] case index (bit c set: corner c is `-`), 0 for inactive cells (classify)    */
+  uint8_t* cell_ntri;        /* [(N-1)^3] triangles of the cell (classify)                                           */
+  uint8_t* edge_flag;        /* [3 N^3] zeroed by the caller; classify stores 1 at every sign-change edge of an active
+                                cell that emits triangles                                                            */
+  const int64_t* cells;      /* [n_cells] compact indices of the cells with triangles, ascending (emit)               */
+  const int64_t* face_off;   /* [n_cells] exclusive prefix sum of their triangle counts (emit)                       */
+  const int64_t* edge_scan;  /* [3 N^3] inclusive prefix sum of edge_flag: vertex of edge e = edge_scan[e] - 1 (emit)  */
+  int64_t* faces;            /* [F, 3] vertex indices (emit)                                                         */
+  const int64_t* edges;      /* [n_edges] ids of the flagged edges, ascending (vertices)                             */
+  float* verts;              /* [n_edges, 3] vertex positions at t = U_a / (U_a + U_b) from the lower end a (vertices) */
+  int64_t n_cells;
+  int64_t n_edges;
+  int64_t n_faces;           /* F: emit refuses a face_off that would write past faces[F]                           */
+  int32_t N;
+  float mean_thr;            /* 1.05 h, h = the largest grid spacing                                                */
+  float max_thr;             /* 1.74 h                                                                               */
+  int32_t pad_;
+} NudfMeshUDF;
+int nudf_meshudf_classify(const NudfMeshUDF* args, void* stream);   /* one thread per cell   */
+int nudf_meshudf_emit(const NudfMeshUDF* args, void* stream);       /* one thread per cell with triangles */
+int nudf_meshudf_vertices(const NudfMeshUDF* args, void* stream);   /* one thread per flagged edge */
+
 #ifdef __cplusplus
 }
 #endif

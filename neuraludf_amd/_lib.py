@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must be loaded before libnudf, see module docstring
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NUDF_LIB") or os.path.join(_HERE, "libnudf.so")      # NUDF_LIB: A/B builds of the library
-ABI_VERSION = 105         # nudf_version() of the include/nudf.h these ctypes structures mirror
+ABI_VERSION = 106         # nudf_version() of the include/nudf.h these ctypes structures mirror
 
 c_fp = C.c_void_p
 i32 = C.c_int32
@@ -191,6 +191,13 @@ class UnpackMulti(C.Structure):
     _fields_ = [("n_layers", i32), ("total_rows", i32), ("layer", UnpackLayer * PACK_MAX_LAYERS)]
 
 
+class MeshUDF(C.Structure):
+    _fields_ = [("U", c_fp), ("G", c_fp), ("axes", c_fp), ("cell_case", c_fp), ("cell_ntri", c_fp), ("edge_flag", c_fp),
+                ("cells", c_fp), ("face_off", c_fp), ("edge_scan", c_fp), ("faces", c_fp), ("edges", c_fp), ("verts", c_fp),
+                ("n_cells", C.c_int64), ("n_edges", C.c_int64), ("n_faces", C.c_int64), ("N", i32), ("mean_thr", f32),
+                ("max_thr", f32), ("pad_", i32)]
+
+
 # float offsets of the device loss-weight vector (include/nudf.h NUDF_LW_*)
 LW = dict(color_base=0, color=1, color_pixel=2, color_patch=3, igr=4, igr_ns=5, sparse=6, mask=7, color_sum=8)
 LW_COUNT = 16
@@ -214,6 +221,7 @@ SYMBOLS = [
     "nudf_gen_ray_batch", "nudf_color_loss_sums", "nudf_color_loss_finish",
     "nudf_step_loss_fwd", "nudf_step_loss_bwd", "nudf_col0_seed4",
     "nudf_blend_loss_prepare", "nudf_blend_loss_fwd", "nudf_blend_loss_bwd",
+    "nudf_meshudf_classify", "nudf_meshudf_emit", "nudf_meshudf_vertices",
 ]
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -278,6 +286,9 @@ _ARGTYPES = {
     "nudf_blend_loss_prepare": [C.POINTER(BlendLoss), _P],
     "nudf_blend_loss_fwd": [C.POINTER(BlendLoss), _P],
     "nudf_blend_loss_bwd": [C.POINTER(BlendLoss), _P],
+    "nudf_meshudf_classify": [C.POINTER(MeshUDF), _P],
+    "nudf_meshudf_emit": [C.POINTER(MeshUDF), _P],
+    "nudf_meshudf_vertices": [C.POINTER(MeshUDF), _P],
 }
 
 _lib = None

@@ -232,15 +232,20 @@ class _ErrorsFn(torch.autograd.Function):
 GRID_CHUNK_POINTS = 1 << 21      # points per field query: large launches (>= 32768 row tiles) instead of 64^3 blocks
 
 
-def _grid_query(bound_min, bound_max, resolution, query_func, device, channels):
+def _grid_axes(bound_min, bound_max, resolution, device):
+    """the grid's coordinates: per-axis ``linspace(bound_min, bound_max, resolution)`` on `device` -> [3, R]"""
+    return torch.stack([torch.linspace(float(bound_min[k]), float(bound_max[k]), int(resolution), device=device)
+                        for k in range(3)])
+
+
+def _grid_query_device(bound_min, bound_max, resolution, query_func, device, channels):
     """Dense-grid evaluation of a field, GPU-resident.  Same grid as the reference (per-axis
     ``linspace(bound_min, bound_max, resolution)``, x-major ordering) but the points are generated on the device in
-    slabs of whole x-planes (up to GRID_CHUNK_POINTS each) and the values land in one device volume that is copied to
-    the host once; the reference walks 64^3 blocks with a host meshgrid, an upload and a download per block
-    (models/udf_renderer_blending.py:16-49)."""
+    slabs of whole x-planes (up to GRID_CHUNK_POINTS each) and the values land in one device volume; the reference walks
+    64^3 blocks with a host meshgrid, an upload and a download per block (models/udf_renderer_blending.py:16-49)."""
     dev = torch.device(device)
     R = int(resolution)
-    axes = [torch.linspace(float(bound_min[k]), float(bound_max[k]), R, device=dev) for k in range(3)]
+    axes = _grid_axes(bound_min, bound_max, R, dev)
     shape = (R, R, R) if channels == 1 else (R, R, R, channels)
     vol = torch.empty(shape, dtype=torch.float32, device=dev)
     planes = max(1, (GRID_CHUNK_POINTS // (1 if channels == 1 else 4)) // (R * R))   # gradient queries keep activations
@@ -250,7 +255,12 @@ def _grid_query(bound_min, bound_max, resolution, query_func, device, channels):
         pts = torch.cat([xs[:, None, None].expand(len(xs), R * R, 1), yz.expand(len(xs), R * R, 2)], -1).reshape(-1, 3)
         val = query_func(pts).detach()
         vol[x0:x0 + len(xs)] = val.reshape((len(xs),) + shape[1:])
-    return vol.cpu().numpy()
+    return vol
+
+
+def _grid_query(bound_min, bound_max, resolution, query_func, device, channels):
+    """`_grid_query_device`, copied to the host once -> numpy volume"""
+    return _grid_query_device(bound_min, bound_max, resolution, query_func, device, channels).cpu().numpy()
 
 
 def extract_fields(bound_min, bound_max, resolution, query_func, device='cuda'):
@@ -734,6 +744,13 @@ class UDFRendererBlending:
                   'alpha_minus', 'mid_z_vals', 'dists', 'alpha_occ', 'raw_occ']:
             ret[k] = e(0, S, 3) if k == 'gradients_flip' else e(0, S)
         return ret
+
+    def extract_udf_geometry(self, bound_min, bound_max, resolution, dist_threshold_ratio=1.0):
+        """open-surface mesh of the UDF (neuraludf_amd.meshing.extract_udf_mesh, MeshUDF on the GPU; the reference's
+        extract_mesh.get_mesh_udf_fast) -> (vertices np.float32 [V, 3], faces np.int64 [F, 3]) in the box's units"""
+        from .. import meshing
+        return meshing.extract_udf_mesh(self.udf_network, resolution, bound_min, bound_max,
+                                        dist_threshold_ratio=dist_threshold_ratio)
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.01, device='cpu'):
         """(:757-760) -> (vertices, triangles).  The grid query runs on the network's GPU whatever `device` says (the
