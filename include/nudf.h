@@ -855,6 +855,70 @@ int nudf_meshudf_classify(const NudfMeshUDF* args, void* stream);   /* one threa
 int nudf_meshudf_emit(const NudfMeshUDF* args, void* stream);       /* one thread per cell with triangles */
 int nudf_meshudf_vertices(const NudfMeshUDF* args, void* stream);   /* one thread per flagged edge */
 
+/* ------------------------------------------------------------------------------------
+ * Point-cloud geometry of the Chamfer evaluation (neuraludf_amd/evaluation.py): replaces the mesh sampling, the radius
+ * down-sampling and the two sklearn KD-tree nearest-neighbour sweeps of evaluation/eval_dtu_python.py (:205-370) and
+ * eval_deepfashion_python.py (:62-215).  All coordinates are float64 and every expression follows the reference's
+ * (numpy's / sklearn's) operation order without contraction, so the results equal a numpy restatement bit for bit.
+ * One struct; each entry point reads the fields its comment names.
+ *   tri_count   one thread per face: tri_n[f] = points of face f (0 for faces the reference drops, cap + 1 when more
+ *               than cap);
+ *   tri_emit    one thread per face: its points at out[out_base + tri_off[f] ...];
+ *   keys        one thread per point: keys[s] = packed cell of pts[s] (21 bits per axis, clamped into the grid);
+ *   cells       one thread per occupied cell r: inserts cell_key[r] -> r into the hash (hash_key zeroed to -1 by the
+ *               caller; hash_cap a power of two >= 2 n_cells);
+ *   thin_round  one thread per point (pts, keys, rank, state in cell-sorted order): state 0 undecided, 1 keep, 2 drop;
+ *               adds 1 to *undecided for every point left undecided;
+ *   nearest     one thread per query: dist / idx [query_idx[t]] = the float64 distance to the nearest of pts and its
+ *               rank (lowest rank on ties), +inf / -1 when that is beyond bound.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfPointCloud {
+  const double* verts;       /* [n_verts, 3] mesh vertices (tri_*)                                                   */
+  const int64_t* faces;      /* [n_faces, 3] (tri_*)                                                                 */
+  int64_t* tri_n;            /* [n_faces] points per face (written by tri_count, read by tri_emit)                   */
+  const int64_t* tri_off;    /* [n_faces] exclusive prefix sum of tri_n (tri_emit)                                   */
+  double* out;               /* [n_out, 3] sampled points (tri_emit)                                                 */
+  int64_t n_verts;
+  int64_t n_faces;
+  int64_t n_out;
+  int64_t out_base;          /* row of the first triangle point (the vertices come first)                            */
+  int64_t cap;               /* largest point count the caller accepts                                              */
+  double density;            /* the reference's downsample_density                                                   */
+  const double* pts;         /* [n, 3] indexed points, cell-sorted for cells / thin_round / nearest                  */
+  int64_t n;
+  double origin[3];          /* lowest corner of the grid                                                            */
+  double cell;               /* cell edge                                                                            */
+  int32_t grid[3];           /* cells per axis, <= 2^21                                                              */
+  int32_t pad_;
+  int64_t* keys;             /* [n] packed cells (keys: written; thin_round: read)                                    */
+  const int64_t* cell_key;   /* [n_cells] the occupied cells, ascending                                              */
+  const int64_t* cell_start; /* [n_cells] first sorted point of each                                                 */
+  const int64_t* cell_count; /* [n_cells]                                                                            */
+  int64_t n_cells;
+  int64_t* hash_key;         /* [hash_cap] -1 = empty                                                                */
+  int64_t* hash_row;         /* [hash_cap]                                                                           */
+  int64_t hash_cap;
+  const int64_t* rank;       /* [n] position of each sorted point in the caller's order (shuffle rank / index)       */
+  uint8_t* state;            /* [n] thin_round                                                                       */
+  int32_t* undecided;        /* one counter, zeroed by the caller before each round                                  */
+  double r2;                 /* thin_round: radius * radius                                                          */
+  const double* query;       /* [n_query, 3] (nearest; cell-sorted for coherence)                                    */
+  const int64_t* query_idx;  /* [n_query] output row of each query                                                   */
+  int64_t n_query;
+  double bound;              /* distances beyond it are reported as +inf / -1                                        */
+  double box_bound2;         /* a query whose squared distance to [box_lo, box_hi] exceeds it is beyond bound        */
+  double box_lo[3];
+  double box_hi[3];
+  double* dist;              /* [n_query] float64 sqrt(((dx dx) + (dy dy)) + (dz dz))                               */
+  int64_t* idx;              /* [n_query]                                                                            */
+} NudfPointCloud;
+int nudf_pc_tri_count(const NudfPointCloud* args, void* stream);   /* one thread per face  */
+int nudf_pc_tri_emit(const NudfPointCloud* args, void* stream);    /* one thread per face  */
+int nudf_pc_keys(const NudfPointCloud* args, void* stream);        /* one thread per point */
+int nudf_pc_cells(const NudfPointCloud* args, void* stream);       /* one thread per occupied cell */
+int nudf_pc_thin_round(const NudfPointCloud* args, void* stream);  /* one thread per point */
+int nudf_pc_nearest(const NudfPointCloud* args, void* stream);     /* one thread per query */
+
 #ifdef __cplusplus
 }
 #endif

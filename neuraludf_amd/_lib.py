@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must be loaded before libnudf, see module docstring
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NUDF_LIB") or os.path.join(_HERE, "libnudf.so")      # NUDF_LIB: A/B builds of the library
-ABI_VERSION = 106         # nudf_version() of the include/nudf.h these ctypes structures mirror
+ABI_VERSION = 107         # nudf_version() of the include/nudf.h these ctypes structures mirror
 
 c_fp = C.c_void_p
 i32 = C.c_int32
@@ -198,6 +198,19 @@ class MeshUDF(C.Structure):
                 ("max_thr", f32), ("pad_", i32)]
 
 
+class PointCloud(C.Structure):
+    _fields_ = [("verts", c_fp), ("faces", c_fp), ("tri_n", c_fp), ("tri_off", c_fp), ("out", c_fp),
+                ("n_verts", C.c_int64), ("n_faces", C.c_int64), ("n_out", C.c_int64), ("out_base", C.c_int64),
+                ("cap", C.c_int64), ("density", C.c_double),
+                ("pts", c_fp), ("n", C.c_int64), ("origin", C.c_double * 3), ("cell", C.c_double), ("grid", i32 * 3),
+                ("pad_", i32), ("keys", c_fp), ("cell_key", c_fp), ("cell_start", c_fp), ("cell_count", c_fp),
+                ("n_cells", C.c_int64), ("hash_key", c_fp), ("hash_row", c_fp), ("hash_cap", C.c_int64),
+                ("rank", c_fp), ("state", c_fp), ("undecided", c_fp), ("r2", C.c_double),
+                ("query", c_fp), ("query_idx", c_fp), ("n_query", C.c_int64), ("bound", C.c_double),
+                ("box_bound2", C.c_double), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
+                ("dist", c_fp), ("idx", c_fp)]
+
+
 # float offsets of the device loss-weight vector (include/nudf.h NUDF_LW_*)
 LW = dict(color_base=0, color=1, color_pixel=2, color_patch=3, igr=4, igr_ns=5, sparse=6, mask=7, color_sum=8)
 LW_COUNT = 16
@@ -222,6 +235,7 @@ SYMBOLS = [
     "nudf_step_loss_fwd", "nudf_step_loss_bwd", "nudf_col0_seed4",
     "nudf_blend_loss_prepare", "nudf_blend_loss_fwd", "nudf_blend_loss_bwd",
     "nudf_meshudf_classify", "nudf_meshudf_emit", "nudf_meshudf_vertices",
+    "nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells", "nudf_pc_thin_round", "nudf_pc_nearest",
 ]
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -289,6 +303,8 @@ _ARGTYPES = {
     "nudf_meshudf_classify": [C.POINTER(MeshUDF), _P],
     "nudf_meshudf_emit": [C.POINTER(MeshUDF), _P],
     "nudf_meshudf_vertices": [C.POINTER(MeshUDF), _P],
+    **{n: [C.POINTER(PointCloud), _P] for n in ("nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells",
+                                                "nudf_pc_thin_round", "nudf_pc_nearest")},
 }
 
 _lib = None

@@ -1,0 +1,542 @@
+"""Chamfer evaluation of meshes on the GPU: the DTU and DeepFashion3D protocols of the reference's
+evaluation/eval_dtu_python.py (its `__main__` loop, :205-370) and evaluation/eval_deepfashion_python.py (:62-215), with
+their open3d file I/O, Python down-sampling loop and sklearn KD-trees replaced.
+
+    sample      sample_mesh         all vertices, then sample_single_tri's points of every triangle of non-zero area
+                                    (csrc/pointcloud.hip tri_count / tri_emit, a torch int64 scan between them)
+    shuffle     radius_downsample   a seeded torch permutation (the reference's shuffle is unseeded)
+    thin        thin                the reference's greedy radius thinning (radius_neighbors + mask loop) as rounds of a
+                                    lexicographically-first maximal independent set (thin_round)
+    masks       chamfer_dtu         the ObsMask / bounding-box / ground-plane selection in the reference's mixed precision
+    distances   nearest             exact float64 nearest neighbours (kneighbors, n_neighbors=1) by rings of hashed cells
+    metrics     chamfer_dtu, chamfer_deepfashion    means below max_dist, precision / recall / F-score, the log file
+    files       read_ply / write_points_ply (neuraludf_amd.meshing), load_dtu_obs
+
+Given the permutation, every step is the reference's float64 computation in its operation order, so the points, the
+masks and the distances equal a numpy restatement bit for bit (tests/pointcloud_ref.py); only the means are summed in
+torch's order.  Mesh units are the caller's: for DTU the mesh must be in world space (millimetres), i.e.
+`extract_udf_mesh(..., scale_mat=...)` / `Trainer.extract_udf_mesh(world_space=True, scale_mat=...)`.
+
+Empty inputs: an empty GT cloud, an empty data cloud and (DTU) no data point inside the ObsMask or no GT point above the
+plane raise ValueError (sklearn raises there); a mean with no distance below max_dist is NaN, as numpy gives.
+Non-finite points raise ValueError before thinning or a nearest-neighbour search (sklearn refuses them too).
+
+    python -m neuraludf_amd.evaluation {dtu,deepfashion} --data X.ply --gt Y.ply [--mode mesh|pcd]
+        [--dataset_dir D --scan N] [--downsample_density ...] [--patch_size ...] [--max_dist ...]
+        [--visualize_threshold ...] [--vis_out_dir ...] [--no_vis] [--log ...] [--seed 0]
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr
+
+MAX_POINTS = 1 << 28            # largest sampled cloud accepted (24 B per point, plus the index: about 20 GB)
+AXIS_CELLS = 1 << 21            # cells per axis of the packed cell key
+THIN_CELL_SLACK = 1.0 + 2.0 ** -19   # thinning cell / radius: the 27-cell window survives the rounding of cell coordinates
+NEAREST_POINTS_PER_CELL = 16    # target points per occupied cell of the nearest-neighbour index (measured: DESIGN.md §4.9)
+KEEP = 1
+
+PROTOCOLS = {
+    "dtu": dict(downsample_density=0.2, patch_size=60.0, max_dist=20.0, visualize_threshold=10.0, thresholds=(1.0, 2.0),
+                decimals=3),
+    "deepfashion": dict(downsample_density=0.002, patch_size=60.0, max_dist=0.1, visualize_threshold=0.01,
+                        thresholds=(0.001, 0.002), decimals=6),
+}
+
+
+# ---- argument checks -------------------------------------------------------------------------------------------------
+def _device(*ts):
+    """the device of the first GPU tensor among ts, else the current GPU"""
+    for t in ts:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.device
+    return torch.device("cuda")
+
+
+def _shape3(p, name):
+    """p as a floating-point [N, 3] tensor (not moved); ValueError otherwise"""
+    t = torch.as_tensor(p) if not isinstance(p, torch.Tensor) else p
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name} must be [N, 3] (got {tuple(t.shape)})")
+    if not t.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point array (got {t.dtype})")
+    return t
+
+
+def _points(p, name, dev, finite=True):
+    """-> contiguous float64 [N, 3] on dev"""
+    t = _shape3(p, name).to(device=dev, dtype=torch.float64).contiguous()
+    if finite and t.numel() and not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name} holds non-finite coordinates")
+    return t
+
+
+def _positive(v, name, allow_inf=False):
+    v = float(v)
+    if not (v > 0 and (allow_inf or math.isfinite(v))):
+        raise ValueError(f"{name} must be a {'' if allow_inf else 'finite '}positive number (got {v})")
+    return v
+
+
+def _grid_size(lo, hi, cell):
+    """(cell, grid) with every axis's cell count within the 21-bit key (the cell grows when it would not fit)"""
+    ext = max(h - l for l, h in zip(lo, hi))
+    cell = max(cell, ext / (AXIS_CELLS - 4))
+    if not cell > 0:
+        cell = 1.0
+    grid = [min(int(math.floor((h - l) / cell)) + 2, AXIS_CELLS) for l, h in zip(lo, hi)]
+    return cell, grid
+
+
+# ---- mesh sampling ---------------------------------------------------------------------------------------------------
+def sample_mesh(vertices, faces, density, *, max_points=MAX_POINTS):
+    """the reference's mesh sampling (eval_dtu_python.py:225-258): every vertex, then for each triangle of non-zero area
+    in triangle order the points (v1 c0 + v2 c1) + t0 of its (n1 + 1) x (n2 + 1) lattice with c0 + c1 < 1, all in float64
+    with numpy's operation order.  vertices [V, 3] (NaN allowed: its triangles drop out, as in the reference; +-inf is
+    refused), faces [F, 3] integer indices.  -> points [V + M, 3] float64 on the GPU.  Raises ValueError when the cloud
+    would exceed max_points (a tiny density on a big mesh)."""
+    density = _positive(density, "density")
+    max_points = int(max_points)
+    _shape3(vertices, "vertices")
+    f = torch.as_tensor(faces) if not isinstance(faces, torch.Tensor) else faces
+    if f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() or f.is_complex() or f.dtype == torch.bool:
+        raise ValueError(f"faces must be an integer [F, 3] array (got {tuple(f.shape)}, {f.dtype})")
+    dev = _device(vertices, faces)
+    v = _points(vertices, "vertices", dev, finite=False)
+    if bool(torch.isinf(v).any()):
+        raise ValueError("vertices hold infinite coordinates")
+    f = f.to(device=dev, dtype=torch.int64).contiguous()
+    nv, nf = v.shape[0], f.shape[0]
+    if nf and (int(f.min()) < 0 or int(f.max()) >= nv):
+        raise ValueError(f"face index out of range [0, {nv})")
+    if nv > max_points:
+        raise ValueError(f"{nv} vertices exceed max_points={max_points}")
+    if nf == 0:
+        return v.clone()
+    tri_n = torch.empty(nf, dtype=torch.int64, device=dev)
+    d = _lib.PointCloud(verts=ptr(v), faces=ptr(f), tri_n=ptr(tri_n), n_verts=nv, n_faces=nf, cap=max_points - nv,
+                        density=density)
+    call("nudf_pc_tri_count", d)
+    ends = torch.cumsum(tri_n, 0)
+    m = int(ends[-1])
+    if nv + m > max_points:
+        raise ValueError(f"sampling at density {density} gives more than max_points={max_points} points: "
+                         "raise the density or max_points")
+    out = torch.empty((nv + m, 3), dtype=torch.float64, device=dev)
+    out[:nv] = v
+    off = ends - tri_n
+    d.tri_off, d.out, d.n_out, d.out_base = ptr(off), ptr(out), nv + m, nv
+    call("nudf_pc_tri_emit", d)
+    return out
+
+
+# ---- the cell index --------------------------------------------------------------------------------------------------
+class _CellIndex:
+    """points sorted by packed cell key (stable: by index inside a cell), the occupied-cell table and its hash"""
+
+    def __init__(self, pts, cell, lo=None, hi=None):
+        dev = pts.device
+        if lo is None:
+            lo, hi = pts.min(0).values.tolist(), pts.max(0).values.tolist()
+        self.lo, self.hi = lo, hi
+        self.cell, self.grid = _grid_size(lo, hi, cell)
+        n = pts.shape[0]
+        self.d = _lib.PointCloud(n=n, cell=self.cell)
+        self.d.origin[:] = lo
+        self.d.grid[:] = self.grid
+        keys = self.keys_of(pts)
+        skeys, order = torch.sort(keys, stable=True)
+        self.keys, self.rank = skeys, order
+        self.pts = pts[order].contiguous()
+        ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
+        self.cell_key, self.cell_count = ukeys.contiguous(), counts.contiguous()
+        self.cell_start = (torch.cumsum(counts, 0) - counts).contiguous()
+        nc = ukeys.numel()
+        cap = 1 << max(1, (2 * nc - 1).bit_length())
+        self.hash_key = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        self.hash_row = torch.empty(cap, dtype=torch.int64, device=dev)
+        d = self.d
+        d.pts, d.keys, d.rank = ptr(self.pts), ptr(self.keys), ptr(self.rank)
+        d.cell_key, d.cell_start, d.cell_count, d.n_cells = ptr(self.cell_key), ptr(self.cell_start), ptr(counts), nc
+        d.hash_key, d.hash_row, d.hash_cap = ptr(self.hash_key), ptr(self.hash_row), cap
+        call("nudf_pc_cells", d)
+
+    def keys_of(self, pts):
+        keys = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
+        k = _lib.PointCloud(pts=ptr(pts), n=pts.shape[0], cell=self.cell, keys=ptr(keys))
+        k.origin[:] = self.lo
+        call("nudf_pc_keys", k)
+        return keys
+
+    @property
+    def n_cells(self):
+        return self.cell_key.numel()
+
+
+def _occupancy(pts, cell, lo, hi):
+    """mean points per occupied cell of edge `cell` (and the cell actually used)"""
+    idx = _CellIndex.__new__(_CellIndex)
+    idx.lo = lo
+    idx.cell, _ = _grid_size(lo, hi, cell)
+    keys = idx.keys_of(pts)
+    return pts.shape[0] / torch.unique(keys).numel(), idx.cell
+
+
+def nearest_cell_size(ref, target=NEAREST_POINTS_PER_CELL):
+    """cell edge of the nearest-neighbour index: `target` points per occupied cell on average.  Starts from the cube of the
+    box holding n / target cells and rescales twice by sqrt(target / measured), the law of a surface-like cloud."""
+    lo, hi = ref.min(0).values.tolist(), ref.max(0).values.tolist()
+    ext = max(h - l for l, h in zip(lo, hi))
+    n = ref.shape[0]
+    if not ext > 0 or n <= target:
+        return _grid_size(lo, hi, ext if ext > 0 else 1.0)[0]
+    cell = ext / max(1.0, (n / target) ** (1.0 / 3.0))
+    for _ in range(2):
+        m, cell = _occupancy(ref, cell, lo, hi)
+        cell *= math.sqrt(target / m)
+    return _grid_size(lo, hi, cell)[0]
+
+
+# ---- thinning --------------------------------------------------------------------------------------------------------
+def thin(points, radius, _info=None):
+    """the reference's radius down-sampling mask (eval_dtu_python.py:265-276) for points already in rank order: point i is
+    kept iff no kept point of lower index lies within `radius` (distance <= radius, boundary included, d^2 compared with
+    radius * radius as sklearn does).  -> keep [N] bool on the GPU.  (`_info`: a dict that receives the round count.)"""
+    r = _positive(radius, "radius")
+    _shape3(points, "points")
+    dev = _device(points)
+    p = _points(points, "points", dev)
+    n = p.shape[0]
+    if n == 0:
+        if _info is not None:
+            _info["rounds"] = 0
+        return torch.zeros(0, dtype=torch.bool, device=dev)
+    idx = _CellIndex(p, r * THIN_CELL_SLACK)
+    state = torch.zeros(n, dtype=torch.uint8, device=dev)
+    undecided = torch.zeros(1, dtype=torch.int32, device=dev)
+    d = idx.d
+    d.state, d.undecided, d.r2 = ptr(state), ptr(undecided), r * r
+    rounds = 0
+    while True:
+        undecided.zero_()
+        call("nudf_pc_thin_round", d)
+        rounds += 1
+        left = int(undecided.item())
+        if left == 0:
+            break
+        if rounds > n:                     # each round decides the lowest-ranked undecided point: cannot happen
+            raise RuntimeError(f"thinning did not finish in {n} rounds ({left} points undecided)")
+    keep = torch.empty(n, dtype=torch.bool, device=dev)
+    keep[idx.rank] = state == KEEP
+    if _info is not None:
+        _info["rounds"] = rounds
+    return keep
+
+
+def radius_downsample(points, radius, seed=0):
+    """shuffle (a seeded permutation) then thin: the reference's data_down, in shuffled order.
+    -> (points_down [K, 3] float64, info dict(perm [N] int64, keep [N] bool in shuffled order, rounds))"""
+    _positive(radius, "radius")
+    _shape3(points, "points")
+    dev = _device(points)
+    p = _points(points, "points", dev)
+    g = torch.Generator(device=dev)
+    g.manual_seed(int(seed))
+    perm = torch.randperm(p.shape[0], generator=g, device=dev)
+    shuffled = p[perm]
+    info = {}
+    keep = thin(shuffled, radius, _info=info)
+    info.update(perm=perm, keep=keep)
+    return shuffled[keep], info
+
+
+# ---- nearest neighbours ----------------------------------------------------------------------------------------------
+def nearest(query, ref, bound=math.inf, *, cell=None, _events=None):
+    """nearest point of `ref` for every point of `query` (sklearn kneighbors with n_neighbors=1): the float64 distance
+    sqrt(((dx dx) + (dy dy)) + (dz dz)) and the lowest index of ref achieving it.  Distances beyond `bound` are reported as
+    +inf with index -1 (they leave every metric of the protocols unchanged when bound >= max_dist and the thresholds).
+    -> (dist [M] float64, idx [M] int64) on the GPU.  (`cell`: the index's cell edge, by default nearest_cell_size.)"""
+    bound = _positive(bound, "bound", allow_inf=True)
+    if _shape3(ref, "ref").shape[0] == 0:
+        raise ValueError("the reference cloud is empty")
+    _shape3(query, "query")
+    dev = _device(query, ref)
+    q = _points(query, "query", dev)
+    r = _points(ref, "ref", dev)
+    m = q.shape[0]
+    dist = torch.empty(m, dtype=torch.float64, device=dev)
+    idx = torch.empty(m, dtype=torch.int64, device=dev)
+    if m == 0:
+        return dist, idx
+    index = _CellIndex(r, nearest_cell_size(r) if cell is None else _positive(cell, "cell"))
+    qkeys = index.keys_of(q)
+    qorder = torch.sort(qkeys, stable=True).indices
+    qs = q[qorder].contiguous()
+    d = index.d
+    d.query, d.query_idx, d.n_query, d.bound = ptr(qs), ptr(qorder), m, bound
+    d.box_bound2 = (bound * (1.0 + 1e-9)) ** 2 if math.isfinite(bound) else math.inf
+    d.box_lo[:], d.box_hi[:] = index.lo, index.hi
+    d.dist, d.idx = ptr(dist), ptr(idx)
+    if _events is not None:
+        _events["cell"] = index.cell
+        _events["cells"] = index.n_cells
+    call("nudf_pc_nearest", d)
+    return dist, idx
+
+
+# ---- the protocols ---------------------------------------------------------------------------------------------------
+def _data_cloud(data, density, dev):
+    if isinstance(data, (tuple, list)):
+        if len(data) != 2:
+            raise ValueError("data must be (vertices, faces) or [N, 3] points")
+        return sample_mesh(data[0], data[1], density)
+    return _points(data, "data", dev, finite=False)
+
+
+def _metrics(d2s, s2d, max_dist, thresholds):
+    def mean_below(d):
+        sel = d[d < max_dist]
+        return float(sel.mean()) if sel.numel() else math.nan
+
+    mean_d2s, mean_s2d = mean_below(d2s), mean_below(s2d)
+    out = dict(mean_d2gt=mean_d2s, mean_gt2d=mean_s2d, over_all=(mean_d2s + mean_s2d) / 2)
+    for k, t in enumerate(thresholds, 1):
+        p = int((d2s < t).sum()) / d2s.numel()
+        r = int((s2d < t).sum()) / s2d.numel()
+        out[f"precision_{k}"], out[f"recall_{k}"] = p, r
+        out[f"fscore_{k}"] = 2 * p * r / (p + r + 1e-6)
+    return out
+
+
+def vis_colors(dist, vis_dist, max_dist, n=None, where=None):
+    """the reference's error colours (float64 RGB in [0, 1]): blue everywhere (n rows), then at rows `where` (all rows
+    when None) the red-white ramp R a + W (1 - a), a = min(d, vis_dist) / vis_dist, and green where d >= max_dist"""
+    dev = dist.device
+    n = dist.numel() if n is None else n
+    c = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+    c[:, 2] = 1.0
+    a = dist.clamp(max=vis_dist) / torch.full_like(dist, vis_dist)   # a true division (torch multiplies by 1 / scalar)
+    ramp = torch.stack([1.0 * a + 1.0 * (1 - a), 0.0 * a + 1.0 * (1 - a), 0.0 * a + 1.0 * (1 - a)], -1)
+    ramp[dist >= max_dist] = torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64, device=dev)
+    if where is None:
+        c[:] = ramp
+    else:
+        c[where] = ramp
+    return c
+
+
+def _write_vis(vis_dir, name, data_down, data_color, gt, gt_color):
+    from .meshing import write_points_ply
+    os.makedirs(vis_dir, exist_ok=True)
+    write_points_ply(os.path.join(vis_dir, f"vis_{name}_d2gt.ply"), data_down.cpu().numpy(), data_color.cpu().numpy())
+    write_points_ply(os.path.join(vis_dir, f"vis_{name}_gt2d.ply"), gt.cpu().numpy(), gt_color.cpu().numpy())
+
+
+def _check_common(max_dist, thresholds, visualize_threshold):
+    max_dist = _positive(max_dist, "max_dist")
+    thresholds = tuple(_positive(t, "threshold") for t in thresholds)
+    visualize_threshold = _positive(visualize_threshold, "visualize_threshold")
+    return max_dist, thresholds, visualize_threshold
+
+
+def chamfer_deepfashion(data, gt, *, downsample_density=0.002, max_dist=0.1, thresholds=(0.001, 0.002), seed=0,
+                        vis_dir=None, name=None, visualize_threshold=0.01):
+    """the DeepFashion3D protocol (eval_deepfashion_python.py:62-215).  data: (vertices, faces) (mode mesh) or [N, 3]
+    points (mode pcd); gt: [G, 3] points.  -> dict with mean_d2gt, mean_gt2d, over_all, precision_k, recall_k, fscore_k
+    (k = 1, 2, ... per threshold), the point counts n_data, n_down, n_gt and thinning_rounds.  vis_dir: also write
+    vis_{name}_d2gt.ply / vis_{name}_gt2d.ply there."""
+    max_dist, thresholds, vis_t = _check_common(max_dist, thresholds, visualize_threshold)
+    density = _positive(downsample_density, "downsample_density")
+    if _shape3(gt, "gt").shape[0] == 0:
+        raise ValueError("the GT cloud is empty")
+    dev = _device(gt, *(data if isinstance(data, (tuple, list)) else (data,)))
+    stl = _points(gt, "gt", dev)
+    pcd = _data_cloud(data, density, dev)
+    if pcd.shape[0] == 0:
+        raise ValueError("the data cloud is empty")
+    down, info = radius_downsample(pcd, density, seed)
+    bound = max(max_dist, *thresholds)
+    d2s, _ = nearest(down, stl, bound)
+    s2d, _ = nearest(stl, down, bound)
+    out = _metrics(d2s, s2d, max_dist, thresholds)
+    out.update(n_data=pcd.shape[0], n_down=down.shape[0], n_gt=stl.shape[0], thinning_rounds=info["rounds"])
+    if vis_dir is not None:
+        _write_vis(vis_dir, name or "000", down, vis_colors(d2s, vis_t, max_dist), stl, vis_colors(s2d, vis_t, max_dist))
+    return out
+
+
+def dtu_masks(data_down, bb, res, obs_mask, patch_size):
+    """the reference's DTU selection (eval_dtu_python.py:277-291) in its mixed precision: BB cast to float32, the bounds
+    BB[0] - patch and BB[1] + 2 patch computed in float32, compared in float64; grid = around((p - BB[0]) / Res) in
+    float64 (half to even) cast to int32.  -> (inbound [K] bool, rows of data_down in data_in_obs [J] int64)"""
+    dev = data_down.device
+    bb32 = torch.as_tensor(np.asarray(bb, dtype=np.float32).reshape(2, 3), device=dev)
+    lo = bb32[0] - torch.tensor(float(patch_size), dtype=torch.float32, device=dev)
+    hi = bb32[1] + torch.tensor(float(patch_size) * 2, dtype=torch.float32, device=dev)
+    inbound = ((data_down >= lo.double()) & (data_down < hi.double())).all(1)
+    rows_in = torch.nonzero(inbound).reshape(-1)
+    rel = data_down[rows_in] - bb32[0].double()
+    g = torch.round(rel / torch.full_like(rel, float(res))).to(torch.int32)   # not rel * (1 / res): torch's scalar division
+    shape = torch.tensor(obs_mask.shape, dtype=torch.int32, device=dev)
+    grid_in = ((g >= 0) & (g < shape)).all(1)
+    gi = g[grid_in].long()
+    in_obs = obs_mask[gi[:, 0], gi[:, 1], gi[:, 2]]
+    return inbound, rows_in[grid_in][in_obs]
+
+
+def above_plane(points, plane):
+    """P . (x, y, z, 1) > 0, summed in numpy's order ((P0 x + P1 y) + P2 z) + P3"""
+    P = [float(v) for v in np.asarray(plane, dtype=np.float64).reshape(4)]
+    s = points[:, 0] * P[0] + points[:, 1] * P[1]
+    s = s + points[:, 2] * P[2]
+    return (s + P[3] * 1.0) > 0
+
+
+def chamfer_dtu(data, gt, obs_mask, bb, res, plane, *, downsample_density=0.2, patch_size=60, max_dist=20,
+                thresholds=(1, 2), seed=0, vis_dir=None, name=None, visualize_threshold=10):
+    """the DTU protocol (eval_dtu_python.py:205-370).  data: (vertices, faces) (mode mesh) or [N, 3] points (mode pcd),
+    in world space (mm); gt: [G, 3] STL points; obs_mask [X, Y, Z], bb [2, 3], res, plane [4]: load_dtu_obs.  d2gt runs
+    over the down-sampled points inside the ObsMask, gt2d over the GT points above the plane against every down-sampled
+    point inside the patch-extended box.  -> dict with mean_d2gt, mean_gt2d, over_all, precision_k, recall_k, fscore_k,
+    the point counts n_data, n_down, n_in, n_in_obs, n_gt, n_gt_above and thinning_rounds."""
+    max_dist, thresholds, vis_t = _check_common(max_dist, thresholds, visualize_threshold)
+    density = _positive(downsample_density, "downsample_density")
+    patch_size = float(patch_size)
+    if not math.isfinite(patch_size):
+        raise ValueError(f"patch_size must be finite (got {patch_size})")
+    res = _positive(np.asarray(res, dtype=np.float64).reshape(-1)[0], "res")
+    bb = np.asarray(bb)
+    if bb.size != 6:
+        raise ValueError(f"bb must be [2, 3] (got shape {bb.shape})")
+    obs = torch.as_tensor(np.asarray(obs_mask) if not isinstance(obs_mask, torch.Tensor) else obs_mask)
+    if obs.dim() != 3:
+        raise ValueError(f"obs_mask must be [X, Y, Z] (got {tuple(obs.shape)})")
+    if np.asarray(plane).size != 4:
+        raise ValueError("plane must hold 4 numbers")
+    if _shape3(gt, "gt").shape[0] == 0:
+        raise ValueError("the GT cloud is empty")
+    dev = _device(gt, *(data if isinstance(data, (tuple, list)) else (data,)))
+    obs = obs.to(dev) != 0
+    stl = _points(gt, "gt", dev)
+    pcd = _data_cloud(data, density, dev)
+    if pcd.shape[0] == 0:
+        raise ValueError("the data cloud is empty")
+    down, info = radius_downsample(pcd, density, seed)
+    inbound, rows_obs = dtu_masks(down, bb, res, obs, patch_size)
+    data_in = down[inbound]
+    data_in_obs = down[rows_obs]
+    above = above_plane(stl, plane)
+    stl_above = stl[above]
+    if data_in_obs.shape[0] == 0:
+        raise ValueError("no down-sampled data point lies inside the ObsMask")
+    if stl_above.shape[0] == 0:
+        raise ValueError("no GT point lies above the ground plane")
+    bound = max(max_dist, *thresholds)
+    d2s, _ = nearest(data_in_obs, stl, bound)
+    s2d, _ = nearest(stl_above, data_in, bound)
+    out = _metrics(d2s, s2d, max_dist, thresholds)
+    out.update(n_data=pcd.shape[0], n_down=down.shape[0], n_in=data_in.shape[0], n_in_obs=data_in_obs.shape[0],
+               n_gt=stl.shape[0], n_gt_above=stl_above.shape[0], thinning_rounds=info["rounds"])
+    if vis_dir is not None:
+        _write_vis(vis_dir, name or "000", down, vis_colors(d2s, vis_t, max_dist, down.shape[0], rows_obs), stl,
+                   vis_colors(s2d, vis_t, max_dist, stl.shape[0], torch.nonzero(above).reshape(-1)))
+    return out
+
+
+def load_dtu_obs(dataset_dir, scan):
+    """(obs_mask [X, Y, Z] bool np, bb [2, 3] np, res float, plane [4] float64 np) from
+    {dataset_dir}/ObsMask/ObsMask{scan}_10.mat (ObsMask, BB, Res) and Plane{scan}.mat (P), via scipy.io.loadmat"""
+    try:
+        from scipy.io import loadmat
+    except ImportError as e:
+        raise ImportError("load_dtu_obs reads MATLAB files with scipy.io.loadmat: install scipy, or pass obs_mask, bb, "
+                          "res and plane to chamfer_dtu directly") from e
+    m = loadmat(os.path.join(dataset_dir, "ObsMask", f"ObsMask{scan}_10.mat"))
+    p = loadmat(os.path.join(dataset_dir, "ObsMask", f"Plane{scan}.mat"))
+    return (np.asarray(m["ObsMask"]).astype(bool), np.asarray(m["BB"]), float(np.asarray(m["Res"]).reshape(-1)[0]),
+            np.asarray(p["P"], dtype=np.float64).reshape(4))
+
+
+# ---- CLI -------------------------------------------------------------------------------------------------------------
+def format_log(res, stem, decimals, units="mm"):
+    """the reference's log file: three lines of metrics rounded with np.round, then [stem]"""
+    def r(k):
+        return np.round(np.float64(res[k]), decimals)
+    return (f"over_all {r('over_all')} mean_d2gt {r('mean_d2gt')} mean_gt2d {r('mean_gt2d')} \n"
+            f"precision_1{units} {r('precision_1')} recall_1{units} {r('recall_1')} fscore_1{units} {r('fscore_1')} \n"
+            f"precision_2{units} {r('precision_2')} recall_2{units} {r('recall_2')} fscore_2{units} {r('fscore_2')} \n"
+            f"[{stem}] \n")
+
+
+def parse_log(text):
+    """{name: float} of a log written by format_log (the names without the units suffix), plus 'stem'"""
+    out = {}
+    lines = text.strip().splitlines()
+    for ln in lines[:3]:
+        tok = ln.split()
+        for k, v in zip(tok[::2], tok[1::2]):
+            out[k.replace("mm", "")] = float(v)
+    out["stem"] = lines[3].strip()[1:-1]
+    return out
+
+
+def main(argv=None):
+    from pathlib import Path
+    from .meshing import read_ply
+    ap = argparse.ArgumentParser(prog="python -m neuraludf_amd.evaluation", description=__doc__.split("\n\n")[0])
+    ap.add_argument("protocol", choices=sorted(PROTOCOLS))
+    ap.add_argument("--data", type=str, default="data_in.ply")
+    ap.add_argument("--gt", type=str, required=True, help="ground truth")
+    ap.add_argument("--scan", type=int, default=1)
+    ap.add_argument("--mode", type=str, default="mesh", choices=["mesh", "pcd"])
+    ap.add_argument("--dataset_dir", type=str, default=None, help="DTU: the directory holding ObsMask/")
+    ap.add_argument("--vis_out_dir", type=str, default=".")
+    ap.add_argument("--no_vis", action="store_true", help="do not write the visualisation clouds")
+    ap.add_argument("--downsample_density", type=float, default=None)
+    ap.add_argument("--patch_size", type=float, default=None)
+    ap.add_argument("--max_dist", type=float, default=None)
+    ap.add_argument("--visualize_threshold", type=float, default=None)
+    ap.add_argument("--log", type=str, default=None)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args(argv)
+    proto = PROTOCOLS[a.protocol]
+    for k in ("downsample_density", "patch_size", "max_dist", "visualize_threshold"):
+        if getattr(a, k) is None:
+            setattr(a, k, proto[k])
+    v, f = read_ply(a.data)
+    if a.mode == "mesh":
+        if f is None:
+            raise SystemExit(f"{a.data} holds no faces: use --mode pcd")
+        data = (v, f)
+    else:
+        data = v
+    gt, _ = read_ply(a.gt)
+    kw = dict(downsample_density=a.downsample_density, max_dist=a.max_dist, thresholds=proto["thresholds"], seed=a.seed,
+              vis_dir=None if a.no_vis else a.vis_out_dir, name=f"{a.scan:03}", visualize_threshold=a.visualize_threshold)
+    if a.protocol == "dtu":
+        if a.dataset_dir is None:
+            raise SystemExit("dtu needs --dataset_dir (the directory holding ObsMask/)")
+        obs, bb, res, plane = load_dtu_obs(a.dataset_dir, a.scan)
+        out = chamfer_dtu(data, gt, obs, bb, res, plane, patch_size=a.patch_size, **kw)
+    else:
+        out = chamfer_deepfashion(data, gt, **kw)
+    print(f"over_all: {out['over_all']}; mean_d2gt: {out['mean_d2gt']}; mean_gt2d: {out['mean_gt2d']}.")
+    print(f"precision_1mm: {out['precision_1']};  recall_1mm: {out['recall_1']};  fscore_1mm: {out['fscore_1']}")
+    print(f"precision_2mm: {out['precision_2']};  recall_2mm: {out['recall_2']};  fscore_2mm: {out['fscore_2']}")
+    path = Path(a.data)
+    log = a.log if a.log is not None else os.path.join(str(path.parent), "eval_result.txt")
+    with open(log, "w+") as fh:
+        fh.write(format_log(out, path.stem, proto["decimals"]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
