@@ -919,6 +919,73 @@ int nudf_pc_cells(const NudfPointCloud* args, void* stream);       /* one thread
 int nudf_pc_thin_round(const NudfPointCloud* args, void* stream);  /* one thread per point */
 int nudf_pc_nearest(const NudfPointCloud* args, void* stream);     /* one thread per query */
 
+/* ------------------------------------------------------------------------------------
+ * Mesh topology for the mesh clean-up (neuraludf_amd/meshclean.py): replaces what the reference does with trimesh,
+ * networkx, scipy.sparse and cv2 on the CPU -- trimesh's fill_holes (extract_mesh.py:222-223), the border smoothing
+ * (extract_mesh.py:238-265), clean_mesh_by_faces_num / clean_outliers (evaluation/clean_dtu_mesh.py:158-191) and
+ * clean_points_by_mask / clean_points_by_visualhull (clean_dtu_mesh.py:36-105).  One struct; each entry point reads the
+ * fields its comment names.  Half-edge 3 f + k of face f runs faces[f][k] -> faces[f][(k + 1) % 3]; its key is
+ * min * n_verts + max (n_verts < 2^31).  The caller sorts the keys (stable) and scans between launches.
+ *   edges       one thread per unique edge e: edges[e] = (u, v, count, first face, second face or -1) with u <= v, and
+ *               he_edge[h] = e for each of its half-edges;
+ *   fill_count  one thread per boundary vertex i: new_count[i] = triangles of the hole whose smallest vertex bverts[i]
+ *               is (a closed loop of 3 or 4 <= max_loop boundary edges whose vertices all have boundary degree 2; a 3-loop
+ *               whose triangle exists gets none);
+ *   fill_emit   the same walk; writes the triangles at new_faces[new_off[i]...].  A 4-loop is split along the shorter
+ *               diagonal (float64 squared length, tie: through the smallest vertex).  A triangle starts at its smallest
+ *               vertex and ascends, unless more of its boundary edges run in that same direction in their face than
+ *               against it;
+ *   smooth      one thread per border vertex v: pos_out[v] = pos[v] + lam (mean of pos over v's boundary neighbours, in
+ *               ascending index - pos[v]), float64;
+ *   cc_hook     one thread per sorted half-edge j >= 1 whose key equals that of j - 1: the larger of the two faces' roots
+ *               takes the smaller as label (atomicMin), *changed = 1;
+ *   cc_jump     one thread per face: labels[f] = its root.  Rounds of hook + jump until *changed stays 0 end with
+ *               labels[f] = the smallest face index of f's component;
+ *   views       one thread per vertex: vis_count[v] = views i with round-half-even((proj_i p)_xy / (proj_i p)_z) + 1 inside
+ *               [border, W - border] x [border, H - border] and the mask, padded by one pixel of ones, set there.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfMeshTopo {
+  const int64_t* faces;      /* [n_faces, 3]                                                                         */
+  const int64_t* he_key;     /* [3 n_faces] half-edge keys, ascending (edges, cc_hook)                               */
+  const int64_t* he_id;      /* [3 n_faces] the half-edge at each sorted position (edges, cc_hook)                   */
+  const int64_t* edge_start; /* [n_edges] sorted position of the first half-edge of each unique edge (edges)         */
+  int64_t* edges;            /* [n_edges, 5] (edges: written; fill_*: read)                                          */
+  int64_t* he_edge;          /* [3 n_faces] (edges)                                                                  */
+  const int64_t* edge_key;   /* [n_edges] the unique keys, ascending (fill_*)                                        */
+  const int64_t* nbr_off;    /* [n_verts + 1] CSR of the boundary neighbours (fill_*, smooth)                        */
+  const int64_t* nbr;        /* boundary neighbours of each vertex, ascending (fill_*, smooth)                       */
+  const int64_t* bverts;     /* [n_bverts] the vertices with a boundary edge, ascending (fill_*, smooth)             */
+  int64_t* new_count;        /* [n_bverts] (fill_count)                                                              */
+  const int64_t* new_off;    /* [n_bverts] exclusive prefix sum of new_count (fill_emit)                             */
+  int64_t* new_faces;        /* [n_new, 3] (fill_emit)                                                               */
+  const double* pos;         /* [n_verts, 3] vertex positions (fill_emit, smooth, views)                             */
+  double* pos_out;           /* [n_verts, 3] (smooth; only the rows of bverts are written)                           */
+  int64_t* labels;           /* [n_faces] set to 0 .. n_faces - 1 by the caller (cc_*)                               */
+  int32_t* changed;          /* one word, zeroed by the caller before each round (cc_hook)                           */
+  const double* proj;        /* [n_views, 3, 4] rows 0..2 of each world matrix (views)                               */
+  const uint8_t* masks;      /* [n_views, H, W] non-zero = set (views)                                               */
+  int32_t* vis_count;        /* [n_verts] (views)                                                                    */
+  int64_t n_faces;
+  int64_t n_verts;
+  int64_t n_edges;
+  int64_t n_bverts;
+  int64_t n_new;
+  double lam;                /* smooth: the step, 0.3 in the reference                                               */
+  int32_t max_loop;          /* fill_*: 3 or 4                                                                       */
+  int32_t n_views;
+  int32_t H;
+  int32_t W;
+  int32_t border;            /* views: 0 for the mask test, 50 for the visual-hull test                              */
+  int32_t pad_;
+} NudfMeshTopo;
+int nudf_meshtopo_edges(const NudfMeshTopo* args, void* stream);       /* one thread per unique edge      */
+int nudf_meshtopo_fill_count(const NudfMeshTopo* args, void* stream);  /* one thread per boundary vertex  */
+int nudf_meshtopo_fill_emit(const NudfMeshTopo* args, void* stream);   /* one thread per boundary vertex  */
+int nudf_meshtopo_smooth(const NudfMeshTopo* args, void* stream);      /* one thread per boundary vertex  */
+int nudf_meshtopo_cc_hook(const NudfMeshTopo* args, void* stream);     /* one thread per sorted half-edge */
+int nudf_meshtopo_cc_jump(const NudfMeshTopo* args, void* stream);     /* one thread per face             */
+int nudf_meshtopo_views(const NudfMeshTopo* args, void* stream);       /* one thread per vertex           */
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must be loaded before libnudf, see module docstring
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NUDF_LIB") or os.path.join(_HERE, "libnudf.so")      # NUDF_LIB: A/B builds of the library
-ABI_VERSION = 107         # nudf_version() of the include/nudf.h these ctypes structures mirror
+ABI_VERSION = 108         # nudf_version() of the include/nudf.h these ctypes structures mirror
 
 c_fp = C.c_void_p
 i32 = C.c_int32
@@ -211,6 +211,15 @@ class PointCloud(C.Structure):
                 ("dist", c_fp), ("idx", c_fp)]
 
 
+class MeshTopo(C.Structure):
+    _fields_ = [("faces", c_fp), ("he_key", c_fp), ("he_id", c_fp), ("edge_start", c_fp), ("edges", c_fp), ("he_edge", c_fp),
+                ("edge_key", c_fp), ("nbr_off", c_fp), ("nbr", c_fp), ("bverts", c_fp), ("new_count", c_fp), ("new_off", c_fp),
+                ("new_faces", c_fp), ("pos", c_fp), ("pos_out", c_fp), ("labels", c_fp), ("changed", c_fp), ("proj", c_fp),
+                ("masks", c_fp), ("vis_count", c_fp), ("n_faces", C.c_int64), ("n_verts", C.c_int64), ("n_edges", C.c_int64),
+                ("n_bverts", C.c_int64), ("n_new", C.c_int64), ("lam", C.c_double), ("max_loop", i32), ("n_views", i32),
+                ("H", i32), ("W", i32), ("border", i32), ("pad_", i32)]
+
+
 # float offsets of the device loss-weight vector (include/nudf.h NUDF_LW_*)
 LW = dict(color_base=0, color=1, color_pixel=2, color_patch=3, igr=4, igr_ns=5, sparse=6, mask=7, color_sum=8)
 LW_COUNT = 16
@@ -236,6 +245,8 @@ SYMBOLS = [
     "nudf_blend_loss_prepare", "nudf_blend_loss_fwd", "nudf_blend_loss_bwd",
     "nudf_meshudf_classify", "nudf_meshudf_emit", "nudf_meshudf_vertices",
     "nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells", "nudf_pc_thin_round", "nudf_pc_nearest",
+    "nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit", "nudf_meshtopo_smooth",
+    "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump", "nudf_meshtopo_views",
 ]
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -305,6 +316,9 @@ _ARGTYPES = {
     "nudf_meshudf_vertices": [C.POINTER(MeshUDF), _P],
     **{n: [C.POINTER(PointCloud), _P] for n in ("nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells",
                                                 "nudf_pc_thin_round", "nudf_pc_nearest")},
+    **{n: [C.POINTER(MeshTopo), _P] for n in ("nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit",
+                                              "nudf_meshtopo_smooth", "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump",
+                                              "nudf_meshtopo_views")},
 }
 
 _lib = None

@@ -17,7 +17,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libnudf.so")
 SOURCES = ["nudf_api.hip", "gemm_f32_mfma.hip", "gemm_tn_f32_mfma.hip", "rays_embed.hip", "composite.hip", "upsample.hip",
            "blend.hip", "optim.hip", "mlp_chain.hip", "mlp_chain_rows.hip", "raybatch.hip", "meshudf.hip",
-           "pointcloud.hip"]
+           "pointcloud.hip", "meshtopo.hip"]
 
 
 # the sources that decide what a kernel class reads and writes (bench.py `roofline.traffic_stale`: a PMC traffic file under
@@ -29,6 +29,7 @@ KERNEL_SOURCES = {
     "composite": ["csrc/composite.hip", "csrc/nudf_common.h", "../include/nudf.h"],
     "meshudf": ["csrc/meshudf.hip", "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
     "pointcloud": ["csrc/pointcloud.hip", "csrc/nudf_common.h", "../include/nudf.h"],
+    "meshtopo": ["csrc/meshtopo.hip", "csrc/nudf_common.h", "../include/nudf.h"],
 }
 
 

@@ -1,0 +1,403 @@
+"""Mesh clean-up on the GPU (csrc/meshtopo.hip): the steps between the mesher and the Chamfer evaluation that the
+reference takes from trimesh, networkx, scipy.sparse and cv2.
+
+    edge table   mesh_edges          unique undirected edges with their faces; boundary edges are those of count 1
+    holes        fill_holes          extract_mesh.py:222-223 (trimesh fill_holes): loops of 3 get one triangle, of 4 two
+    borders      smooth_borders      extract_mesh.py:238-265: 5 Jacobi steps of the border Laplacian, lambda = 0.3
+    components   face_components, filter_components     clean_dtu_mesh.py:158-191
+    views        clean_by_views, clean_dtu_mesh         clean_dtu_mesh.py:36-154 (mask and visual-hull cleaning)
+    masks        ellipse_footprint, dilate_masks, load_dtu_views
+
+Device tensors in, device tensors out; empty meshes pass through unchanged.  Sorts and scans between the launches are
+torch's (stable sort, integer prefix sums): every result is identical from run to run.
+
+Where the definitions differ from the libraries the reference calls:
+  * trimesh takes the boundary loops from a networkx cycle basis, which is not canonical where borders touch.  Here a hole
+    is a closed loop of 3 or 4 boundary edges all of whose vertices have boundary degree exactly 2 (the loop is then a
+    whole connected component of the boundary graph), and for a 3-loop the triangle must not exist already.  Longer loops
+    stay open.  The winding of a new face is a vote over its boundary edges (see fill_holes).
+  * two faces are adjacent when they share an undirected edge of any multiplicity; trimesh's face_adjacency pairs only
+    the edges with exactly two faces.
+  * the structuring element is restated from the formula in OpenCV's documentation (ellipse_footprint); cv2 is not
+    available to check it against.
+"""
+from __future__ import annotations
+
+import glob
+import os
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr
+
+MAX_VERTS = 1 << 31          # half-edge keys are min * V + max in int64
+HULL_BORDER = 50             # clean_dtu_mesh.py:88
+HULL_MAX_OUTSIDE = 5         # clean_dtu_mesh.py:105
+
+
+class EdgeTable(NamedTuple):
+    """edges [E, 5] int64: (u, v, count, first face, second face or -1) per unique undirected edge, u <= v, ordered by
+    (u, v); he_edge [3 F]: row of the edge of half-edge 3 f + k (faces[f][k] -> faces[f][(k + 1) % 3]); he_key / he_id
+    [3 F]: the sorted keys u * V + v and the half-edge at each sorted position; edge_start / edge_key [E]: first sorted
+    position and key of each edge"""
+    edges: torch.Tensor
+    he_edge: torch.Tensor
+    he_key: torch.Tensor
+    he_id: torch.Tensor
+    edge_start: torch.Tensor
+    edge_key: torch.Tensor
+
+
+def _check_faces(faces, n_verts):
+    if not isinstance(faces, torch.Tensor):
+        raise ValueError("faces must be a torch tensor")
+    if faces.dtype != torch.int64:
+        raise ValueError(f"faces must be int64 (got {faces.dtype})")
+    if not faces.is_cuda:
+        raise ValueError(f"faces must be on a GPU (got {faces.device})")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces must be [F, 3] (got {tuple(faces.shape)})")
+    n_verts = int(n_verts)
+    if not 0 <= n_verts < MAX_VERTS:
+        raise ValueError(f"n_verts {n_verts} outside [0, 2^31)")
+    if faces.shape[0]:
+        lo, hi = int(faces.min()), int(faces.max())
+        if lo < 0 or hi >= n_verts:
+            raise ValueError(f"face index out of range: [{lo}, {hi}] for {n_verts} vertices")
+    return faces.contiguous(), n_verts
+
+
+def _check_mesh(verts, faces):
+    if not isinstance(verts, torch.Tensor):
+        raise ValueError("verts must be a torch tensor")
+    if verts.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"verts must be float32 or float64 (got {verts.dtype})")
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    faces, _ = _check_faces(faces, verts.shape[0])
+    if verts.device != faces.device:
+        raise ValueError(f"verts and faces must be on the same GPU (got {verts.device}, {faces.device})")
+    return verts.contiguous(), faces
+
+
+def _topo(faces, n_verts, table=None):
+    d = _lib.MeshTopo(faces=ptr(faces), n_faces=faces.shape[0], n_verts=n_verts)
+    if table is not None:
+        d.he_key, d.he_id, d.edge_start = ptr(table.he_key), ptr(table.he_id), ptr(table.edge_start)
+        d.edges, d.he_edge, d.edge_key = ptr(table.edges), ptr(table.he_edge), ptr(table.edge_key)
+        d.n_edges = table.edges.shape[0]
+    return d
+
+
+def mesh_edges(faces, n_verts):
+    """edge table of a triangle mesh -> EdgeTable.  faces: [F, 3] int64 on a GPU over n_verts < 2^31 vertices."""
+    faces, n_verts = _check_faces(faces, n_verts)
+    return _mesh_edges(faces, n_verts)
+
+
+def _mesh_edges(faces, n_verts):
+    dev = faces.device
+    a, b = faces.reshape(-1), faces.roll(-1, 1).reshape(-1)
+    he_key, he_id = torch.sort(torch.minimum(a, b) * n_verts + torch.maximum(a, b), stable=True)
+    first = torch.ones(he_key.numel(), dtype=torch.bool, device=dev)
+    if he_key.numel():
+        first[1:] = he_key[1:] != he_key[:-1]
+    edge_start = torch.nonzero(first).reshape(-1)
+    table = EdgeTable(torch.empty((edge_start.numel(), 5), dtype=torch.int64, device=dev),
+                      torch.empty(he_key.numel(), dtype=torch.int64, device=dev), he_key, he_id, edge_start,
+                      he_key[edge_start])
+    call("nudf_meshtopo_edges", _topo(faces, n_verts, table))
+    return table
+
+
+class _Boundary(NamedTuple):
+    nbr_off: torch.Tensor      # [V + 1] CSR offsets
+    nbr: torch.Tensor          # boundary neighbours of each vertex, ascending
+    bverts: torch.Tensor       # vertices with a boundary edge, ascending
+    n_edges: int
+
+
+def _boundary(table, n_verts):
+    """CSR of the boundary graph (edges of count 1): a sort of the 2 B directed pairs, a count and a scan"""
+    e = table.edges
+    b = e[e[:, 2] == 1]
+    key = torch.sort(torch.cat([b[:, 0] * n_verts + b[:, 1], b[:, 1] * n_verts + b[:, 0]])).values
+    src = key // n_verts if n_verts else key
+    deg = torch.bincount(src, minlength=n_verts)
+    nbr_off = torch.zeros(n_verts + 1, dtype=torch.int64, device=e.device)
+    torch.cumsum(deg, 0, out=nbr_off[1:])
+    nbr = (key - src * n_verts).contiguous()
+    return _Boundary(nbr_off, nbr, torch.nonzero(deg).reshape(-1), b.shape[0])
+
+
+def boundary_degree(faces, n_verts):
+    """-> [V] int64: number of boundary edges (edges with exactly one face) at each vertex"""
+    faces, n_verts = _check_faces(faces, n_verts)
+    off = _boundary(_mesh_edges(faces, n_verts), n_verts).nbr_off
+    return off[1:] - off[:-1]
+
+
+def fill_holes(verts, faces, max_loop=4):
+    """closes the holes of 3 (one triangle) and, with max_loop = 4, of 4 boundary edges (two triangles, split along the
+    shorter diagonal in float64; tie: the diagonal through the smallest vertex index) -> (faces' [F + n, 3], number of
+    holes filled).  A hole is a closed loop of boundary edges whose vertices all have boundary degree 2; a 3-loop whose
+    triangle is already a face is left.  A new face starts at its smallest vertex and ascends, unless more of its boundary
+    edges run in that direction in the face next to them than against it (trimesh's rule as a vote: MeshUDF meshes are
+    not consistently wound).  New faces follow the old ones, ordered by their smallest vertex.  One pass: a filled hole
+    makes no new boundary."""
+    if max_loop not in (3, 4):
+        raise ValueError(f"max_loop must be 3 or 4 (got {max_loop})")
+    verts, faces = _check_mesh(verts, faces)
+    if faces.shape[0] == 0:
+        return faces, 0
+    n_verts = verts.shape[0]
+    table = _mesh_edges(faces, n_verts)
+    bd = _boundary(table, n_verts)
+    if bd.bverts.numel() == 0:
+        return faces, 0
+    pos = verts.double().contiguous()
+    count = torch.empty(bd.bverts.numel(), dtype=torch.int64, device=faces.device)
+    d = _topo(faces, n_verts, table)
+    d.nbr_off, d.nbr, d.bverts, d.n_bverts = ptr(bd.nbr_off), ptr(bd.nbr), ptr(bd.bverts), bd.bverts.numel()
+    d.pos, d.max_loop, d.new_count = ptr(pos), max_loop, ptr(count)
+    call("nudf_meshtopo_fill_count", d)
+    ends = torch.cumsum(count, 0)
+    n_new = int(ends[-1])
+    if n_new == 0:
+        return faces, 0
+    off = ends - count
+    new = torch.empty((n_new, 3), dtype=torch.int64, device=faces.device)
+    d.new_off, d.new_faces, d.n_new = ptr(off), ptr(new), n_new
+    call("nudf_meshtopo_fill_emit", d)
+    return torch.cat([faces, new]), int((count > 0).sum())
+
+
+def smooth_borders(verts, faces, iterations=5, lam=0.3):
+    """Laplacian smoothing of the border vertices along the border -> verts' [V, 3] float32.  Each of `iterations` Jacobi
+    steps moves every vertex with a boundary edge by lam times the difference between the mean of its neighbours along
+    boundary edges and itself, all from the previous step's positions; float64 inside, neighbours summed in ascending
+    index, cast to float32 at the end only.  Other vertices do not move."""
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError(f"iterations must be >= 0 (got {iterations})")
+    verts, faces = _check_mesh(verts, faces)
+    if faces.shape[0] == 0 or iterations == 0:
+        return verts.float()
+    n_verts = verts.shape[0]
+    bd = _boundary(_mesh_edges(faces, n_verts), n_verts)
+    if bd.bverts.numel() == 0:
+        return verts.float()
+    pos = verts.double().contiguous()                # may be the caller's tensor: read only
+    bufs = [pos.clone(), pos.clone() if iterations > 1 else None]      # a step writes the border rows only
+    d = _topo(faces, n_verts)
+    d.nbr_off, d.nbr, d.bverts, d.n_bverts, d.lam = ptr(bd.nbr_off), ptr(bd.nbr), ptr(bd.bverts), bd.bverts.numel(), lam
+    for i in range(iterations):
+        d.pos, d.pos_out = ptr(pos), ptr(bufs[i % 2])
+        call("nudf_meshtopo_smooth", d)
+        pos = bufs[i % 2]
+    return pos.float()
+
+
+def face_components(faces, n_verts, _info=None):
+    """connected components over faces -> labels [F] int64: the smallest face index of each face's component.  Two faces
+    are adjacent when they share an undirected edge, whatever the number of faces on it (trimesh's face_adjacency, which
+    the reference uses, pairs only the edges with exactly two faces).  Rounds of min-label hooking over the sorted
+    half-edges and pointer jumping, one 4-byte read-back per round.  (`_info`: a dict that receives the number of rounds.)"""
+    faces, n_verts = _check_faces(faces, n_verts)
+    return _face_components(faces, n_verts, _mesh_edges(faces, n_verts) if faces.shape[0] else None, _info)
+
+
+def _face_components(faces, n_verts, table, _info=None):
+    n = faces.shape[0]
+    labels = torch.arange(n, dtype=torch.int64, device=faces.device)
+    rounds = 0
+    if n:
+        changed = torch.zeros(1, dtype=torch.int32, device=faces.device)
+        d = _topo(faces, n_verts, table)
+        d.labels, d.changed = ptr(labels), ptr(changed)
+        while True:
+            if rounds > n:                                   # every round that changes something lowers a label
+                raise RuntimeError("face_components did not converge")
+            changed.zero_()
+            call("nudf_meshtopo_cc_hook", d)
+            call("nudf_meshtopo_cc_jump", d)
+            rounds += 1
+            if int(changed.item()) == 0:
+                break
+    if _info is not None:
+        _info["rounds"] = rounds
+    return labels
+
+
+def compact_mesh(verts, faces, vertex_mask=None, face_mask=None, drop_unreferenced=True):
+    """drops the faces outside `face_mask` and those with a vertex outside `vertex_mask`, then the vertices outside
+    `vertex_mask` and, with drop_unreferenced, those no remaining face uses; the survivors keep their order
+    -> (verts', faces' into them)"""
+    if vertex_mask is not None and faces.numel():
+        keep = vertex_mask[faces].all(1)
+        face_mask = keep if face_mask is None else face_mask & keep
+    if face_mask is not None:
+        faces = faces[face_mask]
+    keep = vertex_mask
+    if drop_unreferenced:
+        keep = torch.zeros(verts.shape[0], dtype=torch.bool, device=verts.device)
+        keep[faces.reshape(-1)] = True
+    if keep is None:
+        return verts, faces
+    remap = torch.cumsum(keep, 0) - 1
+    return verts[keep], remap[faces]
+
+
+def filter_components(verts, faces, min_faces=500, keep_largest=False):
+    """keeps the components (face_components) with at least min_faces faces, or with keep_largest the largest one only
+    (tie: the one with the smallest face index), and drops the vertices no kept face uses -> (verts', faces')
+    (clean_dtu_mesh.py clean_mesh_by_faces_num and clean_outliers(keep_largest=True))"""
+    verts, faces = _check_mesh(verts, faces)
+    if faces.shape[0] == 0:
+        return verts, faces
+    labels = face_components(faces, verts.shape[0])
+    size = torch.bincount(labels, minlength=faces.shape[0])
+    if keep_largest:
+        mask = labels == torch.nonzero(size == size.max())[0, 0]                  # first index of the maximum
+    else:
+        mask = size[labels] >= int(min_faces)
+    return compact_mesh(verts, faces, face_mask=mask)
+
+
+def ellipse_footprint(ksize):
+    """OpenCV's MORPH_ELLIPSE structuring element of size ksize x ksize -> np.uint8 [ksize, ksize], restated from the
+    formula in its documentation: with r = c = ksize // 2, row i sets the columns [max(c - dx, 0), min(c + dx + 1, ksize))
+    where dx = rint(c sqrt((r^2 - (i - r)^2) / r^2)).  It reproduces the 5 x 5 element printed there; cv2 itself is not
+    available to check other sizes against."""
+    ksize = int(ksize)
+    if ksize < 1:
+        raise ValueError(f"ksize must be >= 1 (got {ksize})")
+    out = np.zeros((ksize, ksize), dtype=np.uint8)
+    r = c = ksize // 2
+    inv_r2 = 1.0 / (r * r) if r else 0.0
+    for i in range(ksize):
+        dy = i - r
+        if abs(dy) <= r:
+            dx = int(np.rint(c * np.sqrt((r * r - dy * dy) * inv_r2)))
+            out[i, max(c - dx, 0):min(c + dx + 1, ksize)] = 1
+    return out
+
+
+def dilate_masks(masks, ksize, chunk=8):
+    """binary dilation of masks [n, H, W] (non-zero = set) with ellipse_footprint(ksize), anchored at its centre, pixels
+    beyond the image unset (cv2.dilate's defaults) -> uint8 0 / 1 of the same shape and device.  Every footprint row is
+    one run of columns: a horizontal running count per distinct run, OR-ed over the rows it occurs in."""
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 3:
+        raise ValueError("masks must be a [n, H, W] tensor")
+    fp = ellipse_footprint(ksize)
+    c = fp.shape[0] // 2
+    runs = {}
+    for i, row in enumerate(fp):
+        cols = np.nonzero(row)[0]
+        if len(cols):
+            runs.setdefault((int(cols[0]) - c, int(cols[-1]) - c), []).append(i - c)
+    n, H, W = masks.shape
+    out = torch.zeros((n, H, W), dtype=torch.uint8, device=masks.device)
+    xs = torch.arange(W, device=masks.device)
+    for s in range(0, n, chunk):
+        m = masks[s:s + chunk] != 0
+        acc = torch.zeros_like(m)
+        csum = torch.zeros((m.shape[0], H, W + 1), dtype=torch.int32, device=masks.device)
+        torch.cumsum(m, 2, dtype=torch.int32, out=csum[:, :, 1:])
+        for (lo, hi), dys in runs.items():
+            # out(y, x) takes src(y + dy, x + dx) for dx in [lo, hi]
+            a, b = (xs + lo).clamp(0, W), (xs + hi + 1).clamp(0, W)
+            row_any = csum[:, :, b] > csum[:, :, a]
+            for dy in dys:
+                y0, y1 = max(0, -dy), min(H, H - dy)
+                if y0 < y1:
+                    acc[:, y0:y1] |= row_any[:, y0 + dy:y1 + dy]
+        out[s:s + chunk] = acc
+    return out
+
+
+def load_dtu_views(dataset_dir, scan):
+    """the cameras and object masks of a DTU scan as the reference's cleaning reads them (clean_dtu_mesh.py:37-52):
+    <dataset_dir>/scan<scan>/cameras.npz (world_mat_<i>) and mask/*.png in sorted order, channel 0
+    -> (world_mats np.float64 [n, 4, 4], masks np.uint8 [n, H, W], undilated: the object is where a mask is > 128)."""
+    from PIL import Image
+    root = os.path.join(str(dataset_dir), f"scan{scan}")
+    files = sorted(glob.glob(os.path.join(root, "mask", "*.png")))
+    if not files:
+        raise FileNotFoundError(f"no mask/*.png under {root}")
+    cams = np.load(os.path.join(root, "cameras.npz"))
+    mats = np.stack([np.asarray(cams[f"world_mat_{i}"], dtype=np.float64) for i in range(len(files))])
+    masks = []
+    for f in files:
+        m = np.asarray(Image.open(f))
+        masks.append(np.ascontiguousarray(m[..., 0] if m.ndim == 3 else m).astype(np.uint8))
+    return mats, np.stack(masks)
+
+
+def view_counts(verts, world_mats, masks, border=0):
+    """[V] int32: for each vertex the number of views in which it projects into a set mask pixel.  Per view
+    q = P[:3, :3] p + P[:3, 3] in float64, each row as ((P0 x + P1 y) + P2 z) + P3; (x, y) = round-half-even(q.xy / q.z)
+    + 1; the view counts when border <= x <= W - border, border <= y <= H - border and the mask, padded by one pixel of
+    ones, is set at (y, x).  A non-finite q.xy / q.z counts for nothing.  There is no depth test, as in the reference."""
+    if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+        raise ValueError("verts must be a tensor on a GPU")
+    if verts.dtype not in (torch.float32, torch.float64) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts must be float32 or float64 [V, 3] (got {verts.dtype} {tuple(verts.shape)})")
+    dev = verts.device
+    if not isinstance(masks, torch.Tensor) or masks.dtype != torch.uint8 or masks.dim() != 3:
+        raise ValueError("masks must be a uint8 [n_views, H, W] tensor")
+    if masks.device != dev:
+        raise ValueError(f"masks must be on the vertices' GPU (got {masks.device})")
+    mats = torch.as_tensor(np.asarray(world_mats.cpu() if isinstance(world_mats, torch.Tensor) else world_mats,
+                                      dtype=np.float64))
+    n, H, W = masks.shape
+    if mats.dim() != 3 or mats.shape[0] != n or mats.shape[1] < 3 or mats.shape[2] != 4:
+        raise ValueError(f"world_mats must be [{n}, 4, 4] like the masks (got {tuple(mats.shape)})")
+    border = int(border)
+    if border < 0 or H < 1 or W < 1:
+        raise ValueError("border must be >= 0 and the masks not empty")
+    proj = mats[:, :3, :].contiguous().to(dev)
+    pos = verts.double().contiguous()
+    masks = masks.contiguous()
+    count = torch.zeros(verts.shape[0], dtype=torch.int32, device=dev)
+    d = _lib.MeshTopo(pos=ptr(pos), proj=ptr(proj), masks=ptr(masks), vis_count=ptr(count), n_verts=verts.shape[0],
+                      n_views=n, H=H, W=W, border=border)
+    call("nudf_meshtopo_views", d)
+    return count
+
+
+def clean_by_views(verts, faces, world_mats, masks, mode="mask", minimal_vis=0, max_outside=HULL_MAX_OUTSIDE,
+                   border=HULL_BORDER, drop_unreferenced=False):
+    """cuts the mesh by what the views see (clean_dtu_mesh.py:36-154) -> (verts', faces').
+    mode "mask": masks [n, H, W] uint8 are the (dilated) object masks; a vertex stays when more than minimal_vis views
+    see it inside one (window 0 <= x <= W, 0 <= y <= H after the reference's shift by one).
+    mode "hull": the masks are set *outside* the dilated object; the window shrinks by `border` on each side and a vertex
+    stays when fewer than max_outside views see it outside (the reference hard-codes 5 and ignores minimal_vis here).
+    Faces with a dropped vertex go.  Vertices that pass stay even when no face uses them any more, as in the reference
+    (the DTU evaluation samples every vertex); drop_unreferenced=True removes them."""
+    if mode not in ("mask", "hull"):
+        raise ValueError(f"mode must be 'mask' or 'hull' (got {mode!r})")
+    verts, faces = _check_mesh(verts, faces)
+    if verts.shape[0] == 0:
+        return verts, faces
+    count = view_counts(verts, world_mats, masks, border if mode == "hull" else 0)
+    keep = count > int(minimal_vis) if mode == "mask" else count < int(max_outside)
+    return compact_mesh(verts, faces, vertex_mask=keep, drop_unreferenced=drop_unreferenced)
+
+
+def clean_dtu_mesh(verts, faces, world_mats, masks, mask_dilated_size=11, minimal_vis=2):
+    """the reference's DTU cleaning sequence (clean_dtu_mesh.py __main__): mask cleaning with the object masks (> 128)
+    dilated by mask_dilated_size, then visual-hull cleaning against the masks dilated by mask_dilated_size + 20 (outside =
+    dilated value < 128).  masks: the undilated uint8 [n, H, W] masks of load_dtu_views -> (verts', faces')"""
+    verts, faces = _check_mesh(verts, faces)
+    if not isinstance(masks, torch.Tensor):
+        masks = torch.as_tensor(np.asarray(masks))
+    masks = masks.to(verts.device)
+    inside = dilate_masks(masks > 128, mask_dilated_size)
+    verts, faces = clean_by_views(verts, faces, world_mats, inside, "mask", minimal_vis=minimal_vis)
+    del inside
+    outside = 1 - dilate_masks(masks >= 128, mask_dilated_size + 20)
+    return clean_by_views(verts, faces, world_mats, outside, "hull")

@@ -745,12 +745,13 @@ class UDFRendererBlending:
             ret[k] = e(0, S, 3) if k == 'gradients_flip' else e(0, S)
         return ret
 
-    def extract_udf_geometry(self, bound_min, bound_max, resolution, dist_threshold_ratio=1.0):
+    def extract_udf_geometry(self, bound_min, bound_max, resolution, dist_threshold_ratio=1.0, **clean):
         """open-surface mesh of the UDF (neuraludf_amd.meshing.extract_udf_mesh, MeshUDF on the GPU; the reference's
-        extract_mesh.get_mesh_udf_fast) -> (vertices np.float32 [V, 3], faces np.int64 [F, 3]) in the box's units"""
+        extract_mesh.get_mesh_udf_fast) -> (vertices np.float32 [V, 3], faces np.int64 [F, 3]) in the box's units.
+        `clean`: its clean-up keywords (fill_holes, smooth_borders, min_component_faces, keep_largest), off by default"""
         from .. import meshing
         return meshing.extract_udf_mesh(self.udf_network, resolution, bound_min, bound_max,
-                                        dist_threshold_ratio=dist_threshold_ratio)
+                                        dist_threshold_ratio=dist_threshold_ratio, **clean)
 
     def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.01, device='cpu'):
         """(:757-760) -> (vertices, triangles).  The grid query runs on the network's GPU whatever `device` says (the

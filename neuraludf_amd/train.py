@@ -505,15 +505,17 @@ class Trainer:
         if var_p is not None and var_p.requires_grad is False and iter_step > 20000:
             self.var.set_trainable()
 
-    def extract_udf_mesh(self, resolution=256, world_space=False, scale_mat=None, dist_threshold_ratio=1.0):
+    def extract_udf_mesh(self, resolution=256, world_space=False, scale_mat=None, dist_threshold_ratio=1.0, **clean):
         """open-surface mesh of the UDF in the [-1, 1]^3 box (Runner.extract_udf_mesh, exp_runner_blending.py:763-800,
         without its file output; neuraludf_amd.meshing.extract_udf_mesh) -> (vertices np.float32 [V, 3], faces np.int64
-        [F, 3]).  world_space: map the vertices with `scale_mat` (the dataset's scale_mats_np[0]) as the runner does."""
+        [F, 3]).  world_space: map the vertices with `scale_mat` (the dataset's scale_mats_np[0]) as the runner does.
+        `clean`: the clean-up keywords of meshing.extract_udf_mesh (fill_holes, smooth_borders, min_component_faces,
+        keep_largest), all off by default."""
         from . import meshing
         if world_space and scale_mat is None:
             raise ValueError("world_space=True needs scale_mat (the dataset's scale_mats_np[0])")
         return meshing.extract_udf_mesh(self.udf, resolution, dist_threshold_ratio=dist_threshold_ratio,
-                                        scale_mat=scale_mat if world_space else None)
+                                        scale_mat=scale_mat if world_space else None, **clean)
 
     @torch.no_grad()
     def render_image(self, source, img_idx, resolution_level=4, chunk=65536, cos_anneal_ratio=1.0):
