@@ -524,15 +524,23 @@ enum {
                             N <= iparam: C2 mirrors the sigmoid columns instead                    */
   NUDF_CH_MULMASK = 8,   /* out = (X1 > 0) ? acc * scale : 0            (ReLU backward)           */
   NUDF_CH_ADDMASK = 9,   /* out = (X1 > 0) ? (acc + X2) * scale : 0     (ReLU backward at a join) */
-  NUDF_CH_RELUADD = 10   /* out = relu(acc + bias + X2)   (skip layer whose second input part was multiplied
+  NUDF_CH_RELUADD = 10,  /* out = relu(acc + bias + X2)   (skip layer whose second input part was multiplied
                             by an earlier step: NeRF's cat([input_pts, h]) is wider than the LDS tile)  */
+  /* A kind that contracts NOTHING: it turns the LDS tile a finished forward sweep left behind into the initial tile of the
+     input-gradient sweep, so that the two back-to-back sweeps over the same points run as ONE launch (workgroup-shared kernel,
+     split modes, 32- / 64-point tiles only; nudf_mlp_chain refuses it anywhere else).  Bp, bias are unused (NULL).
+     SEED: directly behind a UDFHEAD step (and the act_write = 0 steps in front of it, which leave the tile alone): the tile
+       still holds the last SOFTPLUS step's activations h, the head's multiplier sign[r] is handed over on chip --
+       tile[r, c] = sign[r] * r1_col[c] * scale * softplus'(h[r, c]) for c < N (xscale as in MULSP), all rows of the tile ->
+       C1 [rows padded, ldc1].  The same values NUDF_CH_INIT_SEED forms from the stored arrays, bit for bit.               */
+  NUDF_CH_SEED = 11
 };
 enum {
   NUDF_CH_INIT_LOAD = 0,   /* activation tile = A0[rows, 0:k0]                                    */
   NUDF_CH_INIT_POSENC = 1, /* activation tile = PE(x) (or its JVP with tangent v), zero-padded to k0 */
   NUDF_CH_INIT_SEED = 2    /* tile[r,c] = seed_sign[r] * seed_wrow[c] * seed_scale * softplus'(A0[r,c]) */
 };
-#define NUDF_CH_MAX_STEPS 14
+#define NUDF_CH_MAX_STEPS 20          /* forward + input gradient of a 9-layer UDF network in one launch: 19 */
 typedef struct NudfChainStep {
   const float* Bp;                 /* packed weights (nudf_pack_frag) of the [K, N] operand          */
   const float* bias;               /* [N] or NULL                                                    */
@@ -662,7 +670,13 @@ typedef struct NudfChain {
   int32_t reserved0;
   NudfChainStep step[NUDF_CH_MAX_STEPS];
 } NudfChain;
+#if defined(__cplusplus)
+static_assert(sizeof(NudfChain) <= 4096, "NudfChain travels by value: the kernel-argument segment holds 4 KB");
+#endif
 int nudf_mlp_chain(const NudfChain* args, void* stream);
+/* NUDF_CH_MAX_STEPS of the header the library was compiled against: the array bound sets sizeof(NudfChain), so a caller that
+ * passes the struct by reference checks it as it checks nudf_version() (the Python loader refuses a library that differs). */
+int nudf_chain_max_steps(void);
 /* 16-bit mode (prec 1 / 2), 64-point tiles: chains whose steps ALL contract in the same 16-bit type run on the 16-bit-tile
  * kernel -- the LDS activation tile holds that type (the MFMA operand itself: one ds_read_b128 per 32-row tile and k step, no
  * conversion in the K loop, 37 KB per workgroup = three workgroups per CU), the epilogue rounds the new activations once on

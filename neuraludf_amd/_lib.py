@@ -140,10 +140,11 @@ class Adam(C.Structure):
                 ("dyn", c_fp)]
 
 
-CH_MAX_STEPS = 14
+CH_MAX_STEPS = 20
 CH_STATE16 = 32     # NudfChainStep.layout: the step's stored-state arrays hold bf16
 CH_P4_X1, CH_P4_C1 = 64, 128   # ReLU-family steps of the 16-bit mode: that array is bf16, 4-point packed
-CH = dict(NONE=0, SOFTPLUS=1, MULSP=2, TANGENT=3, BWD=4, UDFHEAD=5, RELU=6, SIGMOIDN=7, MULMASK=8, ADDMASK=9, RELUADD=10)
+CH = dict(NONE=0, SOFTPLUS=1, MULSP=2, TANGENT=3, BWD=4, UDFHEAD=5, RELU=6, SIGMOIDN=7, MULMASK=8, ADDMASK=9, RELUADD=10,
+          SEED=11)     # contracts nothing: forward + input-gradient sweep in one launch (include/nudf.h)
 CH_INIT = dict(LOAD=0, POSENC=1, SEED=2)
 
 
@@ -229,7 +230,7 @@ EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMO
 
 # every symbol include/nudf.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
-    "nudf_version", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_set_gemm_variant", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
+    "nudf_version", "nudf_chain_max_steps", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_set_gemm_variant", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
     "nudf_composite_bwd", "nudf_partial_sums", "nudf_composite_colour_finish", "nudf_set_composite_blocked", "nudf_upsample", "nudf_merge", "nudf_merge_points", "nudf_coarse_z", "nudf_coarse_start", "nudf_outside_z",
     "nudf_ray_points", "nudf_posenc", "nudf_posenc_vjp", "nudf_copy_cols", "nudf_add_cols",
     "nudf_udf_grad_seed", "nudf_udf_head_bwd", "nudf_signed_colsum", "nudf_sigmoid_head_bwd",
@@ -349,6 +350,12 @@ def lib():
         if _lib.nudf_version() != ABI_VERSION:      # the ctypes structures below mirror include/nudf.h of exactly this version
             v, _lib = _lib.nudf_version(), None
             raise NudfError(f"{LIB_PATH} is ABI version {v}, this package binds {ABI_VERSION}: rebuild with "
+                            "`python -m neuraludf_amd.build --force`")
+        # (the step capacity of NudfChain sets its size: a library built before it grew lacks the symbol or reports another bound)
+        steps = getattr(_lib, "nudf_chain_max_steps", None)
+        if steps is None or int(steps()) != CH_MAX_STEPS:
+            v, _lib = (None if steps is None else int(steps())), None
+            raise NudfError(f"{LIB_PATH} holds {v} chain steps per launch, this package binds {CH_MAX_STEPS}: rebuild with "
                             "`python -m neuraludf_amd.build --force`")
         _bind(_lib)
         _lib.nudf_gemm_tn_grouped_workspace.restype = C.c_int64

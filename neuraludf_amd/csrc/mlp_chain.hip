@@ -31,6 +31,10 @@ struct ChainSmem {
   float vs[TM * 3];
   float red[8];          // workgroup reductions (NudfChain.tile_scale / tile_amax_out): one value per wave
 };
+// Column CH_SGN_COL of the fp32 tile -- inside the row padding (CH_LD - 288 floats that no K loop reads and no step writes) --
+// holds the UDFHEAD step's per-point multiplier ("sign"): a NUDF_CH_SEED step of the same launch takes it from there.
+#define CH_SGN_COL 288
+static_assert(CH_SGN_COL < CH_LD, "the head multiplier lives in the tile's row padding");
 
 // MODE 3 (16-bit-tile kernel, BASELINE config 5): the activation tile holds the MFMA operand type of the chain's steps (fp16 in
 // the forward sweeps, bf16 in the backward ones): 37 KB instead of 75 KB per 64-point workgroup -> three workgroups per CU
@@ -852,6 +856,7 @@ __device__ __forceinline__ float ch_epilogue_tile(const NudfChainStep& st, float
       for (int r = 0; r < 16; ++r) {
         if (st.C2) st.C2[grow0 + CH_KOFF(r)] = out[r];
         if (st.C1) st.C1[grow0 + CH_KOFF(r)] = out2[r];
+        if constexpr (!T16) act[(r0 + CH_KOFF(r)) * CH_LD + CH_SGN_COL] = out2[r];   // (for a SEED step behind the head)
       }
     }
     return tmax;
@@ -1499,6 +1504,35 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
     // CU runs every layer at full MFMA rate and its partner only in the gaps (the kernel then ends with half the
     // wave slots idle for ~13 % of its time).  Alternate the priority layer by layer: speed only.
     if ((si + slot) & 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
+    if constexpr (X3) {
+      if (st.epi == NUDF_CH_SEED) {
+        // The forward sweep is done and the tile still holds X[L] (the features and head steps leave it alone): turn it into
+        // the input-gradient sweep's seed in place -- the values INIT_SEED forms from the stored X[L] and sign, operation for
+        // operation.  One column per thread (N <= 256 = CH_THREADS): conflict-free LDS, a wave stores 256 contiguous bytes.
+        // (t: the thread index behind an empty asm, so that nothing computed from it here is hoisted out of the step loop and
+        // kept in registers across the K loops and epilogues, which have none to spare)
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        const int C = st.N;
+        if (t < C) {
+          const float wc = st.r1_col[t];
+          float* ap = act_f + t;
+          float* gp = st.C1 ? st.C1 + (size_t)m0 * st.ldc1 + t : nullptr;
+#pragma unroll 4
+          for (int r = 0; r < TM; ++r) {
+            float s, om;
+            ch_sp_derivs(ap[r * CH_LD], st.xscale, s, om);
+            const float val = ap[r * CH_LD + CH_SGN_COL - t] * wc * st.scale * s;
+            ap[r * CH_LD] = val;
+            // (all TM rows, like every step's C1: the buffer is row-padded, and the adjoint sweep reads whole tiles of DA -- a
+            // scratch row left undefined would reach its per-tile maximum)
+            if (gp) gp[(size_t)r * st.ldc1] = val;
+          }
+        }
+        __syncthreads();
+        continue;
+      }
+    }
     const int G = st.K >> 3;                 // k groups of 8
     const int NT = (st.N + 31) >> 5;         // 32-column tiles
     const f32x4* __restrict__ Bp = reinterpret_cast<const f32x4*>(st.Bp);
@@ -1629,9 +1663,10 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
         else ch_mma<1, 1, false>(arow, bptr, bstride, G, acc, pf, px1);
       }
     }
-    if (dbg && lane == 0) dbg[2 + 4 * si] = __builtin_amdgcn_s_memtime();
+    // (the timeline holds 14 steps per wave: a longer chain records its first 14)
+    if (dbg && lane == 0 && si < 14) dbg[2 + 4 * si] = __builtin_amdgcn_s_memtime();
     __syncthreads();  // every wave is done reading the activation tile
-    if (dbg && lane == 0) dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
 
     if (nct > 0) {
       switch (st.epi) {
@@ -1650,7 +1685,7 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
         default: ch_epilogue<NUDF_CH_UDFHEAD, MODE>(p, st, act_f, m0, rt0, ct0, nrt, nct, h, ln, acc, px1, bpre, tile_bf, tsig, tinv); break;
       }
     }
-    if (dbg && lane == 0) dbg[4 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[4 + 4 * si] = __builtin_amdgcn_s_memtime();
     if (st.pe_tail_col >= 0) {
       __syncthreads();
       // zero up to the next multiple of 16 columns: the K padding of the step that consumes [.. | PE] must multiply
@@ -1660,7 +1695,7 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
                       min((pe_end + 15) & ~15, 288), (st.layout & NUDF_CH_STATE16) != 0, tfmt, tinv);
     }
     __syncthreads();
-    if (dbg && lane == 0) dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
   }
   if (dbg && lane == 0) dbg[63] = wall_clock64();
   if constexpr (X3) {
@@ -1721,12 +1756,33 @@ extern "C" int nudf_set_chain_t16(int on) {
   return old;
 }
 
+extern "C" int nudf_chain_max_steps(void) { return NUDF_CH_MAX_STEPS; }
+
 extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
   const NudfChain& p = *args;
   if (p.P <= 0 || p.n_steps <= 0) return 0;
   bool bad = p.n_steps > NUDF_CH_MAX_STEPS || (p.k0 & 3) || p.k0 > 288 || p.x_div < 1;
+  // SEED (two sweeps in one launch) contracts nothing and exists in mlp_chain_kernel<TM, 2> only: checked on its own
+  bool fused = false;
   for (int i = 0; i < p.n_steps && !bad; ++i) {
     const NudfChainStep& s = p.step[i];
+    if (s.epi == NUDF_CH_SEED) {
+      // directly behind the head, in front of a step that contracts the seed; no tile scaling (the forward sweep is not linear)
+      bad = i == 0 || i + 1 >= p.n_steps || p.step[i - 1].epi != NUDF_CH_UDFHEAD || p.step[i - 1].act_write || !s.r1_col ||
+            s.N <= 0 || s.N > 256 || p.step[i + 1].K < s.N || p.step[i + 1].K > ((s.N + 15) & ~15) || (s.C1 && s.ldc1 < s.N) ||
+            s.layout || s.pe_tail_col >= 0 || s.X3 || s.row_w || p.tile_scale || p.tile_amax_in || p.tile_amax_out || p.absmax_out;
+      // (columns N .. K of the next step: the tile's padding must be finite zeros -- the SOFTPLUS step that wrote the tile
+      // zeroes whole 32-column tiles, and N of that step equals N here)
+      for (int j = i - 1; j >= 0 && !bad; --j) {
+        if (p.step[j].act_write) {
+          bad = p.step[j].epi != NUDF_CH_SOFTPLUS || p.step[j].N != s.N || p.step[j].act_col0 != 0 || p.step[j].pe_tail_col >= 0;
+          break;
+        }
+        bad = j == 0;
+      }
+      fused = true;
+      continue;
+    }
     bad = (s.K & 15) || s.K <= 0 || s.K > 288 || s.N <= 0 || s.N > 256 || (((uintptr_t)s.Bp) & 15) ||
           (s.act_write && s.act_col0 + ((s.N + 31) / 32) * 32 > 288) || s.prec < 0 || s.prec > 4 ||
           ((s.layout & NUDF_CH_STATE16) && s.epi != NUDF_CH_SOFTPLUS && s.epi != NUDF_CH_MULSP &&
@@ -1738,15 +1794,21 @@ extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
                     p.tile_rows == 130));
   }
   if (bad) {
-    nudf_set_error("nudf_mlp_chain: K%16, K<=288, N<=256, x_div>=1, 16-byte aligned packed weights required", hipErrorInvalidValue);
+    nudf_set_error("nudf_mlp_chain: K%16, K<=288, N<=256, x_div>=1, 16-byte aligned packed weights required; SEED behind the "
+                   "head of a forward sweep", hipErrorInvalidValue);
     return (int)hipErrorInvalidValue;
   }
   hipStream_t st = (hipStream_t)stream;
   bool any16 = false, any3 = false;
   for (int i = 0; i < p.n_steps; ++i) {
+    if (p.step[i].epi == NUDF_CH_SEED) continue;     // (contracts nothing: no operand mode)
     any3 = any3 || p.step[i].prec >= 3;        // the split modes (bf16x3, f16x2) share the MODE 2 instantiation
     any16 = any16 || (p.step[i].prec != 0 && p.step[i].prec < 3) ||
             (p.step[i].layout & (NUDF_CH_STATE16 | NUDF_CH_P4_X1 | NUDF_CH_P4_C1));
+  }
+  if (fused && (!any3 || any16 || (p.tile_rows != 0 && p.tile_rows != 32 && p.tile_rows != 64))) {
+    nudf_set_error("nudf_mlp_chain: a SEED step needs a split-mode chain on the 32- / 64-point workgroup-shared tiles", hipErrorInvalidValue);
+    return (int)hipErrorInvalidValue;
   }
   if (any3 && any16) {
     nudf_set_error("nudf_mlp_chain: split steps (prec 3 / 4) do not mix with 16-bit steps / 16-bit stored state", hipErrorInvalidValue);
@@ -1783,7 +1845,7 @@ extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
       return (int)hipErrorInvalidValue;
     }
   }
-  bool rows_ok = !roww && (p.tile_rows == 128 || p.tile_rows == 0);
+  bool rows_ok = !roww && !fused && (p.tile_rows == 128 || p.tile_rows == 0);
   if (rows_ok && p.tile_rows == 0) {
     const long long round = 1024LL * 32, rounds = (p.P + round - 1) / round;
     rows_ok = nudf_chain_rows_auto() && p.P >= 24576 && (double)p.P >= 0.8 * (double)(rounds * round);
@@ -1808,7 +1870,7 @@ extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
     const int cls = nudf_chain_rows_class(p);
     if (cls >= 0) return nudf_mlp_chain_tq_launch(p, cls, st, 1);
   }
-  if (!roww && (p.tile_rows == 66 || (p.tile_rows == 0 && p.P > 256 * 64 && nudf_chain_quad_mode() > 0))) {
+  if (!roww && !fused && (p.tile_rows == 66 || (p.tile_rows == 0 && p.P > 256 * 64 && nudf_chain_quad_mode() > 0))) {
     const int cls = nudf_chain_rows_class(p);
     if (cls >= 0 && (p.tile_rows == 66 || cls <= 1 || nudf_chain_quad_mode() >= 2)) return nudf_mlp_chain_tq_launch(p, cls, st);
   }

@@ -467,7 +467,8 @@ __global__ __launch_bounds__(CHR_WAVES * 64, 1) void mlp_chain_rows_kernel(NudfC
       default: chr_mma<8>(arow, bptr, bstride, G, bb, acc, tail); break;
     }
     *reinterpret_cast<f32x4*>(sm.bias[wave][(si + 1) & 1] + 4 * lane) = nbias;
-    if (dbg && lane == 0) dbg[2 + 4 * si] = dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
+    // (64 timeline slots per wave hold 14 steps; NUDF_CH_MAX_STEPS is larger)
+    if (dbg && lane == 0 && si < 14) dbg[2 + 4 * si] = dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
 
     switch (st.epi) {
       case NUDF_CH_SOFTPLUS: chr_epilogue<NUDF_CH_SOFTPLUS, W>(st, act, cs, NT, h, ln, acc, px1, px2); break;
@@ -483,7 +484,7 @@ __global__ __launch_bounds__(CHR_WAVES * 64, 1) void mlp_chain_rows_kernel(NudfC
       case NUDF_CH_RELUADD: if (XCLS >= 2) chr_epilogue<NUDF_CH_RELUADD, W>(st, act, cs, NT, h, ln, acc, px1, px2); break;
       default: break;
     }
-    if (dbg && lane == 0) dbg[4 + 4 * si] = dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[4 + 4 * si] = dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
     chr_wave_sync();
     if (st.pe_tail_col >= 0) {
       const int pe_end = st.pe_tail_col + 3 * (2 * p.pe_L + 1);
@@ -909,9 +910,9 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
       else tq_mma<1, 1>(arow, bptr, bstride, G, acc, tail);
     }
     sm.bias[(si + 1) & 1][tid] = nbias;
-    if (dbg && lane == 0) dbg[2 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[2 + 4 * si] = __builtin_amdgcn_s_memtime();
     __syncthreads();  // every wave is done reading the activation tile
-    if (dbg && lane == 0) dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
 
     if (nct > 0) {
       switch (st.epi) {
@@ -929,7 +930,7 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
         default: break;
       }
     }
-    if (dbg && lane == 0) dbg[4 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[4 + 4 * si] = __builtin_amdgcn_s_memtime();
     if (st.pe_tail_col >= 0) {
       __syncthreads();
       const int pe_end = st.pe_tail_col + 3 * (2 * p.pe_L + 1);
@@ -937,7 +938,7 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
                             st.pe_tail_col, min((pe_end + 15) & ~15, 288), false, (st.layout & NUDF_CH_BLK_PE) != 0);
     }
     __syncthreads();
-    if (dbg && lane == 0) dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
   }
   if (dbg && lane == 0) dbg[63] = wall_clock64();
 }
@@ -1116,7 +1117,7 @@ __global__ __launch_bounds__(512, 2) void mlp_chain_pair_kernel(NudfChain p_arg)
       else tq_mma<1, 1>(arow, bptr, bstride, G, acc, tail);
     }
     sm.bias[half][(si + 1) & 1][tid] = nbias;
-    if (dbg && lane == 0) dbg[2 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[2 + 4 * si] = __builtin_amdgcn_s_memtime();
     // the epilogue the OTHER half runs in this phase (half 0 sees E(si - 1) of half 1, half 1 sees E(si) of half 0): if
     // it ends with a positional-encoding tail, it has one barrier inside -- keep it company
     {
@@ -1124,7 +1125,7 @@ __global__ __launch_bounds__(512, 2) void mlp_chain_pair_kernel(NudfChain p_arg)
       if (so >= 0 && p.step[so].pe_tail_col >= 0) __syncthreads();
     }
     __syncthreads();  // phase boundary: the other half's epilogue is done, its K loop may start; ours starts its epilogue
-    if (dbg && lane == 0) dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[3 + 4 * si] = __builtin_amdgcn_s_memtime();
 
     // ---------------- epilogue of step si: beside the other half's K loop ----------------
     if (nct > 0) {
@@ -1144,7 +1145,7 @@ __global__ __launch_bounds__(512, 2) void mlp_chain_pair_kernel(NudfChain p_arg)
         default: break;
       }
     }
-    if (dbg && lane == 0) dbg[4 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[4 + 4 * si] = __builtin_amdgcn_s_memtime();
     if (st.pe_tail_col >= 0) {
       __syncthreads();
       if (live) {
@@ -1154,7 +1155,7 @@ __global__ __launch_bounds__(512, 2) void mlp_chain_pair_kernel(NudfChain p_arg)
       }
     }
     __syncthreads();  // phase boundary
-    if (dbg && lane == 0) dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
+    if (dbg && lane == 0 && si < 14) dbg[5 + 4 * si] = __builtin_amdgcn_s_memtime();
   }
   if (half == 0) {    // last phase: half 1 runs E(L - 1)
     if (p.step[L - 1].pe_tail_col >= 0) __syncthreads();

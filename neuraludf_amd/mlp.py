@@ -423,6 +423,18 @@ class ChainBuilder:
         s.r1_row, s.ldr1, s.r1_col = self._p(r1_row), ldr1, self._p(r1_col)
         s.row_w, s.row_sums = self._p(row_w), self._p(row_sums)      # SIGMOIDN: compositing sum inside the epilogue
         s.K, s.N, s.epi, s.iparam = K, N, CH[epi], iparam
+        if epi == "SEED":        # contracts nothing (include/nudf.h): the forward sweep's tile becomes the reverse sweep's seed
+            if Bp is not None or bias is not None:
+                raise _lib.NudfError("a SEED step takes no weights")
+            s.layout = 0
+            s.act_write, s.act_col0, s.pe_tail_col, s.pe_tail_scale = 1, 0, -1, 0.0
+            s.scale, s.xscale = scale, xscale
+            self.n += 1
+            if PROFILE is not None:
+                if C1 is not None:
+                    self.nbytes += float(self.c.P) * min(N, C1.shape[1]) * C1.element_size()
+                self.epis.append(epi)
+            return
         s.prec = getattr(Bp, "prec", 0)
         # 16-bit stored state (config-5 mode): X1, X2, C1, the TANGENT mirror C2 and pe_dst of a step are bf16 TOGETHER
         state = [t for t in (X1, X2, X3, C1, C2 if epi == "TANGENT" else None, pe_dst) if t is not None]
@@ -523,7 +535,8 @@ class ChainBuilder:
                     x3 = any(self.c.step[i].X3 for i in range(self.n))
                     mode = 4 if ("TANGENT" in e or x3) else 3      # the 16-bit-tile kernel (one operand type in every step)
             kern = "mlp_chain_kernel<%d, %d>" % (32 if t32 else 64, mode)
-        sweep = ("tangent" if ("TANGENT" in e or ("MULSP" in e and self.init == "POSENC")) else "adjoint" if "BWD" in e
+        sweep = ("udf-forward+input-gradient" if "SEED" in e
+                 else "tangent" if ("TANGENT" in e or ("MULSP" in e and self.init == "POSENC")) else "adjoint" if "BWD" in e
                  else "input-gradient" if "MULSP" in e
                  else "relu-backward" if e & {"MULMASK", "ADDMASK"} else "udf-forward" if "SOFTPLUS" in e
                  else "relu-forward")
@@ -757,6 +770,25 @@ EX_FLY = os.environ.get("NUDF_EX_FLY", "1") != "0"
 # maximum the producing sweeps report (NudfChain.absmax_out), the activation side is used as it is.  0 = bf16x3 GEMMs (A/B).
 TN_F16X2 = os.environ.get("NUDF_TN_F16X2", "1") != "0"
 TN_SPLIT = os.environ.get("NUDF_TN_SPLIT", "1") != "0"      # bf16x3 mode: the weight-gradient GEMMs take split operands too
+
+
+# The UDF value sweep and the input-gradient sweep that follows it over the same points as ONE launch (bf16x3 mode,
+# workgroup-shared tiles): a NUDF_CH_SEED step behind the head turns the LDS tile, which still holds X[L], and the head's multiplier
+# into the reverse sweep's seed -- no X[L] round trip through memory, one launch boundary less, and the down-going half re-reads
+# what the same workgroup stored a few steps earlier.  Memory holds the same bits either way.
+# NUDF_FUSE_SWEEPS=0 keeps one launch per sweep (A/B, identity tests).
+FUSE_SWEEPS = os.environ.get("NUDF_FUSE_SWEEPS", "1") != "0"
+
+
+def set_fuse_sweeps(on):
+    """True (default): value + input gradient of the UDF network as one launch; False: one launch per sweep.  -> the old setting."""
+    global FUSE_SWEEPS
+    old, FUSE_SWEEPS = FUSE_SWEEPS, bool(on)
+    return old
+
+
+def _fuse():
+    return FUSE_SWEEPS and PRECISION == "bf16x3" and CHAIN_TILE in (0, 32, 64)
 
 
 def _tn_prec():
@@ -1130,6 +1162,17 @@ class UDFEngine:
             return self._gradient_chain(x, st)
         return self._gradient_layers(x, st)
 
+    def forward_gradient(self, x, feat_ld=0, feat_buf=None):
+        """value (with saved state) and d udf / dx of the same points -> (st, g, DA): what forward(need_grad_state=True)
+        followed by gradient() returns, as ONE chain launch where the mode has it (FUSE_SWEEPS)."""
+        if self._chain_ok() and _fuse() and 2 * self.L + 3 <= CH_MAX_STEPS:
+            st = self._forward_chain(x, True, feat_ld, False, feat_buf, with_grad=True)
+            g, DA = st.pop("g"), st.pop("DA")
+            return st, g, DA
+        st = self.forward(x, need_grad_state=True, feat_ld=feat_ld, feat_buf=feat_buf)
+        g, DA = self.gradient(x, st)
+        return st, g, DA
+
     def backward(self, x, st, DA, d_udf, d_feat, d_feat_ld, d_g):
         if self._chain_ok():
             return self._backward_chain(x, st, DA, d_udf, d_feat, d_feat_ld, d_g)
@@ -1164,9 +1207,11 @@ class UDFEngine:
         """tile column where PE(x)/sqrt(2) starts in the input of skip layer l."""
         return self.layers[l].inp - self.E
 
-    def _forward_chain(self, x, need_grad_state, feat_ld=0, udf_only=False, feat_buf=None):
+    def _forward_chain(self, x, need_grad_state, feat_ld=0, udf_only=False, feat_buf=None, with_grad=False):
         """one launch: posenc -> 8 softplus layers -> abs head, activations resident in LDS.
-        feat_buf: [pad_rows(P), max(feat_ld, F)] with [x | 0] already in columns F.. (nudf_merge_points), or None."""
+        feat_buf: [pad_rows(P), max(feat_ld, F)] with [x | 0] already in columns F.. (nudf_merge_points), or None.
+        with_grad: the input-gradient sweep follows in the same launch (a SEED step behind the head turns the resident X[L]
+        into its seed); the result then carries g and DA as well."""
         P, dev, L = x.shape[0], x.device, self.L
         net = self.net
         pack_group(self.layers, self._frag_kinds())
@@ -1174,7 +1219,7 @@ class UDFEngine:
         blk = _state_blocked(P)
         X = ([_buf(P, self.layers[0].inp, dev, zero=False)] +
              [_buf(P, pl.inp, dev, zero=False, dtype=sd, blocked=blk) for pl in self.layers[1:]]) if need_grad_state else None
-        cb = ChainBuilder(P, "POSENC", k8(self.E), site=("udf_fwd", _memo_token(self)))
+        cb = ChainBuilder(P, "POSENC", k8(self.E), site=("udf_fwd_grad" if with_grad else "udf_fwd", _memo_token(self)))
         cb.posenc(x, net.multires, float(net.scale))
         if need_grad_state:
             cb.init_store(X[0])
@@ -1207,23 +1252,29 @@ class UDFEngine:
                     act_write=0)
         cb.step("UDFHEAD", pl.frag(_head_kind()), k8(pl.inp), 1, bias=pl.bias, C1=sign, C2=udf, ldc1=1, ldc2=1,
                 act_write=0, scale=1.0 / float(net.scale), iparam=self.head_type)
+        st = dict(udf=udf[:P], sign=(sign[:P] if sign is not None else None),
+                  feat=(feat[:P] if feat is not None else None), X=X, P=P)
+        if with_grad:
+            DA = self._gradient_buffers(P, X, dev)
+            n_top = self.layers[L - 1].out
+            cb.step("SEED", None, k8(n_top), n_top, r1_col=pl.W, C1=DA[L - 1], scale=1.0 / float(net.scale),
+                    xscale=self._xs(L - 1))
+            demb0, demb_skip = self._gradient_steps(cb, P, X, DA, dev)
+            cb.launch()
+            st["g"], st["DA"] = self._gradient_finish(x, P, demb0, demb_skip), DA
+            return st
         cb.launch()
-        return dict(udf=udf[:P], sign=(sign[:P] if sign is not None else None),
-                    feat=(feat[:P] if feat is not None else None), X=X, P=P)
+        return st
 
-    def _gradient_chain(self, x, st):
-        """one launch: seed -> reverse sweep DA[L-1..0] -> d/d(embedding); then the encoding's VJP."""
-        P, L, dev = st["P"], self.L, x.device
-        X = st["X"]
-        net = self.net
-        DA = [_buf(P, self.layers[l].out, dev, zero=False, dtype=X[L].dtype, blocked=_isblk(X[L])) for l in range(L)]
-        plL = self.layers[L]
+    def _gradient_buffers(self, P, X, dev):
+        L = self.L
+        return [_buf(P, self.layers[l].out, dev, zero=False, dtype=X[L].dtype, blocked=_isblk(X[L])) for l in range(L)]
+
+    def _gradient_steps(self, cb, P, X, DA, dev):
+        """the reverse sweep behind its seed: DA[L-2..0], then d/d(embedding) -> (demb0, demb_skip)"""
         Epad = pad32(self.E)
-        cb = ChainBuilder(P, "SEED", k8(self.layers[L - 1].out), site=("udf_grad", _memo_token(self)))
-        cb.init_seed(X[L], X[L].shape[1], st["sign"], plL.W, 1.0 / float(net.scale), self._xs(L - 1))
-        cb.init_store(DA[L - 1])
         demb_skip = None
-        for l in range(L - 1, 0, -1):
+        for l in range(self.L - 1, 0, -1):
             pl = self.layers[l]
             if l in self.skip:
                 demb_skip = torch.empty(pad_rows(P), Epad, device=dev)
@@ -1235,11 +1286,28 @@ class UDFEngine:
         demb0 = torch.empty(pad_rows(P), Epad, device=dev)
         pl0 = self.layers[0]
         cb.step("NONE", pl0.frag(_kind("bwd", "grad")), k8(pl0.out), pl0.inp, C1=demb0, act_write=0)
-        cb.launch()
-        g = torch.empty(P, 3, device=dev)
+        return demb0, demb_skip
+
+    def _gradient_finish(self, x, P, demb0, demb_skip):
+        net, Epad = self.net, pad32(self.E)
+        g = torch.empty(P, 3, device=x.device)
         call("nudf_posenc_vjp", ptr(x), 3, net.d_in, net.multires, float(net.scale), P,
              ptr(demb0), Epad, 1.0, ptr(demb_skip), Epad, 1.0, ptr(g))
-        return g, DA
+        return g
+
+    def _gradient_chain(self, x, st):
+        """one launch: seed -> reverse sweep DA[L-1..0] -> d/d(embedding); then the encoding's VJP."""
+        P, L, dev = st["P"], self.L, x.device
+        X = st["X"]
+        net = self.net
+        DA = self._gradient_buffers(P, X, dev)
+        plL = self.layers[L]
+        cb = ChainBuilder(P, "SEED", k8(self.layers[L - 1].out), site=("udf_grad", _memo_token(self)))
+        cb.init_seed(X[L], X[L].shape[1], st["sign"], plL.W, 1.0 / float(net.scale), self._xs(L - 1))
+        cb.init_store(DA[L - 1])
+        demb0, demb_skip = self._gradient_steps(cb, P, X, DA, dev)
+        cb.launch()
+        return self._gradient_finish(x, P, demb0, demb_skip), DA
 
     def _backward_chain(self, x, st, DA, d_udf, d_feat, d_feat_ld, d_g):
         """tangent sweep (second order) and adjoint sweep as one launch each; weight gradients as TN GEMMs."""

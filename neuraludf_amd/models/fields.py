@@ -40,10 +40,9 @@ class _UDFEvalFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)     # unused outputs arrive as None, not as zero-filled tensors
         x = x.detach().contiguous()
         need_state = any(ctx.needs_input_grad)      # all False under no_grad (grad mode is off inside forward)
-        st = engine.forward(x, need_grad_state=(need_state or want_grad), feat_ld=feat_ld, feat_buf=feat_buf)
         g = DA = None
         if want_grad:
-            g, DA = engine.gradient(x, st)
+            st, g, DA = engine.forward_gradient(x, feat_ld=feat_ld, feat_buf=feat_buf)      # (one launch where the mode has it)
             if normals_col >= 0:
                 # colour-net modes that see the normal (fields.py:456-461): gradients / (|gradients| + 1e-5)
                 # (udf_renderer_blending.py:371) and its negative go behind the points of the colour net's base input.
@@ -51,6 +50,8 @@ class _UDFEvalFn(torch.autograd.Function):
                 gn = g / (torch.linalg.norm(g, ord=2, dim=-1, keepdim=True) + 1e-5)
                 st["feat"][:, normals_col:normals_col + 3] = gn
                 st["feat"][:, normals_col + 3:normals_col + 6] = -gn
+        else:
+            st = engine.forward(x, need_grad_state=need_state, feat_ld=feat_ld, feat_buf=feat_buf)
         ctx.engine, ctx.x = engine, x
         ctx.st, ctx.DA = (st if need_state else None), (DA if need_state else None)
         # udf_type 'square': d udf / dx = 2 h0 grad h0 depends on h0 a second time (f'' = 2); the backward needs the

@@ -52,13 +52,14 @@ COLOUR = os.environ.get("TIMELINE_COLOUR", "0") == "1"
 
 
 def run():
-    st = eng.forward(x, need_grad_state=True, feat_ld=ceng.cin_ld)
     if COLOUR:      # the colour net's forward (both branches) and its two reverse sweeps instead of the UDF backward
+        st = eng.forward(x, need_grad_state=True, feat_ld=ceng.cin_ld)
         cb, cc, logits, cst = ceng.forward(st["feat"], rays_d, S, P)
         d_lg = torch.zeros_like(logits) if logits is not None else None
         ceng.backward(cst, cb, cc, d_cb, d_cc, d_lg)
         return
-    gr, DA = eng.gradient(x, st)
+    # value + input gradient: one launch with mlp.FUSE_SWEEPS (NUDF_FUSE_SWEEPS=0: one per sweep)
+    st, gr, DA = eng.forward_gradient(x, feat_ld=ceng.cin_ld)
     eng.backward(x, st, DA, d_udf, d_feat, ceng.cin_ld, d_g)
 
 
@@ -75,7 +76,11 @@ EPI = {v: k for k, v in _CH.items()}
 for li, (dbg, steps, flops, precs) in enumerate(launches):
     d = dbg.cpu().numpy()
     d = d[d[:, 1] > 0]
-    n = len(steps)
+    # (64 stamps per wave hold the first 14 steps of a launch; a fused launch of two sweeps shows its first sweep and the top
+    # of the second.  A SEED step contracts nothing and leaves no stamps: its time shows as the next step's K loop.)
+    n_all = len(steps)
+    stamped = [s for s in range(min(n_all, 14)) if steps[s][0] != _CH["SEED"]]
+    n = stamped[-1] + 1
     t0 = d[:, 1].min()
     tend = d[:, 5 + 4 * (n - 1)].max()
     span = float(tend - t0)
@@ -84,6 +89,9 @@ for li, (dbg, steps, flops, precs) in enumerate(launches):
     prev = d[:, 1].astype(np.float64)
     per_step = []
     for s in range(n):
+        if s not in stamped:
+            per_step.append((0.0, 0.0, 0.0, 0.0))
+            continue
         a, b, c, e = (d[:, 2 + 4 * s + j].astype(np.float64) for j in range(4))
         k += a - prev; w1 += b - a; ep += c - b; w2 += e - c
         per_step.append(((a - prev).mean(), (b - a).mean(), (c - b).mean(), (e - c).mean()))
@@ -93,7 +101,9 @@ for li, (dbg, steps, flops, precs) in enumerate(launches):
     # fp32: v_mfma_f32_32x32x2_f32 = 4 096 flops in 64 cycles; 16-bit: v_mfma_f32_32x32x16 = 32 768 flops in 32 cycles, times the
     # products of the step's operand mode (1: plain 16-bit, 6: bf16x3, 3: f16x2)
     mfma_cycles = 0.0
-    for (epi_, K_, N_), pr in zip(steps, precs):
+    for s_, ((epi_, K_, N_), pr) in enumerate(zip(steps, precs)):
+        if s_ not in stamped:
+            continue
         fl = 2.0 * K_ * N_ * 64 / 4            # (padded K, N: what the tile loop executes)
         mfma_cycles += fl / 4096 * 64 if pr == 0 else fl * mlp.MFMA_PRODUCTS[pr] / 32768 * 32
     wall = (d[:, 63] - d[:, 62]).astype(np.float64)            # 100 MHz ticks
@@ -101,13 +111,13 @@ for li, (dbg, steps, flops, precs) in enumerate(launches):
     ok = wall > 0
     mhz = float((mem[ok] / wall[ok]).mean() * 100.0) if ok.any() else float("nan")
     launch_us = float(d[:, 63].max() - d[:, 62].min()) / 100.0 if ok.any() else float("nan")
-    print(f"launch {li}: {n} steps, {len(d)} waves, flops/point {flops / P:.0f}; s_memtime runs at {mhz:.0f} MHz; first start -> last end {launch_us:.1f} us"
+    print(f"launch {li}: {n_all} steps ({len(stamped)} stamped), {len(d)} waves, flops/point {flops / P:.0f}; s_memtime runs at {mhz:.0f} MHz; first start -> last end {launch_us:.1f} us"
           f" = {flops / launch_us / 1e6 if launch_us == launch_us else float('nan'):.1f} TF")
     print(f"   per wave (mean ticks): K loop {k.mean():8.0f} ({k.mean() / tot.mean():5.1%})  barrier-1 wait {w1.mean():7.0f} ({w1.mean() / tot.mean():5.1%})"
           f"  epilogue {ep.mean():7.0f} ({ep.mean() / tot.mean():5.1%})  barrier-2 wait {w2.mean():7.0f} ({w2.mean() / tot.mean():5.1%})  total {tot.mean():8.0f}")
     print(f"   MFMA ticks needed per wave {mfma_cycles:8.0f}: K-loop efficiency {mfma_cycles / k.mean():5.1%} (2 waves share a SIMD: 50 % = pipe saturated),"
           f" wave-level MFMA share {mfma_cycles / tot.mean():5.1%}")
-    for s, (epi, K, N) in enumerate(steps):
+    for s, (epi, K, N) in enumerate(steps[:n]):
         a, b, c, e = per_step[s]
         print(f"      step {s:2d} epi {EPI.get(epi, epi)!s:9s} K {K:3d} N {N:3d}: K loop {a:7.0f}  wait1 {b:6.0f}  epilogue {c:6.0f}  wait2 {e:6.0f}")
     # per-SIMD matrix-pipe occupancy: group waves by (hw id without wave slot) and start time
