@@ -870,6 +870,57 @@ int nudf_meshudf_emit(const NudfMeshUDF* args, void* stream);       /* one threa
 int nudf_meshudf_vertices(const NudfMeshUDF* args, void* stream);   /* one thread per flagged edge */
 
 /* ------------------------------------------------------------------------------------
+ * Sparse MeshUDF extraction: the mesher above over the B^3-cell blocks near the surface only (neuraludf_amd/meshing.py
+ * udf_sparse_grid, udf_marching_cubes_sparse).  The grid is the dense one (N nodes per axis, M = N - 1 cells).  Blocks:
+ * nb = ceil(M / B) per axis, B in {4, 8}; block (bi, bj, bk), linear id (bi nb + bj) nb + bk, covers the cells
+ * [b B, min((b + 1) B, M)) per axis.  Selection rule (the caller's, part of the contract): with the per-axis spacings
+ * h_a = (bound_max[a] - bound_min[a]) / (N - 1), h = max_a h_a, the block half-diagonal r = sqrt(sum_a (B h_a)^2) / 2 and
+ * thr = 1.74 h + lipschitz r (float64, rounded up to fp32), a block is selected iff the minimum of the UDF (clamped at 0)
+ * at its eight coarse corners -- the nodes min(b B, N - 1) and min((b + 1) B, N - 1) per axis -- is <= thr; a NaN corner
+ * never selects.  Every point of a block lies within r of a corner, and an active cell has all corners <= 1.74 h, so
+ * with |grad U| <= lipschitz no active cell lies outside a selected block.
+ * Storage: the K selected blocks ascending; brick s holds the (B + 1)^3 nodes (b B + a) of its block, local index
+ * (ax (B + 1) + ay) (B + 1) + az; nodes past the grid's end in ragged blocks are padding and are never read.  Every
+ * copy of a shared node must hold the same bits (the caller queries each node once).
+ * Ordering contract, identical to the dense mesher's: vertices ascending by global edge id 3 lin(lower end) + axis,
+ * lin(i, j, k) = (i N + j) N + k; faces by ascending global cell index (i M + j) M + k, then table order.  The caller
+ * sorts the cells with triangles and the unique edge keys (deterministic integer sorts over active cells and edges
+ * only); no output position depends on timing.  3 <= N <= 4096.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfMeshUDFSparse {
+  const float* U;             /* [K, (B+1)^3] brick UDF values                                                       */
+  const float* G;             /* [K, (B+1)^3, 3] brick UDF gradients (read at the corners of active cells only)       */
+  const float* axes;          /* [3, N] grid coordinate of each index, per axis                                      */
+  const int64_t* blocks;      /* [K] linear ids of the selected blocks, ascending                                    */
+  const int32_t* block_slot;  /* [nb^3] brick of a block, -1: not selected                                           */
+  uint8_t* cell_case;         /* [K, B^3] case index per brick cell, 0 for inactive cells and cells past the grid (classify) */
+  uint8_t* cell_ntri;         /* [K, B^3] triangles of the cell (classify)                                           */
+  const int64_t* cells;       /* [n_cells] global indices (i M + j) M + k of the cells with triangles, ascending       */
+  const int64_t* face_off;    /* [n_cells] exclusive prefix sum of their triangle counts (emit)                      */
+  int64_t* edge_keys;         /* [n_cells, 12] global id of every sign-change edge of the cell, INT64_MAX for the other
+                                 edges (edges)                                                                       */
+  const int64_t* edges;       /* [n_edges] the unique edge ids, ascending (emit: vertex of an edge = its position;
+                                 vertices)                                                                           */
+  int64_t* faces;             /* [F, 3] vertex indices (emit)                                                        */
+  float* verts;               /* [n_edges, 3] vertex positions at t = U_a / (U_a + U_b) from the lower end a (vertices) */
+  int64_t n_blocks;           /* K                                                                                   */
+  int64_t n_cells;
+  int64_t n_edges;
+  int64_t n_faces;            /* F: emit refuses a face_off that would write past faces[F]                           */
+  int32_t N;
+  int32_t B;                  /* 4 or 8                                                                              */
+  int32_t nb;                 /* ceil((N - 1) / B)                                                                   */
+  float mean_thr;             /* 1.05 h, h = the largest grid spacing                                                */
+  float max_thr;              /* 1.74 h                                                                               */
+  int32_t pad_;
+} NudfMeshUDFSparse;
+int nudf_meshudf_sparse_struct_size(void);                                      /* sizeof(NudfMeshUDFSparse): the loader refuses a library that differs */
+int nudf_meshudf_sparse_classify(const NudfMeshUDFSparse* args, void* stream);  /* one workgroup per brick, its U in LDS */
+int nudf_meshudf_sparse_edges(const NudfMeshUDFSparse* args, void* stream);     /* one thread per cell with triangles */
+int nudf_meshudf_sparse_emit(const NudfMeshUDFSparse* args, void* stream);      /* one thread per cell with triangles */
+int nudf_meshudf_sparse_vertices(const NudfMeshUDFSparse* args, void* stream);  /* one thread per unique edge */
+
+/* ------------------------------------------------------------------------------------
  * Point-cloud geometry of the Chamfer evaluation (neuraludf_amd/evaluation.py): replaces the mesh sampling, the radius
  * down-sampling and the two sklearn KD-tree nearest-neighbour sweeps of evaluation/eval_dtu_python.py (:205-370) and
  * eval_deepfashion_python.py (:62-215).  All coordinates are float64 and every expression follows the reference's

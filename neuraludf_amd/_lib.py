@@ -199,6 +199,14 @@ class MeshUDF(C.Structure):
                 ("max_thr", f32), ("pad_", i32)]
 
 
+class MeshUDFSparse(C.Structure):
+    _fields_ = [("U", c_fp), ("G", c_fp), ("axes", c_fp), ("blocks", c_fp), ("block_slot", c_fp), ("cell_case", c_fp),
+                ("cell_ntri", c_fp), ("cells", c_fp), ("face_off", c_fp), ("edge_keys", c_fp), ("edges", c_fp),
+                ("faces", c_fp), ("verts", c_fp), ("n_blocks", C.c_int64), ("n_cells", C.c_int64), ("n_edges", C.c_int64),
+                ("n_faces", C.c_int64), ("N", i32), ("B", i32), ("nb", i32), ("mean_thr", f32), ("max_thr", f32),
+                ("pad_", i32)]
+
+
 class PointCloud(C.Structure):
     _fields_ = [("verts", c_fp), ("faces", c_fp), ("tri_n", c_fp), ("tri_off", c_fp), ("out", c_fp),
                 ("n_verts", C.c_int64), ("n_faces", C.c_int64), ("n_out", C.c_int64), ("out_base", C.c_int64),
@@ -245,6 +253,8 @@ SYMBOLS = [
     "nudf_step_loss_fwd", "nudf_step_loss_bwd", "nudf_col0_seed4",
     "nudf_blend_loss_prepare", "nudf_blend_loss_fwd", "nudf_blend_loss_bwd",
     "nudf_meshudf_classify", "nudf_meshudf_emit", "nudf_meshudf_vertices",
+    "nudf_meshudf_sparse_struct_size", "nudf_meshudf_sparse_classify", "nudf_meshudf_sparse_edges",
+    "nudf_meshudf_sparse_emit", "nudf_meshudf_sparse_vertices",
     "nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells", "nudf_pc_thin_round", "nudf_pc_nearest",
     "nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit", "nudf_meshtopo_smooth",
     "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump", "nudf_meshtopo_views",
@@ -315,6 +325,8 @@ _ARGTYPES = {
     "nudf_meshudf_classify": [C.POINTER(MeshUDF), _P],
     "nudf_meshudf_emit": [C.POINTER(MeshUDF), _P],
     "nudf_meshudf_vertices": [C.POINTER(MeshUDF), _P],
+    **{n: [C.POINTER(MeshUDFSparse), _P] for n in ("nudf_meshudf_sparse_classify", "nudf_meshudf_sparse_edges",
+                                                   "nudf_meshudf_sparse_emit", "nudf_meshudf_sparse_vertices")},
     **{n: [C.POINTER(PointCloud), _P] for n in ("nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells",
                                                 "nudf_pc_thin_round", "nudf_pc_nearest")},
     **{n: [C.POINTER(MeshTopo), _P] for n in ("nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit",
@@ -357,6 +369,12 @@ def lib():
             v, _lib = (None if steps is None else int(steps())), None
             raise NudfError(f"{LIB_PATH} holds {v} chain steps per launch, this package binds {CH_MAX_STEPS}: rebuild with "
                             "`python -m neuraludf_amd.build --force`")
+        # (NudfMeshUDFSparse came without a version step, which an existing test pins: its size is checked instead)
+        size = getattr(_lib, "nudf_meshudf_sparse_struct_size", None)
+        if size is None or int(size()) != C.sizeof(MeshUDFSparse):
+            v, _lib = (None if size is None else int(size())), None
+            raise NudfError(f"{LIB_PATH} has a NudfMeshUDFSparse of {v} bytes, this package binds {C.sizeof(MeshUDFSparse)}: "
+                            "rebuild with `python -m neuraludf_amd.build --force`")
         _bind(_lib)
         _lib.nudf_gemm_tn_grouped_workspace.restype = C.c_int64
         _lib.nudf_set_chain_t16.argtypes = [C.c_int]

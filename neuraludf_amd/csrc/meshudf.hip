@@ -11,6 +11,7 @@
 #include "nudf_common.h"
 #include "../../include/nudf.h"
 #include "mc_tables.inc"
+#include "meshudf_cell.h"
 
 #define MESHUDF_BLOCK 256
 #define MESHUDF_MIN_N 3
@@ -43,34 +44,13 @@ __global__ __launch_bounds__(MESHUDF_BLOCK) void meshudf_classify_kernel(NudfMes
   float u[8];
 #pragma unroll
   for (int c = 0; c < 8; ++c) u[c] = a.U[base + corner_offset(c, N)];
-  float sum = u[0];
-  int r = 0;                                    // reference corner: largest U, lowest index on ties
+  uint32_t nt;
+  const uint32_t cs = meshudf_cell_case(u, a.mean_thr, a.max_thr,
+                                        [&](int c) { return a.G + 3 * (base + corner_offset(c, N)); }, nt);
+  if (nt) {
 #pragma unroll
-  for (int c = 1; c < 8; ++c) {
-    sum = __fadd_rn(sum, u[c]);
-    if (u[c] > u[r]) r = c;
-  }
-  uint32_t cs = 0, nt = 0;
-  if (__fmul_rn(sum, 0.125f) < a.mean_thr && u[r] <= a.max_thr) {
-    const float* gr = a.G + 3 * (base + corner_offset(r, N));
-    const double rx = gr[0], ry = gr[1], rz = gr[2];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      if (c == r) continue;
-      const float* g = a.G + 3 * (base + corner_offset(c, N));
-      const double d = __dadd_rn(__dadd_rn(__dmul_rn(rx, (double)g[0]), __dmul_rn(ry, (double)g[1])),
-                                 __dmul_rn(rz, (double)g[2]));
-      if (!(d >= 0.0)) cs |= 1u << c;
-    }
-    nt = nudf_mc_ntri[cs];
-    if (nt) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) {
-        const int lo = nudf_mc_edge[e][0] * 4 + nudf_mc_edge[e][1] * 2 + nudf_mc_edge[e][2];
-        const int hi = lo | (4 >> nudf_mc_edge[e][3]);
-        if (((cs >> lo) ^ (cs >> hi)) & 1) a.edge_flag[edge_id(e, base, N)] = 1;   // every writer stores the same 1
-      }
-    }
+    for (int e = 0; e < 12; ++e)
+      if (meshudf_edge_crossed(cs, e)) a.edge_flag[edge_id(e, base, N)] = 1;   // every writer stores the same 1
   }
   a.cell_case[cell] = (uint8_t)cs;
   a.cell_ntri[cell] = (uint8_t)nt;
@@ -107,12 +87,11 @@ __global__ __launch_bounds__(MESHUDF_BLOCK) void meshudf_vertices_kernel(NudfMes
   }
   const int64_t step = axis == 0 ? N * N : (axis == 1 ? N : 1);
   const float ua = a.U[p], ub = a.U[p + step];
-  const float s = __fadd_rn(ua, ub);
-  const float w = s == 0.0f ? 0.5f : __fdiv_rn(ua, s);
+  const float w = meshudf_vertex_weight(ua, ub);
 #pragma unroll
   for (int x = 0; x < 3; ++x) {
     const float xa = a.axes[x * N + idx[x]];
-    v[x] = x == axis ? __fadd_rn(xa, __fmul_rn(w, __fsub_rn(a.axes[x * N + idx[x] + 1], xa))) : xa;
+    v[x] = x == axis ? meshudf_vertex_coord(xa, a.axes[x * N + idx[x] + 1], w) : xa;
   }
 }
 

@@ -510,7 +510,8 @@ class Trainer:
         without its file output; neuraludf_amd.meshing.extract_udf_mesh) -> (vertices np.float32 [V, 3], faces np.int64
         [F, 3]).  world_space: map the vertices with `scale_mat` (the dataset's scale_mats_np[0]) as the runner does.
         `clean`: the clean-up keywords of meshing.extract_udf_mesh (fill_holes, smooth_borders, min_component_faces,
-        keep_largest), all off by default."""
+        keep_largest), all off by default, and its sparse=True, block, lipschitz (query and mesh only the blocks near the
+        surface: the same mesh as long as the UDF is no steeper than `lipschitz`, resolutions up to 4096)."""
         from . import meshing
         if world_space and scale_mat is None:
             raise ValueError("world_space=True needs scale_mat (the dataset's scale_mats_np[0])")
