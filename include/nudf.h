@@ -921,6 +921,87 @@ int nudf_meshudf_sparse_emit(const NudfMeshUDFSparse* args, void* stream);      
 int nudf_meshudf_sparse_vertices(const NudfMeshUDFSparse* args, void* stream);  /* one thread per unique edge */
 
 /* ------------------------------------------------------------------------------------
+ * Level-set marching cubes of a dense scalar grid: the surface {F = level} of a signed or unsigned field
+ * (neuraludf_amd/meshing.py iso_marching_cubes).  Replaces the PyMCubes call of extract_geometry
+ * (models/udf_renderer_blending.py:52-63, reached from Runner.validate_mesh, exp_runner_blending.py:746-761) and meshes
+ * the zero set of SDF networks, which the MeshUDF mesher above is not meant for.  Sign rule: corner c of a cell is `-`
+ * iff F_c < level (fp32 compare); a cell with any non-finite corner (NaN, +-inf) has case 0 and emits nothing.  The
+ * 256-case table is the generated one (csrc/mc_tables.inc): the triangulation of ambiguous cases, the winding (normals
+ * point to the `+` side, F >= level) and all orders are this library's, only the vertex set is that of any marching
+ * cubes -- one vertex per sign-change edge at t = (level - F_a) / (F_b - F_a) from the lower end a, every operation an
+ * explicit fp32 rounding, t clamped to [0, 1] and 0.5 where it is NaN.  Grid, cell and edge numbering, the three
+ * launches and the ordering contract are NudfMeshUDF's: vertices ascending by edge id 3 lin(lower end) + axis, faces by
+ * ascending cell index, then table order; the scans and compactions between the launches are the caller's
+ * (deterministic integer prefix sums).  3 <= N <= 1024.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfIsoSurface {
+  const float* F;            /* [N, N, N] field values                                                               */
+  const float* axes;         /* [3, N] grid coordinate of each index, per axis                                      */
+  uint8_t* cell_case;        /* [(N-1)^3] case index (bit c set: F_c < level), 0 for cells with a non-finite corner (classify) */
+  uint8_t* cell_ntri;        /* [(N-1)^3] triangles of the cell (classify)                                           */
+  uint8_t* edge_flag;        /* [3 N^3] zeroed by the caller; classify stores 1 at every sign-change edge of a cell that
+                                emits triangles                                                                      */
+  const int64_t* cells;      /* [n_cells] compact indices of the cells with triangles, ascending (emit)               */
+  const int64_t* face_off;   /* [n_cells] exclusive prefix sum of their triangle counts (emit)                       */
+  const int64_t* edge_scan;  /* [3 N^3] inclusive prefix sum of edge_flag: vertex of edge e = edge_scan[e] - 1 (emit)  */
+  int64_t* faces;            /* [F, 3] vertex indices (emit)                                                         */
+  const int64_t* edges;      /* [n_edges] ids of the flagged edges, ascending (vertices)                             */
+  float* verts;              /* [n_edges, 3] vertex positions (vertices)                                             */
+  int64_t n_cells;
+  int64_t n_edges;
+  int64_t n_faces;           /* F: emit refuses a face_off that would write past faces[F]                           */
+  int32_t N;
+  float level;
+} NudfIsoSurface;
+int nudf_isosurface_struct_size(void);                                   /* sizeof(NudfIsoSurface): the loader refuses a library that differs */
+int nudf_isosurface_classify(const NudfIsoSurface* args, void* stream);  /* one thread per cell   */
+int nudf_isosurface_emit(const NudfIsoSurface* args, void* stream);      /* one thread per cell with triangles */
+int nudf_isosurface_vertices(const NudfIsoSurface* args, void* stream);  /* one thread per flagged edge */
+
+/* ------------------------------------------------------------------------------------
+ * Sparse level-set marching cubes: the mesher above over the B^3-cell blocks that can hold a cut cell only
+ * (neuraludf_amd/meshing.py iso_sparse_grid, iso_marching_cubes_sparse).  Blocks, bricks, padding and the ordering
+ * contract are NudfMeshUDFSparse's, without gradients.  Selection rule (the caller's, part of the contract): with
+ * h_a = (bound_max[a] - bound_min[a]) / (N - 1), the block half-diagonal r = sqrt(sum_a (B h_a)^2) / 2, and cmin / cmax
+ * the minimum / maximum of the field at the block's eight coarse corners, a block is selected iff
+ * cmin - lipschitz r <= level and cmax + lipschitz r >= level (level: the fp32 value the kernels compare with; the bounds
+ * level + lipschitz r and level - lipschitz r are evaluated in float64 and rounded outward to fp32); a NaN corner never
+ * selects.  Every node of a block lies within r of a corner and a cut cell has a node below the level and one at or above
+ * it, so with |grad F| <= lipschitz no cut cell lies outside a selected block.  The output is the mesh the dense mesher
+ * gives on the same values, in the same order.  3 <= N <= 4096.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfIsoSurfaceSparse {
+  const float* F;             /* [K, (B+1)^3] brick field values                                                     */
+  const float* axes;          /* [3, N] grid coordinate of each index, per axis                                      */
+  const int64_t* blocks;      /* [K] linear ids of the selected blocks, ascending                                    */
+  const int32_t* block_slot;  /* [nb^3] brick of a block, -1: not selected                                           */
+  uint8_t* cell_case;         /* [K, B^3] case index per brick cell, 0 for cells with a non-finite corner and cells past
+                                 the grid (classify)                                                                 */
+  uint8_t* cell_ntri;         /* [K, B^3] triangles of the cell (classify)                                           */
+  const int64_t* cells;       /* [n_cells] global indices (i M + j) M + k of the cells with triangles, ascending       */
+  const int64_t* face_off;    /* [n_cells] exclusive prefix sum of their triangle counts (emit)                      */
+  int64_t* edge_keys;         /* [n_cells, 12] global id of every sign-change edge of the cell, INT64_MAX for the other
+                                 edges (edges)                                                                       */
+  const int64_t* edges;       /* [n_edges] the unique edge ids, ascending (emit: vertex of an edge = its position;
+                                 vertices)                                                                           */
+  int64_t* faces;             /* [F, 3] vertex indices (emit)                                                        */
+  float* verts;               /* [n_edges, 3] vertex positions (vertices)                                            */
+  int64_t n_blocks;           /* K                                                                                   */
+  int64_t n_cells;
+  int64_t n_edges;
+  int64_t n_faces;            /* F: emit refuses a face_off that would write past faces[F]                           */
+  int32_t N;
+  int32_t B;                  /* 4 or 8                                                                              */
+  int32_t nb;                 /* ceil((N - 1) / B)                                                                   */
+  float level;
+} NudfIsoSurfaceSparse;
+int nudf_isosurface_sparse_struct_size(void);                                         /* sizeof(NudfIsoSurfaceSparse) */
+int nudf_isosurface_sparse_classify(const NudfIsoSurfaceSparse* args, void* stream);  /* one workgroup per brick, its F in LDS */
+int nudf_isosurface_sparse_edges(const NudfIsoSurfaceSparse* args, void* stream);     /* one thread per cell with triangles */
+int nudf_isosurface_sparse_emit(const NudfIsoSurfaceSparse* args, void* stream);      /* one thread per cell with triangles */
+int nudf_isosurface_sparse_vertices(const NudfIsoSurfaceSparse* args, void* stream);  /* one thread per unique edge */
+
+/* ------------------------------------------------------------------------------------
  * Point-cloud geometry of the Chamfer evaluation (neuraludf_amd/evaluation.py): replaces the mesh sampling, the radius
  * down-sampling and the two sklearn KD-tree nearest-neighbour sweeps of evaluation/eval_dtu_python.py (:205-370) and
  * eval_deepfashion_python.py (:62-215).  All coordinates are float64 and every expression follows the reference's

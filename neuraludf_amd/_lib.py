@@ -207,6 +207,19 @@ class MeshUDFSparse(C.Structure):
                 ("pad_", i32)]
 
 
+class IsoSurface(C.Structure):
+    _fields_ = [("F", c_fp), ("axes", c_fp), ("cell_case", c_fp), ("cell_ntri", c_fp), ("edge_flag", c_fp), ("cells", c_fp),
+                ("face_off", c_fp), ("edge_scan", c_fp), ("faces", c_fp), ("edges", c_fp), ("verts", c_fp),
+                ("n_cells", C.c_int64), ("n_edges", C.c_int64), ("n_faces", C.c_int64), ("N", i32), ("level", f32)]
+
+
+class IsoSurfaceSparse(C.Structure):
+    _fields_ = [("F", c_fp), ("axes", c_fp), ("blocks", c_fp), ("block_slot", c_fp), ("cell_case", c_fp), ("cell_ntri", c_fp),
+                ("cells", c_fp), ("face_off", c_fp), ("edge_keys", c_fp), ("edges", c_fp), ("faces", c_fp), ("verts", c_fp),
+                ("n_blocks", C.c_int64), ("n_cells", C.c_int64), ("n_edges", C.c_int64), ("n_faces", C.c_int64), ("N", i32),
+                ("B", i32), ("nb", i32), ("level", f32)]
+
+
 class PointCloud(C.Structure):
     _fields_ = [("verts", c_fp), ("faces", c_fp), ("tri_n", c_fp), ("tri_off", c_fp), ("out", c_fp),
                 ("n_verts", C.c_int64), ("n_faces", C.c_int64), ("n_out", C.c_int64), ("out_base", C.c_int64),
@@ -255,6 +268,9 @@ SYMBOLS = [
     "nudf_meshudf_classify", "nudf_meshudf_emit", "nudf_meshudf_vertices",
     "nudf_meshudf_sparse_struct_size", "nudf_meshudf_sparse_classify", "nudf_meshudf_sparse_edges",
     "nudf_meshudf_sparse_emit", "nudf_meshudf_sparse_vertices",
+    "nudf_isosurface_struct_size", "nudf_isosurface_classify", "nudf_isosurface_emit", "nudf_isosurface_vertices",
+    "nudf_isosurface_sparse_struct_size", "nudf_isosurface_sparse_classify", "nudf_isosurface_sparse_edges",
+    "nudf_isosurface_sparse_emit", "nudf_isosurface_sparse_vertices",
     "nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells", "nudf_pc_thin_round", "nudf_pc_nearest",
     "nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit", "nudf_meshtopo_smooth",
     "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump", "nudf_meshtopo_views",
@@ -327,6 +343,10 @@ _ARGTYPES = {
     "nudf_meshudf_vertices": [C.POINTER(MeshUDF), _P],
     **{n: [C.POINTER(MeshUDFSparse), _P] for n in ("nudf_meshudf_sparse_classify", "nudf_meshudf_sparse_edges",
                                                    "nudf_meshudf_sparse_emit", "nudf_meshudf_sparse_vertices")},
+    **{n: [C.POINTER(IsoSurface), _P] for n in ("nudf_isosurface_classify", "nudf_isosurface_emit",
+                                                "nudf_isosurface_vertices")},
+    **{n: [C.POINTER(IsoSurfaceSparse), _P] for n in ("nudf_isosurface_sparse_classify", "nudf_isosurface_sparse_edges",
+                                                      "nudf_isosurface_sparse_emit", "nudf_isosurface_sparse_vertices")},
     **{n: [C.POINTER(PointCloud), _P] for n in ("nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells",
                                                 "nudf_pc_thin_round", "nudf_pc_nearest")},
     **{n: [C.POINTER(MeshTopo), _P] for n in ("nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit",
@@ -375,6 +395,13 @@ def lib():
             v, _lib = (None if size is None else int(size())), None
             raise NudfError(f"{LIB_PATH} has a NudfMeshUDFSparse of {v} bytes, this package binds {C.sizeof(MeshUDFSparse)}: "
                             "rebuild with `python -m neuraludf_amd.build --force`")
+        for name, mirror in (("nudf_isosurface_struct_size", IsoSurface),
+                             ("nudf_isosurface_sparse_struct_size", IsoSurfaceSparse)):      # (the same, for the level-set mesher)
+            size = getattr(_lib, name, None)
+            if size is None or int(size()) != C.sizeof(mirror):
+                v, _lib = (None if size is None else int(size())), None
+                raise NudfError(f"{LIB_PATH}: {name}() is {v}, this package binds {C.sizeof(mirror)} bytes: rebuild with "
+                                "`python -m neuraludf_amd.build --force`")
         _bind(_lib)
         _lib.nudf_gemm_tn_grouped_workspace.restype = C.c_int64
         _lib.nudf_set_chain_t16.argtypes = [C.c_int]

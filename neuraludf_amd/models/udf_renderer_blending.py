@@ -274,15 +274,34 @@ def extract_gradient_fields(bound_min, bound_max, resolution, query_func, device
     return _grid_query(bound_min, bound_max, resolution, query_func, device, 3)
 
 
-def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, device):
-    """(:52-63) field grid (GPU, `extract_fields`) -> marching cubes -> vertices in world units.  The iso-surfacing
-    itself is the reference's third-party dependency (PyMCubes) and stays one: imported on use."""
+MESHERS = ("auto", "gpu", "mcubes")
+
+
+def extract_geometry(bound_min, bound_max, resolution, threshold, query_func, device, mesher="auto", sparse=False, block=8,
+                     lipschitz=2.0):
+    """(:52-63) field grid (GPU) -> marching cubes at `threshold` -> (vertices np.float64 [V, 3] in the box's units,
+    triangles).  mesher: "mcubes" is the reference's path -- the volume is copied to the host and handed to PyMCubes,
+    ImportError when it is not installed; "gpu" meshes the device volume with the library's own level-set mesher
+    (neuraludf_amd.meshing.extract_iso_mesh: no host copy of the field; triangles np.int64; the vertex set is that of any
+    marching cubes, the triangulation of ambiguous cases, the winding and the order are the library's; RuntimeError when
+    the field does not cross the threshold), with sparse=True from the blocks near the surface only (block, lipschitz);
+    "auto" takes PyMCubes when it can be imported and the GPU mesher otherwise."""
+    if mesher not in MESHERS:
+        raise ValueError(f"mesher {mesher!r} is not one of {MESHERS}")
+    mcubes = None
+    if mesher != "gpu":
+        try:
+            import mcubes
+        except ImportError as e:
+            if mesher == "mcubes":
+                raise ImportError("extract_geometry(mesher='mcubes') needs PyMCubes (`mcubes`), like the reference; "
+                                  "mesher='gpu' needs nothing") from e
+    if mcubes is None:
+        from .. import meshing
+        vertices, triangles = meshing.extract_iso_mesh(query_func, resolution, threshold, bound_min, bound_max,
+                                                       sparse=sparse, block=block, lipschitz=lipschitz, device=device)
+        return vertices.astype(np.float64), triangles
     u = extract_fields(bound_min, bound_max, resolution, query_func, device)
-    try:
-        import mcubes
-    except ImportError as e:          # pragma: no cover - PyMCubes is not in the build image
-        raise ImportError("extract_geometry needs PyMCubes (`mcubes`), like the reference; the field grid itself is "
-                          "available from extract_fields()") from e
     vertices, triangles = mcubes.marching_cubes(u, threshold)
     b_max = np.asarray([float(v) for v in bound_max], dtype=np.float64)
     b_min = np.asarray([float(v) for v in bound_min], dtype=np.float64)
@@ -754,9 +773,11 @@ class UDFRendererBlending:
         return meshing.extract_udf_mesh(self.udf_network, resolution, bound_min, bound_max,
                                         dist_threshold_ratio=dist_threshold_ratio, **clean)
 
-    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.01, device='cpu'):
+    def extract_geometry(self, bound_min, bound_max, resolution, threshold=0.01, device='cpu', **kw):
         """(:757-760) -> (vertices, triangles).  The grid query runs on the network's GPU whatever `device` says (the
-        kernels have no CPU path; the reference default 'cpu' only works there for a CPU network)."""
+        kernels have no CPU path; the reference default 'cpu' only works there for a CPU network).  `kw`: mesher
+        ("auto": PyMCubes when installed, else the GPU level-set mesher; "gpu"; "mcubes"), sparse, block, lipschitz of
+        the module-level extract_geometry."""
         dev = next(self.udf_network.parameters()).device
         return extract_geometry(bound_min, bound_max, resolution, threshold,
-                                lambda pts: self.udf_network.udf(pts)[:, 0], dev)
+                                lambda pts: self.udf_network.udf(pts)[:, 0], dev, **kw)

@@ -9,6 +9,7 @@ import io
 
 import os
 
+import numpy as np
 import torch
 
 from . import dist as nudf_dist
@@ -517,6 +518,21 @@ class Trainer:
             raise ValueError("world_space=True needs scale_mat (the dataset's scale_mats_np[0])")
         return meshing.extract_udf_mesh(self.udf, resolution, dist_threshold_ratio=dist_threshold_ratio,
                                         scale_mat=scale_mat if world_space else None, **clean)
+
+    def validate_mesh(self, resolution=256, threshold=0.0, world_space=False, scale_mat=None, **kw):
+        """mesh of the level set {udf = threshold} in the [-1, 1]^3 box (Runner.validate_mesh,
+        exp_runner_blending.py:746-761, without its file output; renderer.extract_geometry) -> (vertices np.float64
+        [V, 3], triangles [F, 3]).  world_space: map the vertices with `scale_mat` (the dataset's scale_mats_np[0]) as the
+        runner does.  `kw`: mesher ("auto": PyMCubes when installed, else the GPU level-set mesher of
+        neuraludf_amd.meshing; "gpu"; "mcubes"), sparse, block, lipschitz."""
+        if world_space and scale_mat is None:
+            raise ValueError("world_space=True needs scale_mat (the dataset's scale_mats_np[0])")
+        vertices, triangles = self.renderer.extract_geometry((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0), resolution,
+                                                             threshold=threshold, **kw)
+        if world_space:
+            S = np.asarray(scale_mat, dtype=np.float64)
+            vertices = vertices * S[0, 0] + S[:3, 3][None]
+        return vertices, triangles
 
     @torch.no_grad()
     def render_image(self, source, img_idx, resolution_level=4, chunk=65536, cos_anneal_ratio=1.0):
