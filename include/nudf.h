@@ -1132,6 +1132,59 @@ int nudf_meshtopo_cc_hook(const NudfMeshTopo* args, void* stream);     /* one th
 int nudf_meshtopo_cc_jump(const NudfMeshTopo* args, void* stream);     /* one thread per face             */
 int nudf_meshtopo_views(const NudfMeshTopo* args, void* stream);       /* one thread per vertex           */
 
+/* ------------------------------------------------------------------------------------
+ * Consistent face orientation and vertex normals (neuraludf_amd/meshclean.py orient_faces, vertex_normals): the step the
+ * reference leaves out after its mesher because trimesh does it with a serial graph traversal ("DO NOT try to
+ * consistently align winding directions: too slow and poor results", extract_mesh.py:218-219), and
+ * trimesh.geometry.weighted_vertex_normals, which it calls at extract_mesh.py:272-275.  A struct of its own: the layout of
+ * NudfMeshTopo is pinned.  Half-edges and keys are NudfMeshTopo's.  A manifold edge is an undirected edge with exactly two
+ * half-edges, of two different faces neither of which repeats a vertex; the caller lists them (me_a, me_b) from the sorted
+ * keys.  Every face f holds one packed word, parent * 2 + parity, set to 2 f by the caller: parity = 1 says that f and its
+ * parent need opposite flips.  One struct; each entry point reads the fields its comment names.
+ *   hook     one thread per manifold edge: finds the roots of its two faces and the parities along the walks; the larger
+ *            root takes 2 * the smaller + (pa ^ pb ^ [both half-edges start at the same vertex]) (64-bit atomicMin),
+ *            *changed = 1;
+ *   jump     one thread per face: word[f] = 2 * root + parity to the root (its own word only).  Rounds of hook + jump
+ *            until *changed stays 0 end with word[f] >> 1 = the smallest face index of f's orientation component and, in
+ *            an orientable component, word[f] & 1 = whether f is wound against that face;
+ *   check    one thread per manifold edge, after the last round: nonorient[word[f] >> 1] = 1 where the parities of its
+ *            two faces contradict the edge (the component is then not orientable);
+ *   outward  one wavefront per component c: comp_sum[c] = sum over the faces comp_face[comp_off[c] .. comp_off[c + 1]) of
+ *            N_f . (c_f - origin), N_f = (p1 - p0) x (p2 - p0) and c_f = (p0 + (p1 + p2)) / 3 with p1 and p2 swapped where
+ *            word[f] & 1; lane l adds the faces l, l + 64, ... of the list in that order, then the 64 lane sums are added in
+ *            lane order (float64, fixed order, no atomics);
+ *   normals  one thread per vertex v: normals[v] = the normalised sum, over the corners corner[corner_off[v] ..
+ *            corner_off[v + 1]) (corner 3 f + k, ascending), of atan2(|n_f|, e1 . e2) * n_f / |n_f|, n_f as N_f above without
+ *            the swap, e1 / e2 the edges from the corner to the next / previous vertex of the face; a face with |n_f| = 0
+ *            or not finite adds nothing; (0, 0, 0) where the sum has length 0 or is not finite.  float64.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfMeshOrient {
+  const int64_t* faces;      /* [n_faces, 3]                                                                         */
+  const int64_t* me_a;       /* [n_medges] first half-edge of each manifold edge (hook, check)                       */
+  const int64_t* me_b;       /* [n_medges] its second half-edge (hook, check)                                        */
+  int64_t* word;             /* [n_faces] parent * 2 + parity, set to 2 f by the caller (hook, jump; check, outward: read) */
+  int32_t* changed;          /* one word, zeroed by the caller before each round (hook)                              */
+  uint8_t* nonorient;        /* [n_faces] zeroed by the caller (check)                                               */
+  const int64_t* comp_off;   /* [n_comps + 1] offsets into comp_face (outward)                                       */
+  const int64_t* comp_face;  /* [n_faces] the faces grouped by component, ascending inside each (outward)            */
+  double* comp_sum;          /* [n_comps] (outward)                                                                  */
+  const double* pos;         /* [n_verts, 3] vertex positions (outward, normals)                                     */
+  const int64_t* corner_off; /* [n_verts + 1] CSR offsets of the corners of each vertex (normals)                    */
+  const int64_t* corner;     /* [3 n_faces] the corners 3 f + k, grouped by vertex, ascending inside each (normals)  */
+  double* normals;           /* [n_verts, 3] (normals)                                                               */
+  double origin[3];          /* outward: the point the faces should turn away from                                   */
+  int64_t n_faces;
+  int64_t n_verts;
+  int64_t n_medges;
+  int64_t n_comps;
+} NudfMeshOrient;
+int nudf_meshorient_struct_size(void);                                     /* sizeof(NudfMeshOrient)          */
+int nudf_meshorient_hook(const NudfMeshOrient* args, void* stream);        /* one thread per manifold edge    */
+int nudf_meshorient_jump(const NudfMeshOrient* args, void* stream);        /* one thread per face             */
+int nudf_meshorient_check(const NudfMeshOrient* args, void* stream);       /* one thread per manifold edge    */
+int nudf_meshorient_outward(const NudfMeshOrient* args, void* stream);     /* one wavefront per component     */
+int nudf_meshorient_normals(const NudfMeshOrient* args, void* stream);     /* one thread per vertex           */
+
 #ifdef __cplusplus
 }
 #endif

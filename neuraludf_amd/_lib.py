@@ -242,6 +242,13 @@ class MeshTopo(C.Structure):
                 ("H", i32), ("W", i32), ("border", i32), ("pad_", i32)]
 
 
+class MeshOrient(C.Structure):
+    _fields_ = [("faces", c_fp), ("me_a", c_fp), ("me_b", c_fp), ("word", c_fp), ("changed", c_fp), ("nonorient", c_fp),
+                ("comp_off", c_fp), ("comp_face", c_fp), ("comp_sum", c_fp), ("pos", c_fp), ("corner_off", c_fp),
+                ("corner", c_fp), ("normals", c_fp), ("origin", C.c_double * 3), ("n_faces", C.c_int64),
+                ("n_verts", C.c_int64), ("n_medges", C.c_int64), ("n_comps", C.c_int64)]
+
+
 # float offsets of the device loss-weight vector (include/nudf.h NUDF_LW_*)
 LW = dict(color_base=0, color=1, color_pixel=2, color_patch=3, igr=4, igr_ns=5, sparse=6, mask=7, color_sum=8)
 LW_COUNT = 16
@@ -274,6 +281,8 @@ SYMBOLS = [
     "nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells", "nudf_pc_thin_round", "nudf_pc_nearest",
     "nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit", "nudf_meshtopo_smooth",
     "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump", "nudf_meshtopo_views",
+    "nudf_meshorient_struct_size", "nudf_meshorient_hook", "nudf_meshorient_jump", "nudf_meshorient_check",
+    "nudf_meshorient_outward", "nudf_meshorient_normals",
 ]
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -352,6 +361,8 @@ _ARGTYPES = {
     **{n: [C.POINTER(MeshTopo), _P] for n in ("nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit",
                                               "nudf_meshtopo_smooth", "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump",
                                               "nudf_meshtopo_views")},
+    **{n: [C.POINTER(MeshOrient), _P] for n in ("nudf_meshorient_hook", "nudf_meshorient_jump", "nudf_meshorient_check",
+                                                "nudf_meshorient_outward", "nudf_meshorient_normals")},
 }
 
 _lib = None
@@ -396,7 +407,8 @@ def lib():
             raise NudfError(f"{LIB_PATH} has a NudfMeshUDFSparse of {v} bytes, this package binds {C.sizeof(MeshUDFSparse)}: "
                             "rebuild with `python -m neuraludf_amd.build --force`")
         for name, mirror in (("nudf_isosurface_struct_size", IsoSurface),
-                             ("nudf_isosurface_sparse_struct_size", IsoSurfaceSparse)):      # (the same, for the level-set mesher)
+                             ("nudf_isosurface_sparse_struct_size", IsoSurfaceSparse),       # (the same, for the level-set mesher
+                             ("nudf_meshorient_struct_size", MeshOrient)):                   # and the face orientation)
             size = getattr(_lib, name, None)
             if size is None or int(size()) != C.sizeof(mirror):
                 v, _lib = (None if size is None else int(size())), None

@@ -5,6 +5,9 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
     holes        fill_holes          extract_mesh.py:222-223 (trimesh fill_holes): loops of 3 get one triangle, of 4 two
     borders      smooth_borders      extract_mesh.py:238-265: 5 Jacobi steps of the border Laplacian, lambda = 0.3
     components   face_components, filter_components     clean_dtu_mesh.py:158-191
+    orientation  orient_faces        consistent winding per component (csrc/meshorient.hip); the reference leaves it out
+                                     (extract_mesh.py:218-219: trimesh's serial traversal is "too slow")
+    normals      vertex_normals      extract_mesh.py:272-275 (trimesh weighted_vertex_normals, angle-weighted)
     views        clean_by_views, clean_dtu_mesh         clean_dtu_mesh.py:36-154 (mask and visual-hull cleaning)
     masks        ellipse_footprint, dilate_masks, load_dtu_views
 
@@ -18,12 +21,16 @@ Where the definitions differ from the libraries the reference calls:
     stay open.  The winding of a new face is a vote over its boundary edges (see fill_holes).
   * two faces are adjacent when they share an undirected edge of any multiplicity; trimesh's face_adjacency pairs only
     the edges with exactly two faces.
+  * orient_faces links faces over the edges with exactly two faces only (trimesh's face_adjacency, here on purpose: an
+    edge with three faces says nothing about winding), never guesses on a component that cannot be oriented, and picks
+    between the two consistent windings by a stated rule (trimesh keeps whatever its traversal meets first).
   * the structuring element is restated from the formula in OpenCV's documentation (ellipse_footprint); cv2 is not
     available to check it against.
 """
 from __future__ import annotations
 
 import glob
+import math
 import os
 from typing import NamedTuple
 
@@ -230,6 +237,137 @@ def _face_components(faces, n_verts, table, _info=None):
     if _info is not None:
         _info["rounds"] = rounds
     return labels
+
+
+class Orientation(NamedTuple):
+    """faces [F, 3] int64 with the chosen faces flipped ([a, b, c] -> [a, c, b]); flipped [F] bool; labels [F] int64: the
+    smallest face index of each face's orientation component; orientable [F] bool: the verdict on the face's component"""
+    faces: torch.Tensor
+    flipped: torch.Tensor
+    labels: torch.Tensor
+    orientable: torch.Tensor
+
+
+def _check_origin(outward_from):
+    if outward_from is None:
+        return None
+    try:
+        o = [float(x) for x in outward_from]
+    except (TypeError, ValueError):
+        raise ValueError(f"outward_from must be three finite numbers (got {outward_from!r})") from None
+    if len(o) != 3 or not all(math.isfinite(x) for x in o):
+        raise ValueError(f"outward_from must be three finite numbers (got {outward_from!r})")
+    return o
+
+
+def _manifold_edges(faces, n_verts):
+    """the two half-edges of every manifold edge -> (me_a [M], me_b [M]), ordered by edge key: an undirected edge with
+    exactly two half-edges, of two different faces neither of which repeats a vertex"""
+    a, b = faces.reshape(-1), faces.roll(-1, 1).reshape(-1)
+    he_key, he_id = torch.sort(torch.minimum(a, b) * n_verts + torch.maximum(a, b), stable=True)
+    eq = he_key[1:] == he_key[:-1]
+    pair = eq.clone()                                 # position j: keys j and j + 1 are equal and no neighbour joins them
+    pair[1:] &= ~eq[:-1]
+    pair[:-1] &= ~eq[1:]
+    j = torch.nonzero(pair).reshape(-1)
+    ha, hb = he_id[j], he_id[j + 1]
+    degenerate = (faces[:, 0] == faces[:, 1]) | (faces[:, 1] == faces[:, 2]) | (faces[:, 0] == faces[:, 2])
+    fa, fb = ha // 3, hb // 3
+    keep = (fa != fb) & ~degenerate[fa] & ~degenerate[fb]
+    return ha[keep].contiguous(), hb[keep].contiguous()
+
+
+def orient_faces(verts, faces, outward_from=None, _info=None):
+    """winds the faces of every orientable component consistently -> Orientation(faces, flipped, labels, orientable).
+    Two faces across a manifold edge (exactly two half-edges, of two different faces without a repeated vertex) are
+    compatible when they run along it in opposite directions; a component is a set of faces connected over manifold edges
+    (border edges and edges with three or more faces connect nothing; a face with a repeated vertex is a component of its
+    own and is never flipped), labelled by its smallest face index.  An orientable component has exactly two sets of flips
+    that make all its manifold edges compatible, each the complement of the other: the one that flips fewer faces is
+    taken, on a tie the one that leaves the component's smallest face alone.  With outward_from = (x, y, z) the set for
+    which S = sum_f N_f . (c_f - outward_from) is positive is taken instead (N_f = (p1 - p0) x (p2 - p0) after the flips,
+    c_f = (p0 + (p1 + p2)) / 3, float64, summed in a fixed order: the other set gives exactly -S); where S is 0 or not
+    finite the first rule decides.  A component that cannot be oriented is returned as it came and reported in
+    `orientable`.  A flip is [a, b, c] -> [a, c, b]: faces keep their order and their first vertex.  A parity union-find
+    over the faces: rounds of hooking over the manifold edges and pointer jumping as in face_components, one 4-byte
+    read-back per round; the result does not depend on the order in which the atomics land.  (`_info`: a dict that
+    receives rounds, components, orientable, non_orientable, flipped.)"""
+    verts, faces = _check_mesh(verts, faces)
+    origin = _check_origin(outward_from)
+    n, n_verts, dev = faces.shape[0], verts.shape[0], faces.device
+    info = dict(rounds=0, components=0, orientable=0, non_orientable=0, flipped=0)
+    if n == 0:
+        if _info is not None:
+            _info.update(info)
+        none = torch.zeros(0, dtype=torch.bool, device=dev)
+        return Orientation(faces, none, torch.zeros(0, dtype=torch.int64, device=dev), none.clone())
+    me_a, me_b = _manifold_edges(faces, n_verts)
+    word = torch.arange(n, dtype=torch.int64, device=dev) * 2
+    changed = torch.zeros(1, dtype=torch.int32, device=dev)
+    nonorient = torch.zeros(n, dtype=torch.uint8, device=dev)
+    d = _lib.MeshOrient(faces=ptr(faces), me_a=ptr(me_a), me_b=ptr(me_b), word=ptr(word), changed=ptr(changed),
+                        nonorient=ptr(nonorient), n_faces=n, n_verts=n_verts, n_medges=me_a.numel())
+    rounds = 0
+    while me_a.numel():
+        if rounds > n:                                       # every round that changes something lowers a parent
+            raise RuntimeError("orient_faces did not converge")
+        changed.zero_()
+        call("nudf_meshorient_hook", d)
+        call("nudf_meshorient_jump", d)
+        rounds += 1
+        if int(changed.item()) == 0:
+            break
+    call("nudf_meshorient_check", d)
+    labels, parity = word >> 1, (word & 1).bool()
+    orientable = nonorient[labels] == 0
+    size = torch.bincount(labels, minlength=n)
+    complement = 2 * torch.bincount(labels[parity], minlength=n) > size       # per label: the other set flips fewer faces
+    if origin is not None:
+        comps = torch.nonzero(size).reshape(-1)
+        comp_off = torch.zeros(comps.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(size[comps], 0, out=comp_off[1:])
+        comp_face = torch.sort(labels, stable=True).indices              # ascending face index inside a component
+        pos = verts.double().contiguous()
+        comp_sum = torch.empty(comps.numel(), dtype=torch.float64, device=dev)
+        d.comp_off, d.comp_face, d.comp_sum, d.pos, d.n_comps = ptr(comp_off), ptr(comp_face), ptr(comp_sum), ptr(pos), \
+            comps.numel()
+        d.origin[0], d.origin[1], d.origin[2] = origin
+        call("nudf_meshorient_outward", d)
+        decides = torch.isfinite(comp_sum) & (comp_sum != 0)
+        complement[comps] = torch.where(decides, comp_sum < 0, complement[comps])
+    flipped = (parity ^ complement[labels]) & orientable
+    out = torch.where(flipped[:, None], faces[:, [0, 2, 1]], faces)
+    if _info is not None:
+        info.update(rounds=rounds, components=int((size > 0).sum()), non_orientable=int(nonorient.sum()),
+                    flipped=int(flipped.sum()))
+        info["orientable"] = info["components"] - info["non_orientable"]
+        _info.update(info)
+    return Orientation(out, flipped, labels, orientable)
+
+
+def vertex_normals(verts, faces, dtype=torch.float32):
+    """angle-weighted vertex normals -> [V, 3] `dtype` (float32 or float64), computed in float64 and cast at the end:
+    trimesh's weighted_vertex_normals, which the reference calls (extract_mesh.py:272-275).  With n_f = (p1 - p0) x
+    (p2 - p0) of face f, a face whose |n_f| is 0 or not finite adds nothing; at corner k of f the weight is theta =
+    atan2(|n_f|, e1 . e2), e1 / e2 the edges from the corner to the next / previous vertex of the face; N_v = the sum of
+    theta * (n_f / |n_f|) over the corners at v in ascending 3 f + k, and the result N_v / |N_v|, or (0, 0, 0) where
+    |N_v| is 0 or not finite or no face uses the vertex.  The normals follow the winding: orient_faces first."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"dtype must be torch.float32 or torch.float64 (got {dtype})")
+    verts, faces = _check_mesh(verts, faces)
+    n_verts, dev = verts.shape[0], verts.device
+    normals = torch.zeros((n_verts, 3), dtype=torch.float64, device=dev)
+    if n_verts == 0 or faces.shape[0] == 0:
+        return normals.to(dtype)
+    pos = verts.double().contiguous()
+    flat = faces.reshape(-1)
+    corner = torch.sort(flat, stable=True).indices                       # corners 3 f + k by vertex, ascending inside
+    corner_off = torch.zeros(n_verts + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(flat, minlength=n_verts), 0, out=corner_off[1:])
+    d = _lib.MeshOrient(faces=ptr(faces), pos=ptr(pos), corner_off=ptr(corner_off), corner=ptr(corner),
+                        normals=ptr(normals), n_faces=faces.shape[0], n_verts=n_verts)
+    call("nudf_meshorient_normals", d)
+    return normals.to(dtype)
 
 
 def compact_mesh(verts, faces, vertex_mask=None, face_mask=None, drop_unreferenced=True):

@@ -768,7 +768,8 @@ class UDFRendererBlending:
         """open-surface mesh of the UDF (neuraludf_amd.meshing.extract_udf_mesh, MeshUDF on the GPU; the reference's
         extract_mesh.get_mesh_udf_fast) -> (vertices np.float32 [V, 3], faces np.int64 [F, 3]) in the box's units.
         `clean`: its clean-up keywords (fill_holes, smooth_borders, min_component_faces, keep_largest), off by default,
-        and sparse=True, block, lipschitz (sparse extraction from the blocks near the surface, resolutions up to 4096)"""
+        and sparse=True, block, lipschitz (sparse extraction from the blocks near the surface, resolutions up to 4096),
+        orient=True / outward_from (consistent winding of the faces as the last step)"""
         from .. import meshing
         return meshing.extract_udf_mesh(self.udf_network, resolution, bound_min, bound_max,
                                         dist_threshold_ratio=dist_threshold_ratio, **clean)

@@ -512,7 +512,9 @@ class Trainer:
         [F, 3]).  world_space: map the vertices with `scale_mat` (the dataset's scale_mats_np[0]) as the runner does.
         `clean`: the clean-up keywords of meshing.extract_udf_mesh (fill_holes, smooth_borders, min_component_faces,
         keep_largest), all off by default, and its sparse=True, block, lipschitz (query and mesh only the blocks near the
-        surface: the same mesh as long as the UDF is no steeper than `lipschitz`, resolutions up to 4096)."""
+        surface: the same mesh as long as the UDF is no steeper than `lipschitz`, resolutions up to 4096), and
+        orient=True / outward_from=(x, y, z) in the box's coordinates (wind the faces of every orientable component
+        consistently as the last step, away from that point when given)."""
         from . import meshing
         if world_space and scale_mat is None:
             raise ValueError("world_space=True needs scale_mat (the dataset's scale_mats_np[0])")
