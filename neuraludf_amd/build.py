@@ -27,11 +27,12 @@ KERNEL_SOURCES = {
                   "../include/nudf.h", "mlp.py"],
     "gemm_tn": ["csrc/gemm_tn_f32_mfma.hip", "csrc/nudf_common.h", "../include/nudf.h", "mlp.py"],
     "composite": ["csrc/composite.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshudf": ["csrc/meshudf.hip", "csrc/meshudf_cell.h", "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshudf_sparse": ["csrc/meshudf_sparse.hip", "csrc/meshudf_cell.h", "csrc/mc_tables.inc", "csrc/nudf_common.h",
-                       "../include/nudf.h"],
-    "isosurface": ["csrc/isosurface.hip", "csrc/isosurface_cell.h", "csrc/meshudf_cell.h", "csrc/mc_tables.inc",
-                   "csrc/nudf_common.h", "../include/nudf.h"],
+    "meshudf": ["csrc/meshudf.hip", "csrc/mc_pipeline.h", "csrc/meshudf_cell.h", "csrc/isosurface_cell.h",
+                "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
+    "meshudf_sparse": ["csrc/meshudf_sparse.hip", "csrc/mc_pipeline.h", "csrc/meshudf_cell.h", "csrc/isosurface_cell.h",
+                       "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
+    "isosurface": ["csrc/isosurface.hip", "csrc/mc_pipeline.h", "csrc/isosurface_cell.h", "csrc/meshudf_cell.h",
+                   "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
     "pointcloud": ["csrc/pointcloud.hip", "csrc/nudf_common.h", "../include/nudf.h"],
     "meshtopo": ["csrc/meshtopo.hip", "csrc/nudf_common.h", "../include/nudf.h"],
     "meshorient": ["csrc/meshorient.hip", "csrc/nudf_common.h", "../include/nudf.h"],

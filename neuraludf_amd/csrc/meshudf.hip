@@ -1,135 +1,12 @@
 // MeshUDF open-surface extraction from a dense UDF grid (include/nudf.h NudfMeshUDF): the per-cell and per-edge work of
 // the mesher the reference runs serially in Cython (custom_mc udf_mc_lewiner, called by extract_mesh.get_mesh_udf_fast).
-// Signs are chosen per cell with no propagation between cells, so every cell is independent:
-//   classify  -- one thread per cell, consecutive threads along k (the contiguous grid axis): active test, pseudo-signs,
-//                case index, triangle count, and a 1 stored at every sign-change edge of a cell that emits triangles;
-//   emit      -- one thread per cell with triangles: its faces at the caller's exclusive scan of the counts, vertex
-//                indices from the caller's inclusive scan of the edge flags;
-//   vertices  -- one thread per flagged edge: the vertex at t = U_a / (U_a + U_b) from the lower end.
-// Every output position is a function of the inputs alone (no atomics): the mesh is identical from run to run.
-// Cell indices fit 32 bits ((N-1)^3 < 2^30 for N <= 1024); grid point and edge ids (3 N^3 > 2^31) are 64-bit.
-#include "nudf_common.h"
-#include "../../include/nudf.h"
-#include "mc_tables.inc"
-#include "meshudf_cell.h"
+// The dense pipeline of mc_pipeline.h under McUdfRule: signs are chosen per cell from the gradients with no propagation
+// between cells (meshudf_cell.h), so every cell is independent; the vertex of an edge lies at t = U_a / (U_a + U_b) from
+// its lower end.
+#include "mc_pipeline.h"
 
-#define MESHUDF_BLOCK 256
-#define MESHUDF_MIN_N 3
-#define MESHUDF_MAX_N 1024
+__device__ __forceinline__ const float* mc_field(const NudfMeshUDF& a) { return a.U; }
 
-// offset of corner c of a cell from its lowest corner (corner bits: 4 = x, 2 = y, 1 = z; neuraludf_amd/mc_tables.py)
-__device__ __forceinline__ int64_t corner_offset(int c, int64_t N) {
-  return ((c >> 2) & 1) * N * N + ((c >> 1) & 1) * N + (c & 1);
-}
-
-// lowest grid point of compact cell index `cell`
-__device__ __forceinline__ int64_t cell_base(uint32_t cell, uint32_t M, int64_t N) {
-  const uint32_t k = cell % M, r = cell / M;
-  const uint32_t j = r % M, i = r / M;
-  return ((int64_t)i * N + j) * N + k;
-}
-
-// global id of edge e of the cell whose lowest grid point is `base`
-__device__ __forceinline__ int64_t edge_id(int e, int64_t base, int64_t N) {
-  const int64_t p = base + nudf_mc_edge[e][0] * N * N + nudf_mc_edge[e][1] * N + nudf_mc_edge[e][2];
-  return 3 * p + nudf_mc_edge[e][3];
-}
-
-__global__ __launch_bounds__(MESHUDF_BLOCK) void meshudf_classify_kernel(NudfMeshUDF a) {
-  const uint32_t M = (uint32_t)a.N - 1;
-  const uint64_t cell = (uint64_t)blockIdx.x * MESHUDF_BLOCK + threadIdx.x;
-  if (cell >= (uint64_t)M * M * M) return;
-  const int64_t N = a.N;
-  const int64_t base = cell_base((uint32_t)cell, M, N);
-  float u[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) u[c] = a.U[base + corner_offset(c, N)];
-  uint32_t nt;
-  const uint32_t cs = meshudf_cell_case(u, a.mean_thr, a.max_thr,
-                                        [&](int c) { return a.G + 3 * (base + corner_offset(c, N)); }, nt);
-  if (nt) {
-#pragma unroll
-    for (int e = 0; e < 12; ++e)
-      if (meshudf_edge_crossed(cs, e)) a.edge_flag[edge_id(e, base, N)] = 1;   // every writer stores the same 1
-  }
-  a.cell_case[cell] = (uint8_t)cs;
-  a.cell_ntri[cell] = (uint8_t)nt;
-}
-
-__global__ __launch_bounds__(MESHUDF_BLOCK) void meshudf_emit_kernel(NudfMeshUDF a) {
-  const uint64_t t = (uint64_t)blockIdx.x * MESHUDF_BLOCK + threadIdx.x;
-  if (t >= (uint64_t)a.n_cells) return;
-  const uint32_t M = (uint32_t)a.N - 1;
-  const int64_t cell = a.cells[t];
-  if (cell < 0 || cell >= (int64_t)M * M * M) return;
-  const int64_t N = a.N;
-  const int64_t base = cell_base((uint32_t)cell, M, N);
-  const uint32_t cs = a.cell_case[cell];
-  const int nt = nudf_mc_ntri[cs];
-  const int64_t off = a.face_off[t];
-  if (off < 0 || off + nt > a.n_faces) return;
-  int64_t* out = a.faces + 3 * off;
-  for (int q = 0; q < 3 * nt; ++q) out[q] = a.edge_scan[edge_id(nudf_mc_tri[cs][q], base, N)] - 1;
-}
-
-__global__ __launch_bounds__(MESHUDF_BLOCK) void meshudf_vertices_kernel(NudfMeshUDF a) {
-  const uint64_t t = (uint64_t)blockIdx.x * MESHUDF_BLOCK + threadIdx.x;
-  if (t >= (uint64_t)a.n_edges) return;
-  const int64_t N = a.N;
-  const int64_t eid = a.edges[t];
-  float* v = a.verts + 3 * t;
-  const int64_t p = eid / 3;
-  const int axis = (int)(eid - 3 * p);
-  const int64_t idx[3] = {p / (N * N), (p / N) % N, p % N};
-  if (eid < 0 || p >= N * N * N || idx[axis] >= N - 1) {        // not an edge of the grid: no vertex
-    v[0] = v[1] = v[2] = __int_as_float(0x7fc00000);
-    return;
-  }
-  const int64_t step = axis == 0 ? N * N : (axis == 1 ? N : 1);
-  const float ua = a.U[p], ub = a.U[p + step];
-  const float w = meshudf_vertex_weight(ua, ub);
-#pragma unroll
-  for (int x = 0; x < 3; ++x) {
-    const float xa = a.axes[x * N + idx[x]];
-    v[x] = x == axis ? meshudf_vertex_coord(xa, a.axes[x * N + idx[x] + 1], w) : xa;
-  }
-}
-
-static int check_n(const NudfMeshUDF& a, const char* where) {
-  if (a.N < MESHUDF_MIN_N || a.N > MESHUDF_MAX_N) {
-    nudf_set_error(where, hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
-  return 0;
-}
-
-static unsigned blocks(uint64_t n) { return (unsigned)((n + MESHUDF_BLOCK - 1) / MESHUDF_BLOCK); }
-
-extern "C" int nudf_meshudf_classify(const NudfMeshUDF* args, void* stream) {
-  const NudfMeshUDF& a = *args;
-  if (int rc = check_n(a, "nudf_meshudf_classify: N outside [3, 1024]")) return rc;
-  const uint64_t M = (uint64_t)a.N - 1;
-  hipLaunchKernelGGL(meshudf_classify_kernel, dim3(blocks(M * M * M)), dim3(MESHUDF_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_meshudf_classify");
-  return 0;
-}
-
-extern "C" int nudf_meshudf_emit(const NudfMeshUDF* args, void* stream) {
-  const NudfMeshUDF& a = *args;
-  if (int rc = check_n(a, "nudf_meshudf_emit: N outside [3, 1024]")) return rc;
-  if (a.n_cells <= 0) return 0;
-  hipLaunchKernelGGL(meshudf_emit_kernel, dim3(blocks((uint64_t)a.n_cells)), dim3(MESHUDF_BLOCK), 0, (hipStream_t)stream,
-                     a);
-  NUDF_CHECK_LAUNCH("nudf_meshudf_emit");
-  return 0;
-}
-
-extern "C" int nudf_meshudf_vertices(const NudfMeshUDF* args, void* stream) {
-  const NudfMeshUDF& a = *args;
-  if (int rc = check_n(a, "nudf_meshudf_vertices: N outside [3, 1024]")) return rc;
-  if (a.n_edges <= 0) return 0;
-  hipLaunchKernelGGL(meshudf_vertices_kernel, dim3(blocks((uint64_t)a.n_edges)), dim3(MESHUDF_BLOCK), 0,
-                     (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_meshudf_vertices");
-  return 0;
-}
+MC_DENSE_ENTRY(nudf_meshudf_classify, NudfMeshUDF, mc_dense_cells(a), mc_dense_classify_kernel<McUdfRule, NudfMeshUDF>)
+MC_DENSE_ENTRY(nudf_meshudf_emit, NudfMeshUDF, a.n_cells, mc_dense_emit_kernel<NudfMeshUDF>)
+MC_DENSE_ENTRY(nudf_meshudf_vertices, NudfMeshUDF, a.n_edges, mc_dense_vertices_kernel<McUdfRule, NudfMeshUDF>)
