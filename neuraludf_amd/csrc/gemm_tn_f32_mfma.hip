@@ -26,9 +26,6 @@
 #include <string.h>
 #include <type_traits>
 
-#ifndef NUDF_MMA16_REPEAT
-#define NUDF_MMA16_REPEAT 1  // timing probe (see mlp_chain.hip)
-#endif
 #define BM 128
 #define BN 128
 #define BK 32
@@ -36,7 +33,12 @@
 #define T_TILE (BK * LDT)
 #define TN_MAX_TILES 64
 #define TN_WS_TILE (BM * BN + BM)   // floats per workspace slot: 4 waves x 4 sub-tiles x 64 lanes x 16 accumulators + bias
-#define TNF_NO_EPILOGUE 2           // timing experiments only: results are dropped
+// Bits 2 ("drop the epilogue") and 4 ("skip the bias sums") computed wrong results on purpose and are RETIRED: the host masks
+// them off (nudf_set_tn_flags, NUDF_TN_FLAGS), so no kernel ever sees them set.  The three split-image kernels (tn3, tn2,
+// tn3w) still carry the two tests: without them hipcc hoists epilogue address arithmetic into the staging code and
+// reschedules it, and an unmeasured reshuffle of those kernels is not worth two dead scalar tests.
+#define TNF_RETIRED (2 | 4)
+#define TNF_NO_EPILOGUE 2
 #define TNF_NO_BIAS 4
 #define TNF_ATOMICS 8
 #define TNF_UNIFORM_CHUNKS 16
@@ -204,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnPlan g) {
     }
   };
   // bias gradient = column sums of A, taken from the registers on their way to LDS (tiles of the first tile column)
-  const bool do_bias = (q.dbias != nullptr) && (tl.tj == 0) && !(g.flags & TNF_NO_BIAS);
+  const bool do_bias = (q.dbias != nullptr) && (tl.tj == 0);
   f32x4 bacc = {0.f, 0.f, 0.f, 0.f}, bacc2 = {0.f, 0.f, 0.f, 0.f};   // bacc2: columns 4..7 of a bf16 operand's 8
   f32x4 bacc3 = {0.f, 0.f, 0.f, 0.f}, bacc4 = {0.f, 0.f, 0.f, 0.f};   // blocked fp32 operand: one accumulator per pass
   auto widen = [](const f32x4& raw, f32x4& lo, f32x4& hi) {   // 8 bf16 -> 8 fp32 (memory order)
@@ -347,8 +349,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnPlan g) {
           b16[j] = __builtin_convertvector(v, bf16x8);
         }
 #pragma unroll
-        for (int rep = 0; rep < NUDF_MMA16_REPEAT; ++rep)
-#pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int i = 0; i < 2; ++i)
@@ -369,7 +369,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnPlan g) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = vr[(16 * kk + e) * LDT + 32 * s];
         const bf16x8 v16 = __builtin_convertvector(v, bf16x8);
-        for (int rep = 0; rep < NUDF_MMA16_REPEAT; ++rep)
         acc[s] = kLay == 0 ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(v16, f16, acc[s], 0, 0, 0)
                            : __builtin_amdgcn_mfma_f32_32x32x16_bf16(f16, v16, acc[s], 0, 0, 0);
       }
@@ -609,7 +608,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_group_kernel(TnPlan g) {
            ((long long)(__builtin_amdgcn_s_getreg(6164) & 15) << 32);
     d[3] = nk | (((long long)__builtin_amdgcn_s_memtime() - c_begin) << 16);   // shader-clock ticks of the same span
   }
-  if (g.flags & TNF_NO_EPILOGUE) return;
   float* slot = g.ws ? g.ws + (size_t)slot_id * TN_WS_TILE : nullptr;
   if (do_bias) {   // the loop's last barrier has passed: the operand tiles are free
     int ngroups;
@@ -671,7 +669,7 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(TnPlan g) {
   const int i0 = tl.ti * BM, j0 = tl.tj * BN;
   const float* ws = g.ws + (size_t)tl.blk_start * TN_WS_TILE;
   if (slice == 16) {
-    if (!q.dbias || tl.tj != 0 || (g.flags & TNF_NO_BIAS)) return;
+    if (!q.dbias || tl.tj != 0) return;
     const int col = threadIdx.x;
     if (col >= BM || i0 + col >= q.NA) return;
     float s = 0.0f;
@@ -747,7 +745,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn16_group_kernel(TnPlan g) {
   const int mend = min(mbeg + tl.rows_per_block, g.M);
   const int nk = (mend - mbeg + BK16 - 1) / BK16;
   const int pr = tid >> 4, pc = (tid & 15) * 8;
-  const bool do_bias = (q.dbias != nullptr) && (tl.tj == 0) && !(g.flags & TNF_NO_BIAS);
+  const bool do_bias = (q.dbias != nullptr) && (tl.tj == 0);
   f32x4 bias_lo = {0.f, 0.f, 0.f, 0.f}, bias_hi = {0.f, 0.f, 0.f, 0.f};
 
   f32x16 acc[4];
@@ -893,8 +891,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn16_group_kernel(TnPlan g) {
       for (int kk = 0; kk < BK16 / 16; ++kk) {
         if (kk + 1 < BK16 / 16) rd((kk + 1) & 1, kk + 1);
 #pragma unroll
-        for (int rep = 0; rep < NUDF_MMA16_REPEAT; ++rep)
-#pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int i = 0; i < 2; ++i)
@@ -945,7 +941,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn16_group_kernel(TnPlan g) {
     d[0] = t_begin; d[1] = (long long)wall_clock64(); d[2] = 2 * 16 + 4;
     d[3] = nk | (((long long)__builtin_amdgcn_s_memtime() - c_begin) << 16);
   }
-  if (g.flags & TNF_NO_EPILOGUE) return;
   float* slot = g.ws ? g.ws + (size_t)slot_id * TN_WS_TILE : nullptr;
   if (do_bias) {   // the loop's last barrier has passed: the operand image is free
     float* red = reinterpret_cast<float*>(smem);
@@ -998,24 +993,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn16_group_kernel(TnPlan g) {
 // waves, four staging waves, double-buffered image, one barrier per step) was built and measured slower in every variant
 // (1.30-1.51 ms against 1.01-1.15 ms per step; profiles/r04_bf16x3_experiments.txt item 7) and removed.
 // =======================================================================================================
-#ifndef NUDF_TN3_DIST2
-#define NUDF_TN3_DIST2 1
-#endif
-#ifndef NUDF_TN3_PIPE
-#define NUDF_TN3_PIPE 1      // A/B build switch: 1 = the split of the next k-step interleaved with this step's MFMAs (see pstep)
-#endif
-#ifndef NUDF_TN3_LDSPREAD
-#define NUDF_TN3_LDSPREAD 0  // A/B build switch (with NUDF_TN3_PIPE): 1 = the row requests of step kt + 2 issued between the MFMA groups (measured 8 % slower: the requests are throttled by the memory path wherever they are issued)
-#endif
-#ifndef NUDF_TN3_BUFLOAD
-#define NUDF_TN3_BUFLOAD 1   // A/B build switch: 1 = the steady state's row requests are buffer loads (scalar row offset, 32-bit lane offset)
-#endif
-#ifndef NUDF_TN3_STAMPS
-#define NUDF_TN3_STAMPS 0
-#endif
-#ifndef NUDF_TN3_WGS
-#define NUDF_TN3_WGS 2       // workgroups per CU the split-image kernel is register-allocated for (3: 13 spilled registers)
-#endif
+constexpr int TN3_WGS = 2;   // workgroups per CU the split-image kernel is register-allocated for (3: 13 spilled registers)
 #define BK3 32
 #define LD3 132
 #define T3 (16 * LD3)
@@ -1030,7 +1008,7 @@ __device__ __forceinline__ void tn_split3_pair(float x0, float x1, unsigned& p0,
   p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
 }
 
-__global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPlan g) {
+__global__ __launch_bounds__(256, TN3_WGS) void gemm_tn3_group_kernel(TnPlan g) {
   // image: [operand 2][plane 3][k-pair group 4][column 128][4 dwords] -- the four k-pairs (8 rows) a lane's MFMA operand
   // needs for one column are ONE 16-byte unit: a fragment is one conflict-free ds_read_b128 (the [k-pair][column] layout of
   // the 16-bit kernel costs four ds_read_b32 at half the LDS rate, and its 32-byte-per-lane staging writes hit every bank
@@ -1144,17 +1122,10 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
   __syncthreads();
   auto kstep = [&](int kt, float (&la)[16], float (&lb)[16], float (&ua)[16], float (&ub)[16]) {
     // la / lb: free set, receives step kt + 2; ua / ub: holds step kt + 1 (requested one step ago), stored after the MFMAs
-#if NUDF_TN3_DIST2
     if (kt + 2 < nk) {
       load(pa, lda, la, kt + 2);
       load(pb, ldb, lb, kt + 2);
     }
-#else      // A/B: requests one step ahead only (into the set that is stored after this step's MFMAs)
-    if (kt + 1 < nk && kt > 0) {
-      load(pa, lda, ua, kt + 1);
-      load(pb, ldb, ub, kt + 1);
-    }
-#endif
     __builtin_amdgcn_sched_barrier(0);   // keep the global loads above the MFMA block
     mma();
     __builtin_amdgcn_sched_barrier(0);
@@ -1170,15 +1141,12 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
   // step -- as many as the split), and hipcc, recycling those address registers, put an s_waitcnt vmcnt(0) in front of every
   // step's requests: the "two steps ahead" prefetch waited for the previous step's rows first.  Here a step's rows start at a
   // wave-uniform offset formed by the scalar unit and a thread's only address register is its column offset: a load is ONE
-  // instruction (buffer_load_dword v, v_col, s[descriptor], s_row offen; NUDF_TN3_BUFLOAD), no vector address arithmetic, nothing
+  // instruction (buffer_load_dword v, v_col, s[descriptor], s_row offen), no vector address arithmetic, nothing
   // to wait for; full steps also need no row-validity selects in the split.  (The first form of this loop used flat loads from
   // `base + r * ld`: hipcc kept those bases in VECTOR registers -- a chain of 30 v_lshl_add_u64 per step, still 39 % fewer VALU
   // operations than the generic staging; the descriptor form is the one without any.)  Same values, same order: C and dbias are
   // unchanged bit for bit.
   int kt0 = 0;
-#if NUDF_TN3_STAMPS     // tuning build (scripts/tn3_phases.py): shader-clock ticks of waves 0 / 3 per segment of the pipelined steps
-  long long tk_load = 0, tk_mma = 0, tk_bar1 = 0, tk_store = 0, tk_bar2 = 0;
-#endif
   if (!(g.flags & TNF_GENERIC_STAGE)) {
     const bool last_ragged = ((mend - mbeg) % BK3) != 0 || mend > g.M;
     const int n_fast = nk - 2 - (last_ragged ? 1 : 0);          // steps kt with kt + 1 and kt + 2 full and inside the chunk
@@ -1187,10 +1155,8 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
       // (16 sg is wave-uniform: waves 0-1 stage rows 0..15 of a step, waves 2-3 rows 16..31)
       const int sgu = __builtin_amdgcn_readfirstlane(sg);
       const unsigned ca = (unsigned)min(i0 + sc, q.lda1 - 1), cbb = (unsigned)min(j0 + sc, q.ldb1 - 1);
-#if NUDF_TN3_BUFLOAD
       // BUFFER loads: address = descriptor base (the chunk's first row) + a 32-bit lane offset (the column) + a scalar offset (the
-      // row): `buffer_load_dword v, v_col, s[rsrc], s_row offen` -- no vector address arithmetic at all.  (The flat form of the
-      // same loop, `(base + r * ld)[col]`, compiled to a chain of 30 v_lshl_add_u64 and 64-bit per-lane addresses.)
+      // row)
       const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.A1 + (size_t)mbeg * lda), 0,
                                                                            (int)((size_t)(g.M - mbeg) * lda * 4), 0x00020000);
       const __amdgpu_buffer_rsrc_t rsb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.B1 + (size_t)mbeg * ldb), 0,
@@ -1203,58 +1169,10 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
         for (int r = 0; r < 16; ++r)
           st[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(col * 4), so + r * ld4, 0));
       };
-#define TN3_LOAD_A(st) load_f(rsa, ba, lda4, ca, st)
-#define TN3_LOAD_B(st) load_f(rsb, bb, ldb4, cbb, st)
-#else
-      auto load_f = [&](const float* __restrict__ base, size_t ld, unsigned col, float (&st)[16]) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[r] = (base + (size_t)r * ld)[col];     // scalar row base + one 32-bit lane offset
-      };
-#define TN3_LOAD_A(st) load_f(ba, lda, ca, st)
-#define TN3_LOAD_B(st) load_f(bb, ldb, cbb, st)
-#endif
-      auto store_f = [&](const float (&st)[16], unsigned* tile, bool bias) {
-        u32x4 hq[2], mq[2], lq[2];
-        float ps[8];
-#pragma unroll
-        for (int pp = 0; pp < 8; ++pp) {
-          unsigned a, b, d;
-          tn_split3_pair(st[2 * pp], st[2 * pp + 1], a, b, d);
-          hq[pp >> 2][pp & 3] = a; mq[pp >> 2][pp & 3] = b; lq[pp >> 2][pp & 3] = d;
-          ps[pp] = st[2 * pp] + st[2 * pp + 1];
-        }
-        if (bias) bias_acc += ((ps[0] + ps[1]) + (ps[2] + ps[3])) + ((ps[4] + ps[5]) + (ps[6] + ps[7]));
-        unsigned* dst = tile + ((2 * sg) * 128 + sc) * 4;
-        *reinterpret_cast<u32x4*>(dst) = hq[0];
-        *reinterpret_cast<u32x4*>(dst + 512) = hq[1];
-        *reinterpret_cast<u32x4*>(dst + T3Q) = mq[0];
-        *reinterpret_cast<u32x4*>(dst + T3Q + 512) = mq[1];
-        *reinterpret_cast<u32x4*>(dst + 2 * T3Q) = lq[0];
-        *reinterpret_cast<u32x4*>(dst + 2 * T3Q + 512) = lq[1];
-      };
-      // uniform bases of the rows of step kt + 2 (scalar registers; the readfirstlane only tells the compiler so)
-#if !NUDF_TN3_BUFLOAD
-      const float* ba = q.A1 + (size_t)(mbeg + 2 * BK3 + 16 * sgu) * lda;
-      const float* bb = q.B1 + (size_t)(mbeg + 2 * BK3 + 16 * sgu) * ldb;
-      const size_t sa_step = (size_t)BK3 * lda, sb_step = (size_t)BK3 * ldb;
-#endif
-      auto fstep = [&](float (&la)[16], float (&lb)[16], float (&ua)[16], float (&ub)[16]) {
-        TN3_LOAD_A(la);
-        TN3_LOAD_B(lb);
-        ba += sa_step;
-        bb += sb_step;
-        __builtin_amdgcn_sched_barrier(0);
-        mma();
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();
-        store_f(ua, As, do_bias);
-        store_f(ub, Bs, false);
-        __syncthreads();
-      };
-      // PIPELINED form (build switch NUDF_TN3_PIPE, scripts/build_variants.sh): the split of step kt + 1 -- pure register arithmetic -- is
-      // interleaved with step kt's MFMAs inside the wave (four VALU operations behind every MFMA, pinned with
-      // sched_group_barrier), so that what is left between the two barriers is twelve LDS stores: the stretch in which this
-      // workgroup cannot issue an MFMA shrinks from the whole split to the stores.  Same values, same order: bit-identical.
+      // PIPELINED step: the split of step kt + 1 -- pure register arithmetic -- is interleaved with step kt's MFMAs inside the
+      // wave (four VALU operations behind every MFMA, pinned with sched_group_barrier), so that what is left between the two
+      // barriers is twelve LDS stores: the stretch in which this workgroup cannot issue an MFMA shrinks from the whole split to
+      // the stores.  Same values, same order as the generic steps: bit-identical.
       auto store_r = [&](const u32x4 (&pl)[3][2], unsigned* tile) {
         unsigned* dst = tile + ((2 * sg) * 128 + sc) * 4;
 #pragma unroll
@@ -1265,23 +1183,14 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
       };
       const unsigned* fas = As + ((lane >> 5) * 128 + (wave >> 1) * 64 + (lane & 31)) * 4;
       const unsigned* fbs = Bs + ((lane >> 5) * 128 + (wave & 1) * 64 + (lane & 31)) * 4;
-#if NUDF_TN3_STAMPS
-#define TN3_STAMP(acc_) { const long long n_ = (long long)__builtin_amdgcn_s_memtime(); acc_ += n_ - tk_last; tk_last = n_; }
-#else
-#define TN3_STAMP(acc_)
-#endif
       auto pstep = [&](float (&la)[16], float (&lb)[16], float (&ua)[16], float (&ub)[16]) {
-#if NUDF_TN3_STAMPS
-        long long tk_last = (long long)__builtin_amdgcn_s_memtime();
-#endif
-#if !NUDF_TN3_LDSPREAD
-        TN3_LOAD_A(la);
-        TN3_LOAD_B(lb);
+        // the 32 row requests of step kt + 2 in one burst at the top (spread over the twelve MFMA groups below they measured 8 %
+        // slower: the requests are throttled by the memory path wherever they are issued)
+        load_f(rsa, ba, lda4, ca, la);
+        load_f(rsb, bb, ldb4, cbb, lb);
         ba += sa_step;
         bb += sb_step;
         __builtin_amdgcn_sched_barrier(0);
-#endif
-        TN3_STAMP(tk_load)
         // 12 groups of 4 MFMAs (2 groups of 16 rows x 6 plane pairs); behind each of the first eight, the split of TWO row
         // pairs of the next step (22 VALU operations + the bias partial), pinned in source order by sched_barrier: a wave
         // issues its four MFMAs (4 x 32 pipe cycles) and splits while they execute
@@ -1327,59 +1236,25 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
                 }
               }
             }
-#if NUDF_TN3_LDSPREAD && !NUDF_TN3_BUFLOAD
-            // the 32 row requests of step kt + 2, spread over the twelve groups as well (3 3 3 3 3 3 3 3 2 2 2 2, in the order
-            // the next step's split consumes them): issued in one burst at the top of the step they held the wave for ~1 800
-            // cycles per step before its first MFMA (8 waves x 32 requests x 256 B against a 64 B / clk vector cache path)
-            if (c < 8) {
-              la[2 * c] = (ba + (size_t)(2 * c) * lda)[ca];
-              la[2 * c + 1] = (ba + (size_t)(2 * c + 1) * lda)[ca];
-              lb[c] = (bb + (size_t)c * ldb)[cbb];
-            } else {
-              lb[2 * c - 8] = (bb + (size_t)(2 * c - 8) * ldb)[cbb];
-              lb[2 * c - 7] = (bb + (size_t)(2 * c - 7) * ldb)[cbb];
-            }
-#endif
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-#if NUDF_TN3_LDSPREAD
-        ba += sa_step;
-        bb += sb_step;
-#endif
         // (a select, not a branch; the same tree and running sum as store_f)
         const float bsum = ((ps[0] + ps[1]) + (ps[2] + ps[3])) + ((ps[4] + ps[5]) + (ps[6] + ps[7]));
         bias_acc = do_bias ? bias_acc + bsum : bias_acc;
         __builtin_amdgcn_sched_barrier(0);
-        TN3_STAMP(tk_mma)
         __syncthreads();
-        TN3_STAMP(tk_bar1)
         store_r(pa3, As);
         store_r(pb3, Bs);
-        TN3_STAMP(tk_store)
         __syncthreads();
-        TN3_STAMP(tk_bar2)
       };
-#undef TN3_STAMP
-#undef TN3_LOAD_A
-#undef TN3_LOAD_B
-      // (n_fast >= 2 here: a do-while keeps the two steps of an iteration in straight-line code -- with a for loop and both
-      // forms selectable at run time hipcc rotated the loop BETWEEN a step's MFMAs and its split, i.e. put them in different
-      // basic blocks, where nothing can be interleaved)
-#if NUDF_TN3_PIPE
+      // (n_fast >= 2 here: a do-while keeps the two steps of an iteration in straight-line code -- with a for loop hipcc rotated
+      // the loop BETWEEN a step's MFMAs and its split, i.e. put them in different basic blocks, where nothing can be interleaved)
       do {
         pstep(sa, sb, sa2, sb2);
         pstep(sa2, sb2, sa, sb);
         kt0 += 2;
       } while (kt0 + 1 < n_fast);
-#else
-      (void)pstep;
-      do {
-        fstep(sa, sb, sa2, sb2);
-        fstep(sa2, sb2, sa, sb);
-        kt0 += 2;
-      } while (kt0 + 1 < n_fast);
-#endif
     }
   }
   for (int kt = kt0; kt < nk; kt += 2) {
@@ -1387,20 +1262,11 @@ __global__ __launch_bounds__(256, NUDF_TN3_WGS) void gemm_tn3_group_kernel(TnPla
     if (kt + 1 < nk) kstep(kt + 1, sa2, sb2, sa, sb);
   }
 
-#if NUDF_TN3_STAMPS
-  if (g.dbg && lane == 0 && (wave == 0 || wave == 3)) {
-    long long* d = g.dbg + 16 * (size_t)blockIdx.x + (wave ? 8 : 0);
-    d[0] = t_begin; d[1] = (long long)wall_clock64();
-    d[2] = nk | ((long long)kt0 << 20) | (((long long)__builtin_amdgcn_s_memtime() - c_begin) << 40);
-    d[3] = tk_load; d[4] = tk_mma; d[5] = tk_bar1; d[6] = tk_store; d[7] = tk_bar2;
-  }
-#else
   if (g.dbg && tid == 0) {
     long long* d = g.dbg + 4 * (size_t)blockIdx.x;
     d[0] = t_begin; d[1] = (long long)wall_clock64(); d[2] = 2 * 16 + 4;
     d[3] = nk | (((long long)__builtin_amdgcn_s_memtime() - c_begin) << 16);
   }
-#endif
   if (g.flags & TNF_NO_EPILOGUE) return;
   float* slot = g.ws ? g.ws + (size_t)slot_id * TN_WS_TILE : nullptr;
   if (do_bias) {   // the loop's last barrier has passed: the operand image is free
@@ -1472,18 +1338,12 @@ __device__ __forceinline__ void tn_scale_of(const float* amax, float& sc, float&
   inv = __builtin_bit_cast(float, (unsigned)(254 - se) << 23);
 }
 
-#ifndef NUDF_TN2_DB
-#define NUDF_TN2_DB 0      // A/B build switch, see the kernel's shared-memory comment (measured: no gain for the step)
-#endif
 __global__ __launch_bounds__(256, 2) void gemm_tn2_group_kernel(TnPlan g) {
   // image: [operand 2][plane 2][k-pair group 4][column 128][4 dwords], as gemm_tn3_group_kernel's with two planes
-  // NUDF_TN2_DB=1 (A/B build, not the default): TWO images (64 KB, still two workgroups per CU) -- step kt's MFMAs read image
-  // kt & 1 while step kt + 1 is split into the other one, so a k-step has ONE barrier and a wave's split / LDS stores run beside
-  // the other waves' MFMAs; same arithmetic, bit-identical results, 250 VGPRs.  MEASURED (profiles/r06_tn2_double_buffer_ab.txt):
-  // the kernel alone 5-10 % faster (331 / 319 / 200 vs 346-355 / 316 / 201 us), the train step SLOWER (3.56-3.57 vs 3.52 ms): the
-  // card answers the denser kernel with a lower clock for the whole replayed step (2 008 vs 2 110 MHz at 1 276 vs 1 310 W).
-  __shared__ __attribute__((aligned(16))) unsigned smem[(NUDF_TN2_DB ? 8 : 4) * T3Q];
-  constexpr int IMG = NUDF_TN2_DB ? 4 * T3Q : 0;      // dwords from one image to the other
+  // (TWO images, 64 KB -- step kt's MFMAs read one while step kt + 1 is split into the other, one barrier per k-step -- made the
+  // kernel alone 5-10 % faster and the train step SLOWER, 3.56-3.57 vs 3.52 ms: the card answers the denser kernel with a lower
+  // clock for the whole replayed step.  profiles/r06_tn2_double_buffer_ab.txt)
+  __shared__ __attribute__((aligned(16))) unsigned smem[4 * T3Q];
   unsigned* As = smem;
   unsigned* Bs = smem + 2 * T3Q;
 
@@ -1545,9 +1405,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn2_group_kernel(TnPlan g) {
     *reinterpret_cast<u32x4*>(dst + T3Q + 512) = lq[1];
   };
   // one k-step: 2 groups of 16 rows; per group 2 + 2 operand sub-tiles x 2 planes (one ds_read_b128 each) and 12 MFMAs
-  auto mma = [&](int img) {
-    const unsigned* as = As + img + ((lane >> 5) * 128 + (wave >> 1) * 64 + (lane & 31)) * 4;
-    const unsigned* bs = Bs + img + ((lane >> 5) * 128 + (wave & 1) * 64 + (lane & 31)) * 4;
+  auto mma = [&]() {
+    const unsigned* as = As + ((lane >> 5) * 128 + (wave >> 1) * 64 + (lane & 31)) * 4;
+    const unsigned* bs = Bs + ((lane >> 5) * 128 + (wave & 1) * 64 + (lane & 31)) * 4;
 #pragma unroll
     for (int kk = 0; kk < BK3 / 16; ++kk) {
       u32x4 a[2][2], b[2][2];
@@ -1595,24 +1455,14 @@ __global__ __launch_bounds__(256, 2) void gemm_tn2_group_kernel(TnPlan g) {
       load(pb, ldb, lb, kt + 2);
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the global loads above the MFMA block
-    if (NUDF_TN2_DB) {
-      const int nxt = ((kt + 1) & 1) * IMG;
-      if (kt + 1 < nk) {                 // (the other image: every wave left it at the previous step's barrier)
-        store(Ragged{}, ua, kt + 1, As + nxt, sca, do_bias);
-        store(Ragged{}, ub, kt + 1, Bs + nxt, scb, false);
-      }
-      mma((kt & 1) * IMG);
-      __syncthreads();
-    } else {
-      mma(0);
-      __builtin_amdgcn_sched_barrier(0);
-      __syncthreads();                     // every wave is done reading the image
-      if (kt + 1 < nk) {
-        store(Ragged{}, ua, kt + 1, As, sca, do_bias);
-        store(Ragged{}, ub, kt + 1, Bs, scb, false);
-      }
-      __syncthreads();
+    mma();
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();                     // every wave is done reading the image
+    if (kt + 1 < nk) {
+      store(Ragged{}, ua, kt + 1, As, sca, do_bias);
+      store(Ragged{}, ub, kt + 1, Bs, scb, false);
     }
+    __syncthreads();
   };
   // steady state: FULL k-steps, buffer loads with a scalar row offset (gemm_tn3_group_kernel's loop-invariant addressing)
   int kt0 = 0;
@@ -1634,30 +1484,22 @@ __global__ __launch_bounds__(256, 2) void gemm_tn2_group_kernel(TnPlan g) {
         for (int r = 0; r < 16; ++r)
           st[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(col * 4), so + r * ld4, 0));
       };
-      auto fstep = [&](auto CURc, float (&la)[16], float (&lb)[16], float (&ua)[16], float (&ub)[16]) {
-        constexpr int cur = decltype(CURc)::value * IMG, nxt = IMG - cur;       // the loop runs an even number of steps from kt0 = 0
+      auto fstep = [&](float (&la)[16], float (&lb)[16], float (&ua)[16], float (&ub)[16]) {
         load_f(rsa, ba, lda4, ca, la);
         load_f(rsb, bb, ldb4, cbb, lb);
         ba += sa_step;
         bb += sb_step;
         __builtin_amdgcn_sched_barrier(0);
-        if (NUDF_TN2_DB) {
-          store(Full{}, ua, 0, As + nxt, sca, do_bias);
-          store(Full{}, ub, 0, Bs + nxt, scb, false);
-          mma(cur);
-          __syncthreads();
-        } else {
-          mma(0);
-          __builtin_amdgcn_sched_barrier(0);
-          __syncthreads();
-          store(Full{}, ua, 0, As, sca, do_bias);
-          store(Full{}, ub, 0, Bs, scb, false);
-          __syncthreads();
-        }
+        mma();
+        __builtin_amdgcn_sched_barrier(0);
+        __syncthreads();
+        store(Full{}, ua, 0, As, sca, do_bias);
+        store(Full{}, ub, 0, Bs, scb, false);
+        __syncthreads();
       };
       do {
-        fstep(std::integral_constant<int, 0>{}, sa, sb, sa2, sb2);
-        fstep(std::integral_constant<int, 1>{}, sa2, sb2, sa, sb);
+        fstep(sa, sb, sa2, sb2);
+        fstep(sa2, sb2, sa, sb);
         kt0 += 2;
       } while (kt0 + 1 < n_fast);
     }
@@ -1966,7 +1808,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn3w_group_kernel(TnPlan g) {
 static int g_tn_flags = -1;   // NUDF_TN_FLAGS / nudf_set_tn_flags
 extern "C" int nudf_set_tn_flags(int f) {
   const int old = g_tn_flags < 0 ? 0 : g_tn_flags;
-  g_tn_flags = f;
+  g_tn_flags = f & ~TNF_RETIRED;
   return old;
 }
 static long long* g_tn_dbg = nullptr;
@@ -1975,7 +1817,7 @@ extern "C" int nudf_set_tn_debug(void* buf) {   // device buffer of >= 4 int64 p
   return 0;
 }
 static int tn_flags() {
-  if (g_tn_flags < 0) { const char* e = getenv("NUDF_TN_FLAGS"); g_tn_flags = e ? atoi(e) : 0; }
+  if (g_tn_flags < 0) { const char* e = getenv("NUDF_TN_FLAGS"); g_tn_flags = (e ? atoi(e) : 0) & ~TNF_RETIRED; }
   return g_tn_flags;
 }
 
@@ -2256,7 +2098,7 @@ extern "C" int nudf_gemm_tn_grouped(const NudfGemmTNGroup* args, void* stream) {
   pl.ws = (pl.flags & TNF_ATOMICS) ? nullptr : args->workspace;
   pl.dbg = g_tn_dbg;
   pl.assign = args->assign ? 1 : 0;
-  if (pl.assign && (!pl.ws || (pl.flags & TNF_NO_EPILOGUE))) {
+  if (pl.assign && !pl.ws) {
     nudf_set_error("nudf_gemm_tn_grouped: assign needs the workspace (two-pass) path", hipErrorInvalidValue);
     return (int)hipErrorInvalidValue;
   }
@@ -2300,7 +2142,7 @@ extern "C" int nudf_gemm_tn_grouped(const NudfGemmTNGroup* args, void* stream) {
     pl.amax_b = args->amax_b;
     hipLaunchKernelGGL(gemm_tn2_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
     NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped");
-    if (pl.ws && !(pl.flags & TNF_NO_EPILOGUE)) {
+    if (pl.ws) {
       hipLaunchKernelGGL(tn_reduce_kernel, dim3(pl.n_tiles * 17), dim3(256), 0, (hipStream_t)stream, pl);
       NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped (reduce)");
     }
@@ -2315,7 +2157,7 @@ extern "C" int nudf_gemm_tn_grouped(const NudfGemmTNGroup* args, void* stream) {
   else if (packed16) hipLaunchKernelGGL(gemm_tn16_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
   else hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
   NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped");
-  if (pl.ws && !(pl.flags & TNF_NO_EPILOGUE)) {
+  if (pl.ws) {
     hipLaunchKernelGGL(tn_reduce_kernel, dim3(pl.n_tiles * 17), dim3(256), 0, (hipStream_t)stream, pl);
     NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped (reduce)");
   }

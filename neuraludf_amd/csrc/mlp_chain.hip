@@ -147,27 +147,12 @@ __device__ __forceinline__ void ch_mma(const float* __restrict__ arow, const f32
 // activation tile converted on the fly (v_cvt_pk_*_f32, round-to-nearest-even) and one 16-byte read of the
 // pre-converted weight fragments per 32-column tile.  16x the fp32 MFMA rate and a separate matrix pipe: the
 // sweep becomes epilogue / LDS bound.
-#ifndef NUDF_STAGGER16
-#define NUDF_STAGGER16 0u    // s_sleep(127) units the odd wave slots of the 16-bit instantiation start late (A/B switch;
-#endif                       // measured 0..4 at the config-5 shape: 7.53 / 7.68 / 7.77 / 7.87 / 7.98 ms -- pure delay there)
-#ifndef NUDF_STAGGER32
-#define NUDF_STAGGER32 2u    // the same for the fp32 instantiation's 64-point tiles (0 also switches the 32-point tiles' stagger off)
-#endif
-#ifndef NUDF_MMA16_REPEAT
-#define NUDF_MMA16_REPEAT 1  // timing probe: every 16-bit MFMA issued this many times (what a split-operand fp32 emulation costs)
-#endif
-#ifndef NUDF_MMA16_RING
-#define NUDF_MMA16_RING 1    // A/B build switch (scripts/build_variants.sh): 0 = one k step of weight fragments in flight
-#endif
 template <int NRT, int NCT, bool BF>
 __device__ __forceinline__ void ch_mma16(const float* __restrict__ arow, const uint4* __restrict__ bptr, size_t bstride,
                                          int G16, f32x16 (&acc)[2][2]) {
   // (requesting the epilogue's stored-state operands under this loop, as the fp32 loop does, was measured in round 2:
   // 64 more live registers next to the conversions -> 185-511 spilled registers, chains 7.2 -> 17.8 ms at config 5)
   f32x4 a0[NRT][2], a1[NRT][2];
-#if !NUDF_MMA16_RING
-  uint4 b0[NCT], b1[NCT];
-#endif
   auto lda = [&](f32x4 (&a)[NRT][2], int g) {
 #pragma unroll
     for (int i = 0; i < NRT; ++i) {
@@ -182,8 +167,6 @@ __device__ __forceinline__ void ch_mma16(const float* __restrict__ arow, const u
   };
   auto mma = [&](f32x4 (&a)[NRT][2], uint4 (&b)[NCT]) {
 #pragma unroll
-    for (int rep = 0; rep < NUDF_MMA16_REPEAT; ++rep)     // > 1: timing probes only (results are garbage)
-#pragma unroll
     for (int i = 0; i < NRT; ++i) {
       const f32x8 av = {a[i][0][0], a[i][0][1], a[i][0][2], a[i][0][3], a[i][1][0], a[i][1][1], a[i][1][2], a[i][1][3]};
 #pragma unroll
@@ -197,7 +180,6 @@ __device__ __forceinline__ void ch_mma16(const float* __restrict__ arow, const u
       }
     }
   };
-#if NUDF_MMA16_RING
   // Weight fragments come from L2 (~600-800 cycles) and a 16-wide k step is only 4 MFMAs = 128 matrix cycles per wave:
   // with the fragments of ONE step in flight (the fp32 loop's depth, where a step is 1024 cycles) two waves per SIMD keep
   // the pipe at ~50 % (scripts/chain_timeline.py, 16-bit mode).  Ring of 4 fragment sets = three k steps in flight; the
@@ -244,26 +226,6 @@ __device__ __forceinline__ void ch_mma16(const float* __restrict__ arow, const u
       if (rem > 2) mma(a0, br[2]);
     }
   }
-#else
-  lda(a0, 0);
-  ldb(b0, 0);
-  int g = 0;
-#pragma unroll 1
-  for (; g + 1 < G16; g += 2) {
-    lda(a1, g + 1);
-    ldb(b1, g + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(a0, b0);
-    __builtin_amdgcn_sched_barrier(0);
-    const int gn = (g + 2 < G16) ? g + 2 : g + 1;
-    lda(a0, gn);
-    ldb(b0, gn);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(a1, b1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if (g < G16) mma(a0, b0);   // odd number of 16-wide k steps
-#endif
 }
 
 // 16-bit-TILE K loop (MODE 3): the LDS tile already holds the operand type, row-major [row][CH_LD16] halfwords -- lane (i, h)
@@ -375,17 +337,6 @@ __device__ __forceinline__ void ch_split3(const f32x4& lo4, const f32x4& hi4, bf
   p1 = __builtin_bit_cast(bf16x8, b);
   p2 = __builtin_bit_cast(bf16x8, c);
 }
-#ifndef NUDF_X3_BDIST
-#define NUDF_X3_BDIST 1     // A/B build switch: k steps the weight fragments are requested ahead.  2 (three register sets, one
-                            // set of split activations; 5 spilled registers in the 64-point tile) measured the same as 1:
-                            // the fetch is not latency-bound (profiles/r04_bf16x3_experiments.txt item 9)
-#endif
-#ifndef NUDF_X3_PIPE
-#define NUDF_X3_PIPE 2      // the next step's split interleaved with this step's MFMAs (sched_group_barrier pattern): 0 = never,
-                            // 1 = always (measured slower on the 64-point tiles: 4.63 vs 4.44 ms per step -- two in-phase waves
-                            // per SIMD already cover each other's split), 2 = only where a wave has its SIMD to itself: the
-                            // 32-point tiles of the 8 192-point launches (81-85 -> 70-75 us per launch, experiments item 10)
-#endif
 template <int NRT, int NCT, bool PIPE>
 __device__ __forceinline__ void ch_mma16x3(const float* __restrict__ arow, const uint4* __restrict__ bptr, size_t bstride3,
                                            int G16, f32x16 (&acc)[2][2]) {
@@ -406,9 +357,6 @@ __device__ __forceinline__ void ch_mma16x3(const float* __restrict__ arow, const
     }
   };
   auto ldb = [&](uint4 (&bb)[NCT][3], int g) {
-#ifdef NUDF_X3_PROBE_B0      // timing probe only (wrong results): every k step re-reads step 0's fragments -- L1 hits
-    g = 0;
-#endif
     const uint4* bq = bptr + (size_t)g * bstride3;
 #pragma unroll
     for (int j = 0; j < NCT; ++j)
@@ -444,43 +392,8 @@ __device__ __forceinline__ void ch_mma16x3(const float* __restrict__ arow, const
     }
   };
   const int gl = G16 - 1;
-#if NUDF_X3_BDIST == 2
-  // Weight fragments requested TWO k steps ahead (three register sets in rotation), one set of split activations: the
-  // split of step g + 1 runs after step g's MFMAs have been issued and have read their operands, so it may overwrite them.
-  // (Built because a probe with every k step re-reading step 0's fragments -- L1 hits, NUDF_X3_PROBE_B0 -- runs every chain
-  // launch 12-17 % faster; the distance turned out not to be the reason.)
-  {
-    uint4 b3[3][NCT][3];
-    lda(0);
-    ldb(b3[0], 0);
-    ldb(b3[1], min(1, gl));
-    split(pa[0]);
-    int g3 = 0;
-#define CH_X3_STEP(cur, nxt2, gg)                                   \
-    __builtin_amdgcn_sched_barrier(0);                              \
-    lda(min((gg) + 1, gl));                                         \
-    ldb(b3[nxt2], min((gg) + 2, gl));                               \
-    __builtin_amdgcn_sched_barrier(0);                              \
-    mfmas(pa[0], b3[cur]);                                          \
-    split(pa[0]);
-#pragma unroll 1
-    for (; g3 + 3 <= G16; g3 += 3) {
-      CH_X3_STEP(0, 2, g3)
-      CH_X3_STEP(1, 0, g3 + 1)
-      CH_X3_STEP(2, 1, g3 + 2)
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (g3 + 2 <= G16) {          // two steps left: sets 0 and 1 hold them
-      CH_X3_STEP(0, 2, g3)
-      __builtin_amdgcn_sched_barrier(0);
-      mfmas(pa[0], b3[1]);
-    } else if (g3 < G16) {
-      mfmas(pa[0], b3[0]);
-    }
-#undef CH_X3_STEP
-    return;
-  }
-#endif
+  // (Weight fragments requested TWO k steps ahead, three register sets in rotation, measured the same as one step: the fetch
+  // is not latency-bound, profiles/r04_bf16x3_experiments.txt item 9.)
   lda(0);
   ldb(b[0], 0);
   split(pa[0]);
@@ -560,9 +473,6 @@ __device__ __forceinline__ void ch_mma16x2(const float* __restrict__ arow, const
     }
   };
   auto ldb = [&](uint4 (&bb)[NCT][2], int g) {
-#ifdef NUDF_X2_PROBE_B0      // timing probe only (wrong results): every k step re-reads step 0's fragments -- L1 hits
-    g = 0;
-#endif
     const uint4* bq = bptr + (size_t)g * bstride2;
 #pragma unroll
     for (int j = 0; j < NCT; ++j)
@@ -570,19 +480,8 @@ __device__ __forceinline__ void ch_mma16x2(const float* __restrict__ arow, const
       for (int pl = 0; pl < 2; ++pl) bb[j][pl] = bq[j * 128 + pl * 64];
   };
   auto split = [&](f16x8 (&q)[NRT][2]) {
-#ifdef NUDF_X2_PROBE_NOSPLIT     // timing probe only (wrong results): the operands are the raw LDS words -- what a K loop costs
-#pragma unroll                   // whose tile already holds the two fp16 parts (the split done once, by the producing epilogue)
-    for (int i = 0; i < NRT; ++i) {
-      uint4 u0 = __builtin_bit_cast(uint4, raw[i][0]), u1 = __builtin_bit_cast(uint4, raw[i][1]);
-      u0.x &= 0x33ff33ffu; u0.y &= 0x33ff33ffu; u0.z &= 0x33ff33ffu; u0.w &= 0x33ff33ffu;      // finite, |.| < 0.25
-      u1.x &= 0x33ff33ffu; u1.y &= 0x33ff33ffu; u1.z &= 0x33ff33ffu; u1.w &= 0x33ff33ffu;
-      q[i][0] = __builtin_bit_cast(f16x8, u0);
-      q[i][1] = __builtin_bit_cast(f16x8, u1);
-    }
-#else
 #pragma unroll
     for (int i = 0; i < NRT; ++i) ch_split2(raw[i][0], raw[i][1], q[i][0], q[i][1]);
-#endif
   };
   auto mfmas = [&](const f16x8 (&q)[NRT][2], const uint4 (&bb)[NCT][2]) {
     // the two correction products first (their accumulator), then hi hi'
@@ -610,10 +509,8 @@ __device__ __forceinline__ void ch_mma16x2(const float* __restrict__ arow, const
     }
   };
   const int gl = G16 - 1;
-  // (Weight fragments TWO k steps ahead -- a k step is 384 matrix cycles per wave against 600-800 of L2 latency, and a probe
-  // that re-reads step 0's fragments, NUDF_X2_PROBE_B0, runs the f16x2 sweeps 7-12 % faster -- was built as a ring of three
-  // fragment sets: 208 live registers next to the two accumulator sets, and hipcc spilled 397 of them.  Not kept.)
-  {
+  // (Weight fragments TWO k steps ahead, a ring of three fragment sets, was tried because a k step is 384 matrix cycles per
+  // wave against 600-800 of L2 latency: 208 live registers next to the two accumulator sets, hipcc spilled 397.  Not kept.)
   lda(0);
   ldb(b[0], 0);
   split(pa[0]);
@@ -637,7 +534,6 @@ __device__ __forceinline__ void ch_mma16x2(const float* __restrict__ arow, const
   }
   __builtin_amdgcn_sched_barrier(0);
   if (g < G16) mfmas(pa[0], b[0]);   // odd number of 16-wide k steps
-  }
 #pragma unroll
   for (int i = 0; i < NRT; ++i)
 #pragma unroll
@@ -839,16 +735,6 @@ __device__ __forceinline__ float ch_epilogue_tile(const NudfChainStep& st, float
     sacc += __shfl_xor(sacc, 32);
     if (h == 0 && col < st.iparam && col < 4) st.row_sums[(size_t)(grow0 >> 5) * 4 + col] = sacc;
   }
-#ifdef NUDF_X3_PROBE_NOSTORE   // timing probe (wrong results downstream): the stored-state arrays are not written
-  if (EPI == NUDF_CH_SOFTPLUS || EPI == NUDF_CH_MULSP || EPI == NUDF_CH_TANGENT || EPI == NUDF_CH_BWD) {
-    if (st.act_write) {
-      float* ap = act + r0 * CH_LD + st.act_col0 + col;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ap[CH_KOFF(r) * CH_LD] = col_ok ? out[r] : 0.0f;
-    }
-    return tmax;
-  }
-#endif
   // ---- stores ----
   if (EPI == NUDF_CH_UDFHEAD) {
     if (col == 0) {
@@ -972,9 +858,6 @@ __device__ __forceinline__ void ch_epilogue_seq(const NudfChainStep& st, float* 
 // at config 5's shape the tangent sweep (two operands in, two arrays out) took 1.95 ms against 1.13 ms for the adjoint.
 // Raw 16-bit values wait in registers and are widened at use.  The registers come from the X1 prefetch of the fp32 K
 // loop, which the 16-bit instantiation does not use at all (see mlp_chain_kernel).
-#ifndef NUDF_SEQ16
-#define NUDF_SEQ16 1     // A/B build switch (scripts/build_variants.sh): 0 = per-tile loop for the 16-bit stored state
-#endif
 template <int EPI, int NRT, int NCT, bool T16 = false, bool X3 = false>
 __device__ __forceinline__ void ch_epilogue_seq16(const NudfChainStep& st, float* act, int m0, int rt0, int ct0, int h,
                                                   int ln, f32x16 (&acc)[2][2], const float (&bpre)[2], bool tile_bf = false) {
@@ -1024,9 +907,6 @@ __device__ __forceinline__ void ch_epilogue_seq16(const NudfChainStep& st, float
   }
 }
 
-#ifndef NUDF_X3_EPI_AHEAD
-#define NUDF_X3_EPI_AHEAD 2  // A/B build switch: tiles the epilogue's stored operands are requested ahead (1 = as the fp32 kernels)
-#endif
 // bf16x3 mode (fp32 stored state, no operand prefetch under the K loop: the split needs those registers): BOTH stored
 // operands of tile t + 1 are requested before tile t is computed and stored, as in ch_epilogue_seq16.
 template <int EPI, int NRT, int NCT, bool X3 = false>
@@ -1035,24 +915,14 @@ __device__ __forceinline__ float ch_epilogue_seq32(const NudfChainStep& st, floa
                                                   float tinv = 1.0f) {
   float smax = 0.0f;
   constexpr bool U1 = CH_USES_X1(EPI), U2 = CH_USES_X2(EPI), U3 = (EPI == NUDF_CH_BWD) && X3;
-  // (three stored operands: one tile ahead -- the same 96 registers as two operands two tiles ahead)
-  constexpr int AHEAD = U3 ? 1 : NUDF_X3_EPI_AHEAD;
+  // tiles the stored operands are requested ahead: two (the fp32 kernels: one); with three stored operands one -- the same
+  // 96 registers as two operands two tiles ahead
+  constexpr int AHEAD = U3 ? 1 : 2;
   float xa[AHEAD + 1][16], xb[AHEAD + 1][16], xc[U3 ? AHEAD + 1 : 1][16];
   auto issue = [&](float (&a1)[16], float (&a2)[16], float (&a3)[16], int i, int j) {
     const int col = (ct0 + j) * 32 + ln;
     const unsigned colc = (unsigned)((col < st.N) ? col : 0);
     const unsigned row0 = (unsigned)(m0 + (rt0 + i) * 32 + 4 * h);
-#ifdef NUDF_X3_PROBE_NOX      // timing probe (wrong results): the epilogues' stored operands cost nothing -- the upper bound
-    if (U1) {                 // of what an LDS-DMA prefetch of them under the K loop could buy
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a1[r] = 0.01f * (float)(row0 & 7);
-    }
-    if (U2) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a2[r] = 0.5f;
-    }
-    return;
-#endif
     if (U1) {
       const unsigned vo = row0 * (unsigned)st.ldx1 + colc;
 #pragma unroll
@@ -1205,7 +1075,7 @@ __device__ __forceinline__ float ch_epilogue(const NudfChain& p, const NudfChain
     }
   }
   if constexpr (ANY16 && (EPI == NUDF_CH_MULSP || EPI == NUDF_CH_TANGENT || EPI == NUDF_CH_BWD)) {
-    if (NUDF_SEQ16 && (st.layout & NUDF_CH_STATE16) && nrt == 2) {
+    if ((st.layout & NUDF_CH_STATE16) && nrt == 2) {
       if constexpr (EPI == NUDF_CH_BWD && MODE != 3) {     // (the dispatcher sends three-operand chains to MODE 4)
         if (st.X3) {
           if (nct == 2) ch_epilogue_seq16<EPI, 2, 2, T16, true>(st, act, m0, rt0, ct0, h, ln, acc, bpre, tile_bf);
@@ -1294,14 +1164,9 @@ __device__ __forceinline__ float ch_epilogue(const NudfChain& p, const NudfChain
 // MODE 4: the same 16-bit-tile kernel register-allocated for TWO workgroups per CU (201 VGPRs, no spills): the TANGENT
 // sweeps -- two stored operands in, two arrays out per tile, 176 live registers in the epilogue -- spill 54 registers at the
 // 168 of three workgroups and run 1115 instead of 872 us at config 5's shape; every other sweep is faster with three.
-#ifndef NUDF_T16_WGS
-#define NUDF_T16_WGS 3       // A/B build switch: workgroups per CU MODE 3 is register-allocated for
-#endif
-#ifndef NUDF_TS_LOG2
-#define NUDF_TS_LOG2 (-6)    // NudfChain.tile_scale: the tile's largest seed is scaled into [2^NUDF_TS_LOG2, 2 x that)
-#endif
+constexpr int CH_T16_WGS = 3;   // workgroups per CU MODE 3 is register-allocated for (see above)
 template <int TM, int MODE>
-__global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void mlp_chain_kernel(NudfChain p_arg) {
+__global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? CH_T16_WGS : 2) void mlp_chain_kernel(NudfChain p_arg) {
   constexpr bool ANY16 = MODE == 1 || MODE == 3 || MODE == 4, X3 = MODE == 2, T16 = MODE == 3 || MODE == 4;
   // The descriptor is read where it lies, in the kernarg segment: the by-value parameter is otherwise a private copy that
   // the optimiser has to prove away, and once it fails (it did when the 16-bit epilogues grew) all 2 KB go to scratch and
@@ -1341,7 +1206,8 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
   // number, and every element down to 2^-8 of that seed keeps the full 22 bits of the f16x2 split (below: 2^-36 absolute)
   auto set_sigma = [&](float m) {
     const unsigned e = (__builtin_bit_cast(unsigned, m) >> 23) & 0xffu;
-    const int se = 254 + NUDF_TS_LOG2 - (int)e;
+    constexpr int TS_LOG2 = -6;    // NudfChain.tile_scale: the largest seed is scaled into [2^TS_LOG2, 2 x that)
+    const int se = 254 + TS_LOG2 - (int)e;
     if (e != 0u && e != 255u && se >= 1 && se <= 254) {
       tsig = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_readfirstlane(se) << 23);
       tinv = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_readfirstlane(254 - se) << 23);
@@ -1473,23 +1339,15 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
   // that one workgroup's epilogues run under the other's MFMA phases.  Speed only.
   const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);  // HW_REG_HW_ID.wave_id
   if (gridDim.x > 256) {
-    const unsigned k = (ANY16 || X3) ? (slot & 1u) * NUDF_STAGGER16 : ((TM == 64) ? (slot & 1u) * NUDF_STAGGER32 : (slot % 3u) * (NUDF_STAGGER32 ? 1u : 0u));
+    // s_sleep(127) units an odd slot starts late.  16-bit and split-operand instantiations: none (measured 0..4 at the config-5
+    // shape: 7.53 / 7.68 / 7.77 / 7.87 / 7.98 ms -- pure delay there); fp32 64-point tiles: 2; fp32 32-point tiles: slot % 3
+    constexpr unsigned STAGGER16 = 0u, STAGGER32 = 2u;
+    const unsigned k = (ANY16 || X3) ? (slot & 1u) * STAGGER16 : ((TM == 64) ? (slot & 1u) * STAGGER32 : slot % 3u);
     for (unsigned d = 0; d < k; ++d) __builtin_amdgcn_s_sleep(127);
   }
 
-#ifdef NUDF_X3_CU_STAGGER   // experiment (profiles/r05_chain_cu_stagger.txt): de-phase the CUs against each other so that the
-  // epilogue phases (HBM) of one half of the chip fall into the K-loop phases (no HBM traffic) of the other half
-  if (X3 && gridDim.x > 256) {
-    const unsigned hw = __builtin_amdgcn_s_getreg((8 << 11) | (8 << 6) | 4);      // HW_REG_HW_ID bits [15:8]: cu_id, sh_id, se_id
-#if NUDF_X3_CU_STAGGER > 0
-    const unsigned late = hw & 1u;                                                // odd CUs
-    for (int d = 0; d < (int)late * NUDF_X3_CU_STAGGER; ++d) __builtin_amdgcn_s_sleep(127);
-#else
-    const unsigned xcc = __builtin_amdgcn_s_getreg((4 << 11) | (0 << 6) | 20);    // HW_REG_XCC_ID
-    for (int d = 0; d < (int)(xcc & 1u) * (-NUDF_X3_CU_STAGGER); ++d) __builtin_amdgcn_s_sleep(127);
-#endif
-  }
-#endif
+  // (De-phasing the CUs against each other for the bf16x3 sweeps, odd CUs or odd XCCs late, was tried and not kept:
+  // profiles/r05_chain_cu_stagger.txt)
   unsigned long long* dbg = p.dbg ? p.dbg + ((size_t)blockIdx.x * 4 + wave) * 64 : nullptr;
   if (dbg && lane == 0) {
     dbg[0] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4);
@@ -1609,11 +1467,10 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
         const uint4* bp2 = reinterpret_cast<const uint4*>(st.Bp) + (size_t)ct0 * 128 + lane;
         const size_t bstride2 = (size_t)NT * 128;
         const int G16 = st.K >> 4;
-#ifdef NUDF_X2_PIPE64          // A/B: the split interleaved with the MFMAs on the 64-point tiles as well
-        constexpr bool PIPE2 = true;
-#else
-        constexpr bool PIPE2 = (NUDF_X3_PIPE == 1) || (NUDF_X3_PIPE == 2 && TM == 32);
-#endif
+        // the next step's split is interleaved with this step's MFMAs only where a wave has its SIMD to itself, the 32-point
+        // tiles of the 8 192-point launches (81-85 -> 70-75 us per launch); on the 64-point tiles it measured slower (4.63 vs
+        // 4.44 ms per step: two in-phase waves per SIMD already cover each other's split)
+        constexpr bool PIPE2 = TM == 32;
         if (nrt == 2 && nct == 2) ch_mma16x2<2, 2, PIPE2>(arow16, bp2, bstride2, G16, acc);
         else if (nrt == 2) ch_mma16x2<2, 1, PIPE2>(arow16, bp2, bstride2, G16, acc);
         else if (nct == 2) ch_mma16x2<1, 2, PIPE2>(arow16, bp2, bstride2, G16, acc);
@@ -1623,21 +1480,9 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? NUDF_T16_WGS : 2) void ml
         const uint4* bp3 = reinterpret_cast<const uint4*>(st.Bp) + (size_t)ct0 * 192 + lane;
         const size_t bstride3 = (size_t)NT * 192;
         const int G16 = st.K >> 4;
-        constexpr bool PIPE3 = (NUDF_X3_PIPE == 1) || (NUDF_X3_PIPE == 2 && TM == 32);
-#ifdef NUDF_X3_PROBE_COLSPLIT
-        // probe of VERDICT r4's column split (profiles/r05_chain_colsplit_probe.txt): the wave's two column tiles as two
-        // passes over K -- the K-loop shape a half-step of 128 columns would have (each activation split feeds 12 MFMAs
-        // instead of 24), bit-identical results (same k order per output)
-        if (nrt == 2 && nct == 2) {
-          f32x16 t[2][2];
-          t[0][0] = acc[0][0]; t[1][0] = acc[1][0];
-          ch_mma16x3<2, 1, PIPE3>(arow16, bp3, bstride3, G16, t);
-          acc[0][0] = t[0][0]; acc[1][0] = t[1][0];
-          t[0][0] = acc[0][1]; t[1][0] = acc[1][1];
-          ch_mma16x3<2, 1, PIPE3>(arow16, bp3 + 192, bstride3, G16, t);
-          acc[0][1] = t[0][0]; acc[1][1] = t[1][0];
-        } else
-#endif
+        constexpr bool PIPE3 = TM == 32;
+        // (VERDICT r4's column split -- the wave's two column tiles as two passes over K, each activation split feeding 12 MFMAs
+        // instead of 24 -- was probed and not kept: profiles/r05_chain_colsplit_probe.txt)
         if (nrt == 2 && nct == 2) ch_mma16x3<2, 2, PIPE3>(arow16, bp3, bstride3, G16, acc);
         else if (nrt == 2) ch_mma16x3<2, 1, PIPE3>(arow16, bp3, bstride3, G16, acc);
         else if (nct == 2) ch_mma16x3<1, 2, PIPE3>(arow16, bp3, bstride3, G16, acc);

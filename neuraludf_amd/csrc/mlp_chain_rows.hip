@@ -16,27 +16,13 @@
 //    groups of the K loop, those of tile t + 4 as soon as tile t has been consumed; the bias of step s + 1 is staged
 //    through LDS during step s and enters as the accumulators' initial value (bias-first summation: results differ
 //    from the workgroup-shared kernel by the rounding of that one addition);
-//  * the 4 waves of a workgroup read the same weight fragments; re-aligning them with a barrier per step
-//    (CHR_STEP_SYNC) so that three of the four reads hit the CU's vector L1 measured 3 % SLOWER and is off.
+//  * the 4 waves of a workgroup read the same weight fragments; re-aligning them with a barrier per step so that three of
+//    the four reads hit the CU's vector L1 measured 3 % SLOWER and is not done.
 #include "mlp_chain_shared.h"
 #include <stdio.h>
 #include <stdlib.h>
 
-// A/B build switches of the transposed-product shared-tile kernel (scripts/build_variants.sh): alternating wave priority
-// per layer (1, shipping) / none (0) / fixed by wave slot (2); the one-off start-up delay of odd wave slots (1 / 0)
-#ifndef NUDF_TQ_SPREAD
-#define NUDF_TQ_SPREAD 1     // K loop: next group's operand requests spread over the current group's MFMA quarters (A/B: 0)
-#endif
-#ifndef NUDF_TQ_PRIO
-#define NUDF_TQ_PRIO 1
-#endif
-#ifndef NUDF_TQ_SLEEP
-#define NUDF_TQ_SLEEP 1
-#endif
 #define CHR_WAVES 4
-#ifndef CHR_STEP_SYNC
-#define CHR_STEP_SYNC 0      // 1: barrier at the top of every step (L1 sharing of the weight stream): measured -3 %
-#endif
 #define CHR_ROWS 32
 
 struct ChainRowsSmem {
@@ -429,9 +415,6 @@ __global__ __launch_bounds__(CHR_WAVES * 64, 1) void mlp_chain_rows_kernel(NudfC
     cs.scale = chr_pin(st.scale);
     cs.xscale = chr_pin(st.xscale);
 
-#if CHR_STEP_SYNC
-    __builtin_amdgcn_s_barrier();     // speed only (L1 sharing of the weight stream); terminated waves are not counted
-#endif
     f32x16 acc[8];       // initialised inside chr_mma (only the NT tiles that exist) from the staged bias
     const float* bb = sm.bias[wave][si & 1] + 4 * h;
     // next step's bias: requested now, staged into LDS after the K loop
@@ -527,7 +510,6 @@ __device__ __forceinline__ void tq_mma(const float* __restrict__ arow, const f32
   for (int i = 0; i < NRT; ++i) a0[i] = *reinterpret_cast<const f32x4*>(arow + i * 32 * CH_LD);
 #pragma unroll
   for (int j = 0; j < NCT; ++j) b0[j] = bptr[j * 64];
-#if NUDF_TQ_SPREAD
   // the next group's operand requests spread over the four quarters of this group's MFMAs (weights first: the longer
   // latency) instead of all in front of it: the wave's own request burst no longer sits between two MFMA blocks
   auto grp = [&](const f32x4 (&ac)[NRT], const f32x4 (&bc)[NCT], f32x4 (&an)[NRT], f32x4 (&bn)[NCT], int gn)
@@ -552,41 +534,6 @@ __device__ __forceinline__ void tq_mma(const float* __restrict__ arow, const f32
     grp(a0, b0, a1, b1, g + 1);
     grp(a1, b1, a0, b0, g + 2);
   }
-#else
-#pragma unroll 1
-  for (int g = 0; g < G - 2; g += 2) {
-    {
-      const f32x4* bq = bptr + (size_t)(g + 1) * bstride;
-#pragma unroll
-      for (int j = 0; j < NCT; ++j) b1[j] = bq[j * 64];
-#pragma unroll
-      for (int i = 0; i < NRT; ++i) a1[i] = *reinterpret_cast<const f32x4*>(arow + i * 32 * CH_LD + (g + 1) * 8);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-      for (int i = 0; i < NRT; ++i)
-#pragma unroll
-        for (int j = 0; j < NCT; ++j) acc[i][j] = ch_mfma(b0[j][jj], a0[i][jj], acc[i][j]);
-    __builtin_amdgcn_sched_barrier(0);
-    {
-      const f32x4* bq = bptr + (size_t)(g + 2) * bstride;
-#pragma unroll
-      for (int j = 0; j < NCT; ++j) b0[j] = bq[j * 64];
-#pragma unroll
-      for (int i = 0; i < NRT; ++i) a0[i] = *reinterpret_cast<const f32x4*>(arow + i * 32 * CH_LD + (g + 2) * 8);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-      for (int i = 0; i < NRT; ++i)
-#pragma unroll
-        for (int j = 0; j < NCT; ++j) acc[i][j] = ch_mfma(b1[j][jj], a1[i][jj], acc[i][j]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#endif
   {
     const f32x4* bq = bptr + (size_t)(G - 1) * bstride;
 #pragma unroll
@@ -649,7 +596,6 @@ __device__ __forceinline__ void tq_mma_ring(const float* __restrict__ arow, cons
   for (; g + D <= G; g += D) {
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-#if NUDF_TQ_SPREAD
       const int nx = (d + D - 1) % D;
       int gn = g + d + D - 1;
       gn = (gn < glast) ? gn : glast;
@@ -667,12 +613,6 @@ __device__ __forceinline__ void tq_mma_ring(const float* __restrict__ arow, cons
           for (int j = 0; j < NCT; ++j) acc[i][j] = ch_mfma(b[d][j][jj], a[d][i][jj], acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
       }
-#else
-      load(a[(d + D - 1) % D], b[(d + D - 1) % D], g + d + D - 1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(a[d], b[d]);
-      __builtin_amdgcn_sched_barrier(0);
-#endif
     }
   }
   const int rem = G - g;
@@ -690,12 +630,11 @@ __device__ __forceinline__ void tq_mma_ring(const float* __restrict__ arow, cons
 }
 
 // the wave's tiles as straight-line code; X2 of tile t + 1 is requested before tile t is computed and stored.
-// S1: so is X1 -- only tile 0's X1 (px1[0][0]) and X2 (px2_0) were requested under the K loop, 32 registers instead of the
-// 64 of a whole-step X1 prefetch; the registers pay for a third operand set in the K loop (tq_mma_ring).
+// S1: so is X1 -- only tile 0's X1 (px1[0][0]) was requested under the K loop, 16 registers instead of the 64 of a
+// whole-step X1 prefetch; the registers pay for a third operand set in the K loop (tq_mma_ring).
 template <int EPI, int NRT, int NCT, bool S1 = false>
 __device__ __forceinline__ void tq_epilogue(const NudfChainStep& st, float* act, const ChrStep (&cs)[2], int rt0, int ct0,
-                                            int h, int ln, f32x16 (&acc)[2][2], float (&px1)[2][2][16], const float* bias_lds,
-                                            float (*px2_0)[16] = nullptr) {
+                                            int h, int ln, f32x16 (&acc)[2][2], float (&px1)[2][2][16], const float* bias_lds) {
   constexpr bool U1 = CH_USES_X1(EPI), U2 = CH_USES_X2(EPI);
   constexpr int NTL = NRT * NCT;
   float xa[2][16], xb[2][16];
@@ -716,14 +655,7 @@ __device__ __forceinline__ void tq_epilogue(const NudfChainStep& st, float* act,
       for (int e = 0; e < 4; ++e) x[4 * q + e] = v[e];
     }
   };
-  if (U2) {
-    if (S1 && px2_0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) xb[0][r] = (*px2_0)[r];
-    } else {
-      issue(xb[0], 0, 0);
-    }
-  }
+  if (U2) issue(xb[0], 0, 0);
 #pragma unroll
   for (int t = 0; t < NTL; ++t) {
     if (S1 && U1 && t + 1 < NTL) issue1(xa[(t + 1) & 1], (t + 1) / NCT, (t + 1) % NCT);
@@ -738,11 +670,11 @@ __device__ __forceinline__ void tq_epilogue(const NudfChainStep& st, float* act,
 template <int EPI, bool S1 = false>
 __device__ __forceinline__ void tq_epilogue_any(const NudfChainStep& st, float* act, const ChrStep (&cs)[2], int rt0, int ct0,
                                                 int nrt, int nct, int h, int ln, f32x16 (&acc)[2][2],
-                                                float (&px1)[2][2][16], const float* bias_lds, float (*px2_0)[16] = nullptr) {
-  if (nrt == 2 && nct == 2) tq_epilogue<EPI, 2, 2, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds, px2_0);
-  else if (nrt == 2) tq_epilogue<EPI, 2, 1, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds, px2_0);
-  else if (nct == 2) tq_epilogue<EPI, 1, 2, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds, px2_0);
-  else tq_epilogue<EPI, 1, 1, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds, px2_0);
+                                                float (&px1)[2][2][16], const float* bias_lds) {
+  if (nrt == 2 && nct == 2) tq_epilogue<EPI, 2, 2, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds);
+  else if (nrt == 2) tq_epilogue<EPI, 2, 1, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds);
+  else if (nct == 2) tq_epilogue<EPI, 1, 2, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds);
+  else tq_epilogue<EPI, 1, 1, S1>(st, act, cs, rt0, ct0, h, ln, acc, px1, bias_lds);
 }
 
 // S1: the epilogues' X1 operand is streamed one tile ahead (tq_epilogue) instead of prefetched for the whole step
@@ -804,10 +736,8 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
 
   // de-phase the two workgroups of a CU once (see mlp_chain_kernel)
   const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4);  // HW_REG_HW_ID.wave_id
-#if NUDF_TQ_SLEEP
   if (gridDim.x > 256)
     for (unsigned d = 0; d < (slot & 1u) * 2u; ++d) __builtin_amdgcn_s_sleep(127);
-#endif
 
   unsigned long long* dbg = p.dbg ? p.dbg + ((size_t)blockIdx.x * 4 + wave) * 64 : nullptr;
   if (dbg && lane == 0) {
@@ -818,11 +748,9 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
 
   for (int si = 0; si < p.n_steps; ++si) {
     const NudfChainStep& st = p.step[si];
-#if NUDF_TQ_PRIO == 1
+    // alternating wave priority per layer; with the one-off delay above: no difference beyond the run-to-run 0.3 % against
+    // none / a priority fixed by wave slot / no delay (profiles/r03_chain_experiments.txt item 4).  Kept as is.
     if ((si + slot) & 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#elif NUDF_TQ_PRIO == 2
-    if (si == 0) __builtin_amdgcn_s_setprio(slot & 1u);
-#endif
     const int G = st.K >> 3;
     const int NT = (st.N + 31) >> 5;
     int rt0, ct0, nrt, nct;
@@ -861,7 +789,6 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
 
     f32x16 acc[2][2];
     float px1[2][2][16];
-    float px2[16];      // S1: X2 of the wave's first tile
     // next step's bias: requested now, staged into LDS after the K loop (thread t <-> feature t)
     float nbias = 0.0f;
     if (si + 1 < p.n_steps) {
@@ -887,15 +814,6 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) px1[i][j][4 * q + e] = v[e];
             }
-        if (S1 && XCLS >= 2) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (u2) v = chr_load_quad(cs[0].X2, cs[0].x2, 32 * ct0 + 4 * h + 8 * q, cs[0].nq, cs[0].m2);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) px2[4 * q + e] = v[e];
-          }
-        }
       };
       if (RING > 1) {
         constexpr int D = RING > 1 ? RING : 2;
@@ -916,17 +834,17 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
 
     if (nct > 0) {
       switch (st.epi) {
-        case NUDF_CH_SOFTPLUS: tq_epilogue_any<NUDF_CH_SOFTPLUS, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_NONE: tq_epilogue_any<NUDF_CH_NONE, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_RELU: tq_epilogue_any<NUDF_CH_RELU, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_SIGMOIDN: tq_epilogue_any<NUDF_CH_SIGMOIDN, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_UDFHEAD: tq_epilogue_any<NUDF_CH_UDFHEAD, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_MULSP: if (XCLS >= 1) tq_epilogue_any<NUDF_CH_MULSP, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_MULMASK: if (XCLS >= 1) tq_epilogue_any<NUDF_CH_MULMASK, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_TANGENT: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_TANGENT, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_BWD: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_BWD, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_ADDMASK: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_ADDMASK, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
-        case NUDF_CH_RELUADD: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_RELUADD, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1], (S1 && XCLS >= 2) ? &px2 : nullptr); break;
+        case NUDF_CH_SOFTPLUS: tq_epilogue_any<NUDF_CH_SOFTPLUS, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_NONE: tq_epilogue_any<NUDF_CH_NONE, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_RELU: tq_epilogue_any<NUDF_CH_RELU, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_SIGMOIDN: tq_epilogue_any<NUDF_CH_SIGMOIDN, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_UDFHEAD: tq_epilogue_any<NUDF_CH_UDFHEAD, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_MULSP: if (XCLS >= 1) tq_epilogue_any<NUDF_CH_MULSP, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_MULMASK: if (XCLS >= 1) tq_epilogue_any<NUDF_CH_MULMASK, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_TANGENT: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_TANGENT, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_BWD: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_BWD, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_ADDMASK: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_ADDMASK, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
+        case NUDF_CH_RELUADD: if (XCLS >= 2) tq_epilogue_any<NUDF_CH_RELUADD, S1>(st, sm.act, cs, rt0, ct0, nrt, nct, h, ln, acc, px1, sm.bias[si & 1]); break;
         default: break;
       }
     }
@@ -1181,15 +1099,7 @@ int nudf_chain_pair_mode() {
 int nudf_mlp_chain_tq_launch(const NudfChain& p, int cls, hipStream_t st, int force_pair) {
   const dim3 grid((p.P + 63) / 64), block(256);
   // forward sweeps (no stored-state operand): three register sets in the K loop, two k groups of operand reads in flight
-  // (tq_mma_ring; measured 629 -> 605 us at 65 536 points).  NUDF_TQ_RING=0: two sets.
-  static const int ring = [] {
-    const char* e = getenv("NUDF_TQ_RING");
-    return e ? atoi(e) : 3;
-  }();
-  static const int s1 = [] {
-    const char* e = getenv("NUDF_TQ_S1");
-    return e ? atoi(e) : 1;
-  }();
+  // (tq_mma_ring; measured 629 -> 605 us at 65 536 points against two sets).
   if (force_pair || (nudf_chain_pair_mode() > 0 && p.P >= 32768)) {   // paired tiles: tile_rows 130 / NUDF_CHAIN_PAIR
     const dim3 pgrid((p.P + 127) / 128), pblock(512);
     if (cls == 0) hipLaunchKernelGGL((mlp_chain_pair_kernel<0>), pgrid, pblock, 0, st, p);
@@ -1198,17 +1108,12 @@ int nudf_mlp_chain_tq_launch(const NudfChain& p, int cls, hipStream_t st, int fo
     NUDF_CHECK_LAUNCH("nudf_mlp_chain(pair)");
     return 0;
   }
-  if (cls == 0 && ring == 3) hipLaunchKernelGGL((mlp_chain_tq_kernel<0, 3>), grid, block, 0, st, p);
-  else if (cls == 0) hipLaunchKernelGGL((mlp_chain_tq_kernel<0>), grid, block, 0, st, p);
-  // input-gradient sweeps: X1 streamed one tile ahead (NUDF_TQ_S1, default 1) frees the registers for the third operand
-  // set (197 VGPRs, 646-652 -> 637 us at 65 536 points).  The tangent / adjoint instantiation gets SLOWER with a streamed
-  // X1, with two or three operand sets (tangent 675 -> 703 us, adjoint 692-750 -> 727-775: two more exposed operand
-  // requests per tile): it keeps the whole-step prefetch; NUDF_TQ_S1=2 / 3 select those builds for measurements.
-  else if (cls == 1 && s1 && ring == 3) hipLaunchKernelGGL((mlp_chain_tq_kernel<1, 3, true>), grid, block, 0, st, p);
-  else if (cls == 1 && s1) hipLaunchKernelGGL((mlp_chain_tq_kernel<1, 0, true>), grid, block, 0, st, p);
-  else if (cls == 1) hipLaunchKernelGGL((mlp_chain_tq_kernel<1>), grid, block, 0, st, p);
-  else if (s1 == 3 && ring == 3) hipLaunchKernelGGL((mlp_chain_tq_kernel<2, 3, true>), grid, block, 0, st, p);
-  else if (s1 >= 2) hipLaunchKernelGGL((mlp_chain_tq_kernel<2, 0, true>), grid, block, 0, st, p);
+  if (cls == 0) hipLaunchKernelGGL((mlp_chain_tq_kernel<0, 3>), grid, block, 0, st, p);
+  // input-gradient sweeps: X1 streamed one tile ahead frees the registers for the third operand set (197 VGPRs, 646-652 ->
+  // 637 us at 65 536 points).  The tangent / adjoint instantiation gets SLOWER with a streamed X1, with two or three operand
+  // sets (tangent 675 -> 703 us, adjoint 692-750 -> 727-775: two more exposed operand requests per tile): it keeps the
+  // whole-step prefetch and two sets.
+  else if (cls == 1) hipLaunchKernelGGL((mlp_chain_tq_kernel<1, 3, true>), grid, block, 0, st, p);
   else hipLaunchKernelGGL((mlp_chain_tq_kernel<2>), grid, block, 0, st, p);
   NUDF_CHECK_LAUNCH("nudf_mlp_chain(tq)");
   return 0;

@@ -574,7 +574,7 @@ TN_ASSIGN = os.environ.get("NUDF_TN_ASSIGN", "1") == "1"     # A/B + tests: 0 = 
 
 def tn_can_assign():
     """the weight-gradient launches can ASSIGN their outputs (two-pass deterministic reduction; not the atomic A/B path)"""
-    return TN_ASSIGN and TN_DETERMINISTIC and not (int(os.environ.get("NUDF_TN_FLAGS", "0")) & (8 | 2))
+    return TN_ASSIGN and TN_DETERMINISTIC and not (int(os.environ.get("NUDF_TN_FLAGS", "0")) & 8)
 
 
 def gemm_tn_grouped(jobs, M, assign=False, rows_per_block=0, f16x2=False, amax_a=None, amax_b=None):

@@ -16,9 +16,9 @@ batch = {k: v.to(dev) for k, v in rays.items()}
 for _ in range(5):
     tr.step(batch)
 torch.cuda.synchronize()
-if os.environ.get("PROBE_GC_FREEZE") == "1":
+if os.environ.get("FWD_GC_FREEZE") == "1":
     gc.collect(); gc.freeze()
-if os.environ.get("PROBE_GC_OFF") == "1":
+if os.environ.get("FWD_GC_OFF") == "1":
     gc.disable()
 for rep in range(4):
     g0 = [s["collections"] for s in gc.get_stats()]

@@ -167,7 +167,6 @@ if os.environ.get("TN_BENCH_16"):       # 16-bit MFMA mode: packed k-pair image 
     for rnd in range(2):
         timed("packed k-pair image (default)", 0)
         timed("generic kernel, fp32 image (256)", 256)
-        timed("no epilogue: packed", 2)
     sys.exit(0)
 if os.environ.get("TN_BENCH_CHECK"):
     check(int(os.environ["TN_BENCH_CHECK"]))
@@ -179,8 +178,6 @@ if os.environ.get("TN_BENCH_AB"):      # interleaved full-tile loop + XCD-aware 
         timed("default (interleaved full-tile loop, XCD-aware order)", 0)
         timed("generic k-loop for full tiles (128)", 128)
         timed("tile-major blockIdx order (64)", 64)
-        timed("no epilogue: default", 2)
-        timed("no epilogue: generic k-loop", 130)
     run(30)
     timeline("default", 0)
     sys.exit(0)
@@ -198,8 +195,6 @@ for rnd in range(2):      # twice: the first lines of a fresh process also pay c
     timed("workspace + reduce, equal chunks", 16)
     timed("fp32 atomics, cost-weighted chunks", 8, deterministic=False)
     timed("fp32 atomics, equal chunks", 24, deterministic=False)
-    timed("no epilogue at all (timing only)", 2)
-    timed("no epilogue, no bias sums (timing only)", 6)
     timed("workspace + reduce, cost-weighted, no 2x2 quadrant layout", 32)
     timed("workspace + reduce, equal chunks, no 2x2 quadrant layout", 48)
 

@@ -2,7 +2,7 @@
 // operand bits?  The chip clocks to its 1400 W package limit: the dense bf16 "peak" a kernel can be priced against is the rate
 // of this loop on data of the kernel's bit activity, not 2.5 PFLOP/s at 2.4 GHz.  Two waves per SIMD (512 workgroups x 4 waves),
 // four independent accumulators per wave, eight operand register sets rotated so consecutive MFMAs see different bits.
-// Prints TFLOP/s, the shader clock s_memtime saw, and (via rocm-smi, if present) nothing -- run scripts/tn3_power.py for power.
+// Prints TFLOP/s and the shader clock s_memtime saw; power is read beside it (scripts/chain_power.py samples it the same way).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>

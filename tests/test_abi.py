@@ -131,6 +131,18 @@ def test_weight_gradient_gemm_plan_host_logic():
     assert lib.nudf_gemm_tn_grouped_workspace(C.byref(g2)) > 0
 
 
+def test_retired_tn_flag_bits_are_masked_off():
+    """bits 2 (drop the epilogue) and 4 (skip the bias sums) of nudf_set_tn_flags computed wrong results on purpose and are
+    retired: the setter drops them, so an old command line cannot produce garbage.  Host-only call."""
+    from neuraludf_amd import _lib
+    lib = _lib.lib()
+    prev = lib.nudf_set_tn_flags(2 | 4 | 16)
+    try:
+        assert lib.nudf_set_tn_flags(0) == 16
+    finally:
+        lib.nudf_set_tn_flags(prev)
+
+
 def test_per_layer_weight_gradient_gemm_refuses_formatted_operands():
     """nudf_gemm_tn reads row-major fp32 only: the per-layer fallback must refuse bf16-stored / blocked-layout state
     instead of producing silent garbage."""
