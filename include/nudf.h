@@ -158,6 +158,13 @@ int64_t nudf_gemm_tn_grouped_workspace(const NudfGemmTNGroup* args);
  * same XCD: the tiles of a problem that read the same row chunk are given the same b % 8 -- every chunk, the holes are what
  * that costs -- and no XCD receives more live workgroups than it holds at once (64). */
 int nudf_gemm_tn_grouped_plan(const NudfGemmTNGroup* args, int32_t* out, int capacity);
+/* which kernel nudf_gemm_tn_grouped gives this group (host code only: the launcher's own plan, checks and selection; nothing
+ * the group points to is read, nothing is launched).  name (capacity bytes) receives gemm_tn_group_kernel (the generic fp32-image
+ * kernel), gemm_tn16_group_kernel, gemm_tn3_group_kernel, gemm_tn3w_group_kernel or gemm_tn2_group_kernel, and out[0..3] =
+ * {grid.x, block.x, grid.x of the tn_reduce_kernel launch that follows (workspace path) or 0, 0}.  Returns what
+ * nudf_gemm_tn_grouped would return before launching: 0, or the error of a refused group (text in nudf_last_error, empty
+ * name, zero grids).  An empty group gives 0, an empty name and zero grids. */
+int nudf_gemm_tn_grouped_kernel(const NudfGemmTNGroup* args, char* name, int capacity, int32_t* out);
 /* tuning / cross-check bits (every one computes correct results), returns the old value: 8 = ignore the workspace
  * (atomics), 16 = equal row chunks for every tile instead of the cost-weighted split, 32 = no 2 x 2 quadrant layout for full
  * tiles, 64 = tile-major workgroup order instead of the XCD-aware one, 128 = full fp32 tiles through the generic k-loop
@@ -630,7 +637,7 @@ typedef struct NudfChain {
                                       kernel (4 waves x 32 points); 130 = two 64-point tiles per workgroup run in
                                       anti-phase (mlp_chain_pair_kernel: opt-in, a measured counter-example -- NUDF_CHAIN_PAIR);
                                       66 / 128 / 130 need fp32 steps and 16-byte aligned rows and fall back
-                                      to 64 otherwise */
+                                      to 64 otherwise (NUDF_CH_TILE_* below; nudf_mlp_chain_plan tells what a launch gets) */
   int32_t lda0, ldg0;
   int32_t pe_L, pe_jvp;            /* positional encoding: frequencies, 1 = JVP with tangent v       */
   int32_t init_state16;            /* INIT_SEED: bit 0 = A0 holds bf16, bit 1 = G0 receives bf16, bit 2 = A0 is in the
@@ -671,10 +678,20 @@ typedef struct NudfChain {
   int32_t reserved0;
   NudfChainStep step[NUDF_CH_MAX_STEPS];
 } NudfChain;
+#define NUDF_CH_TILE_TQ 66            /* NudfChain.tile_rows: the transposed-product shared tile (mlp_chain_tq_kernel)  */
+#define NUDF_CH_TILE_ROWS 128         /* ... the wave-private kernel (mlp_chain_rows_kernel)                            */
+#define NUDF_CH_TILE_PAIR 130         /* ... paired transposed-product tiles (mlp_chain_pair_kernel)                    */
 #if defined(__cplusplus)
 static_assert(sizeof(NudfChain) <= 4096, "NudfChain travels by value: the kernel-argument segment holds 4 KB");
 #endif
 int nudf_mlp_chain(const NudfChain* args, void* stream);
+/* which kernel nudf_mlp_chain gives this descriptor (host code only: the launcher's own check and selection, nothing the
+ * descriptor points to is read, nothing is launched).  name (capacity bytes) receives the instantiation as spelled in the
+ * source -- "mlp_chain_kernel<64, 2>", "mlp_chain_tq_kernel<1, 3, true>", ... -- and out[0..3] = {grid.x, block.x, 0, 0}.
+ * Returns what nudf_mlp_chain would return before launching: 0, or the error of a refused descriptor (text in
+ * nudf_last_error, empty name, zero grid).  An empty launch (P <= 0 or no steps) gives 0, an empty name and a zero grid.
+ * The choice depends on the process-wide settings NUDF_CHAIN_ROWS / _QUAD / _PAIR / _T16 / _WIN2. */
+int nudf_mlp_chain_plan(const NudfChain* args, char* name, int capacity, int32_t* out);
 /* NUDF_CH_MAX_STEPS of the header the library was compiled against: the array bound sets sizeof(NudfChain), so a caller that
  * passes the struct by reference checks it as it checks nudf_version() (the Python loader refuses a library that differs). */
 int nudf_chain_max_steps(void);

@@ -258,14 +258,14 @@ EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMO
 
 # every symbol include/nudf.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
-    "nudf_version", "nudf_chain_max_steps", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_set_gemm_variant", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
+    "nudf_version", "nudf_chain_max_steps", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_set_gemm_variant", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_gemm_tn_grouped_kernel", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
     "nudf_composite_bwd", "nudf_partial_sums", "nudf_composite_colour_finish", "nudf_set_composite_blocked", "nudf_upsample", "nudf_merge", "nudf_merge_points", "nudf_coarse_z", "nudf_coarse_start", "nudf_outside_z",
     "nudf_ray_points", "nudf_posenc", "nudf_posenc_vjp", "nudf_copy_cols", "nudf_add_cols",
     "nudf_udf_grad_seed", "nudf_udf_head_bwd", "nudf_signed_colsum", "nudf_sigmoid_head_bwd",
     "nudf_weightnorm_pack", "nudf_weightnorm_unpack_grad",
     "nudf_pixel_blend_fwd", "nudf_pixel_blend_bwd", "nudf_pixel_composite_fwd", "nudf_pixel_composite_bwd",
     "nudf_patch_blend_fwd", "nudf_patch_blend_bwd", "nudf_ssim_patch", "nudf_pixel_warp", "nudf_patch_warp",
-    "nudf_adam_step", "nudf_adam_chunk", "nudf_mlp_chain", "nudf_set_chain_t16", "nudf_pack_frag",
+    "nudf_adam_step", "nudf_adam_chunk", "nudf_mlp_chain", "nudf_mlp_chain_plan", "nudf_set_chain_t16", "nudf_pack_frag",
     "nudf_weightnorm_pack_multi", "nudf_weightnorm_unpack_grad_multi",
     "nudf_scalars_fwd", "nudf_scalars_bwd", "nudf_l1_sum_fwd", "nudf_l1_sum_bwd",
     "nudf_sums_errors_fwd", "nudf_sums_errors_bwd", "nudf_color_loss_fwd", "nudf_color_loss_bwd",
@@ -292,6 +292,7 @@ _ARGTYPES = {
     "nudf_gemm_tn_grouped": [C.POINTER(GemmTNGroup), _P],
     "nudf_gemm_tn_grouped_workspace": [C.POINTER(GemmTNGroup)],
     "nudf_gemm_tn_grouped_plan": [C.POINTER(GemmTNGroup), C.POINTER(C.c_int32), i32],
+    "nudf_gemm_tn_grouped_kernel": [C.POINTER(GemmTNGroup), C.c_char_p, i32, C.POINTER(C.c_int32)],
     "nudf_set_tn_flags": [i32],
     "nudf_set_tn_debug": [_P],
     "nudf_composite_fwd": [C.POINTER(Composite), _P],
@@ -327,6 +328,7 @@ _ARGTYPES = {
     "nudf_patch_metric": [_I] + [_P, _P, _P, _I, _I, _P, _P, _P, _P],
     "nudf_adam_step": [C.POINTER(Adam), _P],
     "nudf_mlp_chain": [C.POINTER(Chain), _P],
+    "nudf_mlp_chain_plan": [C.POINTER(Chain), C.c_char_p, i32, C.POINTER(C.c_int32)],
     "nudf_pack_frag": [_P, _I, _I, _I, _P, _P],
     "nudf_weightnorm_pack_multi": [C.POINTER(PackMulti), _P],
     "nudf_weightnorm_unpack_grad_multi": [C.POINTER(UnpackMulti), _P],
@@ -414,6 +416,11 @@ def lib():
                 v, _lib = (None if size is None else int(size())), None
                 raise NudfError(f"{LIB_PATH}: {name}() is {v}, this package binds {C.sizeof(mirror)} bytes: rebuild with "
                                 "`python -m neuraludf_amd.build --force`")
+        # (the two dispatch reports came without a version step as well: a library from before them is refused by name)
+        for name in ("nudf_mlp_chain_plan", "nudf_gemm_tn_grouped_kernel"):
+            if getattr(_lib, name, None) is None:
+                _lib = None
+                raise NudfError(f"{LIB_PATH} does not export {name}: rebuild with `python -m neuraludf_amd.build --force`")
         _bind(_lib)
         _lib.nudf_gemm_tn_grouped_workspace.restype = C.c_int64
         _lib.nudf_set_chain_t16.argtypes = [C.c_int]
@@ -507,3 +514,12 @@ def call(name, *args):
     rc = fn(*[C.byref(a) if isinstance(a, C.Structure) else a for a in args], stream())
     if rc != 0:
         check(rc, name)
+
+
+def kernel_of(name, desc):
+    """what the launcher would give `desc`, from its host-only report `name` (nudf_mlp_chain_plan / nudf_gemm_tn_grouped_kernel):
+    (kernel instantiation, [grid.x, block.x, grid.x of the reduce launch or 0, 0]); ("", zeros) for an empty or a refused
+    descriptor -- the launch itself raises the refusal."""
+    buf, out = C.create_string_buffer(64), (C.c_int32 * 4)()
+    getattr(lib(), name)(C.byref(desc), buf, len(buf), out)
+    return buf.value.decode(), list(out)

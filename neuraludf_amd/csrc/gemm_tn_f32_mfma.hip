@@ -2090,75 +2090,91 @@ extern "C" int nudf_gemm_tn_grouped_plan(const NudfGemmTNGroup* args, int32_t* o
   return pl.grid_blocks;
 }
 
-extern "C" int nudf_gemm_tn_grouped(const NudfGemmTNGroup* args, void* stream) {
-  TnPlan pl;
-  const int blocks = tn_plan(*args, pl);
+// The five kernels behind the plan: the name and the launch of a row are made from the same token
+struct TnKernel {
+  const char* name;
+  int threads;
+  void (*launch)(const TnPlan& pl, int grid, hipStream_t st);
+};
+template <int THREADS, void (*KERNEL)(TnPlan)>
+static void tn_launch(const TnPlan& pl, int grid, hipStream_t st) {
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(THREADS), 0, st, pl);
+}
+#define TN_KERNEL(kernel, threads) {#kernel, threads, tn_launch<threads, kernel>}
+enum { TN_GENERIC, TN_16, TN_3, TN_3W, TN_2 };
+static const TnKernel g_tn_kernels[] = {
+    TN_KERNEL(gemm_tn_group_kernel, 256), TN_KERNEL(gemm_tn16_group_kernel, 256), TN_KERNEL(gemm_tn3_group_kernel, 256),
+    TN_KERNEL(gemm_tn3w_group_kernel, 512), TN_KERNEL(gemm_tn2_group_kernel, 256),
+};
+
+// Plan, check and select: completes `pl` with the launch's options and picks the kernel (kernel < 0: an empty group), its grid
+// and the grid of the tn_reduce_kernel launch that follows (0: none).  Host logic only, nothing the group points to is read.
+static int tn_select(const NudfGemmTNGroup& g, TnPlan& pl, int& kernel, int& grid, int& reduce_grid) {
+  kernel = -1;
+  grid = reduce_grid = 0;
+  const int blocks = tn_plan(g, pl);
   if (blocks == 0) return 0;
   if (blocks < 0) return (int)hipErrorInvalidValue;
-  pl.ws = (pl.flags & TNF_ATOMICS) ? nullptr : args->workspace;
+  pl.ws = (pl.flags & TNF_ATOMICS) ? nullptr : g.workspace;
   pl.dbg = g_tn_dbg;
-  pl.assign = args->assign ? 1 : 0;
-  if (pl.assign && !pl.ws) {
-    nudf_set_error("nudf_gemm_tn_grouped: assign needs the workspace (two-pass) path", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
-  if (pl.ws && ((((uintptr_t)pl.ws) & 15) || args->workspace_floats < (int64_t)blocks * TN_WS_TILE)) {
-    nudf_set_error("nudf_gemm_tn_grouped: workspace too small or not 16-byte aligned "
-                   "(nudf_gemm_tn_grouped_workspace gives the size)", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
-  // 16-bit MFMA mode: the packed-image kernel, unless an operand is in the blocked fp32 layout (generic kernel only) or
-  // most operands are stored as fp32 (its staging of an fp32 operand is heavier: 262 -> 278 us with all-fp32 operands,
-  // 228 -> 183 us with all-bf16 ones at 65 536 points)
-  bool packed16 = pl.prec != 0 && pl.prec != 3 && !(pl.flags & TNF_NO_PACK16);   // (bf16x3 splits from the fp32 image)
+  pl.assign = g.assign ? 1 : 0;
+  if (pl.assign && !pl.ws) return nudf_refuse("nudf_gemm_tn_grouped: assign needs the workspace (two-pass) path");
+  if (pl.ws && ((((uintptr_t)pl.ws) & 15) || g.workspace_floats < (int64_t)blocks * TN_WS_TILE))
+    return nudf_refuse("nudf_gemm_tn_grouped: workspace too small or not 16-byte aligned "
+                     "(nudf_gemm_tn_grouped_workspace gives the size)");
   int n16 = 0;
-  for (int i = 0; i < args->n_problems && packed16; ++i) {
-    const int f = args->prob[i].flags;
-    if (f & (NUDF_TN_A_BLK | NUDF_TN_B_BLK)) packed16 = false;
+  bool any_p4 = false, any_blk = false, any_fmt = false;    // (any_fmt: an operand that is not fp32 row-major)
+  for (int i = 0; i < g.n_problems; ++i) {
+    const int f = g.prob[i].flags;
     n16 += ((f & NUDF_TN_A16) ? 1 : 0) + ((f & NUDF_TN_B16) ? 1 : 0);
+    any_p4 = any_p4 || (f & (NUDF_TN_A_P4 | NUDF_TN_B_P4));
+    any_blk = any_blk || (f & (NUDF_TN_A_BLK | NUDF_TN_B_BLK));
+    any_fmt = any_fmt || (f & (NUDF_TN_A16 | NUDF_TN_B16 | NUDF_TN_A_BLK | NUDF_TN_B_BLK | NUDF_TN_A_P4 | NUDF_TN_B_P4));
   }
-  if (n16 < args->n_problems) packed16 = false;
-  bool any_p4 = false;
-  for (int i = 0; i < args->n_problems; ++i) any_p4 = any_p4 || (args->prob[i].flags & (NUDF_TN_A_P4 | NUDF_TN_B_P4));
-  if (any_p4) {   // only the packed-image kernel reads 4-point packed operands
-    for (int i = 0; i < args->n_problems; ++i)
-      if (args->prob[i].flags & (NUDF_TN_A_BLK | NUDF_TN_B_BLK)) {
-        nudf_set_error("nudf_gemm_tn_grouped: 4-point packed and blocked operands cannot share a group", hipErrorInvalidValue);
-        return (int)hipErrorInvalidValue;
-      }
-    packed16 = true;
-  }
-  // bf16x3 mode: the split-image kernel when every operand is fp32 row-major (what the bf16x3 chains store); anything else
-  // goes through the generic kernel, which splits on the way OUT of its fp32 image (NUDF_TN_FLAGS & 512 forces that: A/B)
+  // only the packed-image kernel reads 4-point packed operands
+  if (any_p4 && any_blk) return nudf_refuse("nudf_gemm_tn_grouped: 4-point packed and blocked operands cannot share a group");
   // f16x2 mode (prec 4): fp32 row-major operands only (what the split-mode chains store); anything else is an error -- the
   // caller decides per group (mlp.py) and falls back to prec 3 itself
+  if (pl.prec == 4 && any_fmt) return nudf_refuse("nudf_gemm_tn_grouped: prec 4 (f16x2) takes fp32 row-major operands");
   if (pl.prec == 4) {
-    for (int i = 0; i < args->n_problems; ++i)
-      if (args->prob[i].flags & (NUDF_TN_A16 | NUDF_TN_B16 | NUDF_TN_A_BLK | NUDF_TN_B_BLK | NUDF_TN_A_P4 | NUDF_TN_B_P4)) {
-        nudf_set_error("nudf_gemm_tn_grouped: prec 4 (f16x2) takes fp32 row-major operands", hipErrorInvalidValue);
-        return (int)hipErrorInvalidValue;
-      }
-    pl.amax_a = args->amax_a;
-    pl.amax_b = args->amax_b;
-    hipLaunchKernelGGL(gemm_tn2_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
-    NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped");
-    if (pl.ws) {
-      hipLaunchKernelGGL(tn_reduce_kernel, dim3(pl.n_tiles * 17), dim3(256), 0, (hipStream_t)stream, pl);
-      NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped (reduce)");
-    }
-    return 0;
+    pl.amax_a = g.amax_a;
+    pl.amax_b = g.amax_b;
+    kernel = TN_2;
+  } else if (pl.prec == 3 && !(pl.flags & TNF_NO_SPLIT_IMAGE) && !any_fmt) {
+    // bf16x3 mode: the split-image kernel when every operand is fp32 row-major (what the bf16x3 chains store); anything else
+    // goes through the generic kernel, which splits on the way OUT of its fp32 image (NUDF_TN_FLAGS & 512 forces that: A/B)
+    kernel = pl.wide ? TN_3W : TN_3;
+  } else if (any_p4 || (pl.prec != 0 && pl.prec != 3 && !(pl.flags & TNF_NO_PACK16) && !any_blk && n16 >= g.n_problems)) {
+    // 16-bit MFMA mode: the packed-image kernel, unless an operand is in the blocked fp32 layout (generic kernel only) or
+    // most operands are stored as fp32 (its staging of an fp32 operand is heavier: 262 -> 278 us with all-fp32 operands,
+    // 228 -> 183 us with all-bf16 ones at 65 536 points); bf16x3 splits from the fp32 image
+    kernel = TN_16;
+  } else {
+    kernel = TN_GENERIC;
   }
-  bool split3 = pl.prec == 3 && !(pl.flags & TNF_NO_SPLIT_IMAGE);
-  for (int i = 0; i < args->n_problems && split3; ++i)
-    if (args->prob[i].flags & (NUDF_TN_A16 | NUDF_TN_B16 | NUDF_TN_A_BLK | NUDF_TN_B_BLK | NUDF_TN_A_P4 | NUDF_TN_B_P4)) split3 = false;
-  if (split3 && pl.wide)
-    hipLaunchKernelGGL(gemm_tn3w_group_kernel, dim3(pl.n_units * pl.unit_chunks), dim3(512), 0, (hipStream_t)stream, pl);
-  else if (split3) hipLaunchKernelGGL(gemm_tn3_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
-  else if (packed16) hipLaunchKernelGGL(gemm_tn16_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
-  else hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(pl.grid_blocks), dim3(256), 0, (hipStream_t)stream, pl);
+  grid = kernel == TN_3W ? pl.n_units * pl.unit_chunks : pl.grid_blocks;
+  reduce_grid = pl.ws ? pl.n_tiles * 17 : 0;
+  return 0;
+}
+
+extern "C" int nudf_gemm_tn_grouped_kernel(const NudfGemmTNGroup* args, char* name, int capacity, int32_t* out) {
+  TnPlan pl;
+  int kernel, grid, reduce_grid;
+  const int err = tn_select(*args, pl, kernel, grid, reduce_grid);
+  const TnKernel* k = (!err && kernel >= 0) ? &g_tn_kernels[kernel] : nullptr;
+  nudf_report_kernel(name, capacity, out, k ? k->name : nullptr, grid, k ? k->threads : 0, reduce_grid);
+  return err;
+}
+
+extern "C" int nudf_gemm_tn_grouped(const NudfGemmTNGroup* args, void* stream) {
+  TnPlan pl;
+  int kernel, grid, reduce_grid;
+  const int err = tn_select(*args, pl, kernel, grid, reduce_grid);
+  if (err || kernel < 0) return err;
+  g_tn_kernels[kernel].launch(pl, grid, (hipStream_t)stream);
   NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped");
-  if (pl.ws) {
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3(pl.n_tiles * 17), dim3(256), 0, (hipStream_t)stream, pl);
+  if (reduce_grid) {
+    hipLaunchKernelGGL(tn_reduce_kernel, dim3(reduce_grid), dim3(256), 0, (hipStream_t)stream, pl);
     NUDF_CHECK_LAUNCH("nudf_gemm_tn_grouped (reduce)");
   }
   return 0;

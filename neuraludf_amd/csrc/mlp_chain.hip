@@ -1556,59 +1556,72 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? CH_T16_WGS : 2) void mlp_
   }
 }
 
-int nudf_chain_rows_class(const NudfChain& p, bool allow_blocked = false);  // mlp_chain_rows.hip
-int nudf_mlp_chain_rows_launch(const NudfChain& p, int cls, hipStream_t st);
-int nudf_mlp_chain_tq_launch(const NudfChain& p, int cls, hipStream_t st, int force_pair = 0);
-int nudf_chain_pair_mode();
+// ---------------------------------------------------------------------------------------------------
+// host side: check the descriptor, select one row of the kernel table, launch that row
+// ---------------------------------------------------------------------------------------------------
+// mlp_chain_kernel's rows of the table (ChainKernelId of mlp_chain_shared.h); the other ten are in mlp_chain_rows.hip
+static const ChainKernel g_shared_kernels[CK_PAIR] = {
+    CH_KERNEL(32, CH_THREADS, mlp_chain_kernel<32, 2>), CH_KERNEL(32, CH_THREADS, mlp_chain_kernel<32, 1>),
+    CH_KERNEL(32, CH_THREADS, mlp_chain_kernel<32, 0>),
+    CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 2>), CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 4>),
+    CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 3>), CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 1>),
+    CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 0>),
+};
+static const ChainKernel& chain_kernel(int id) { return id < CK_PAIR ? g_shared_kernels[id] : nudf_chain_tq_kernel(id); }
 
-// NUDF_CHAIN_ROWS=1 lets large launches choose the wave-private kernel on their own (measured in round 2: equal to
-// the workgroup-shared tiles on the forward sweeps, 10-20 % slower on the sweeps that stream stored state, see
-// DESIGN.md section 4.1b); tile_rows = 128 requests it explicitly.  Read once.
-static bool nudf_chain_rows_auto() {
-  static const int on = [] {
-    const char* e = getenv("NUDF_CHAIN_ROWS");
-    return (e && e[0] == '1') ? 1 : 0;
+// The process-wide settings of the selection, read once:
+//  NUDF_CHAIN_ROWS=1 lets large launches choose the wave-private kernel on their own (measured in round 2: equal to the
+//    workgroup-shared tiles on the forward sweeps, 10-20 % slower on the sweeps that stream stored state, see DESIGN.md section
+//    4.1b); tile_rows = NUDF_CH_TILE_ROWS requests it explicitly.
+//  NUDF_CHAIN_QUAD: the transposed-product form of the 64-point tile (mlp_chain_rows.hip, tile_rows = NUDF_CH_TILE_TQ: 16-byte
+//    epilogue accesses).  Measured at 65 536 points against mlp_chain_kernel<64> (profiles/r02_chain_timeline.txt): per-wave
+//    time -8 % / -6 % on the UDF forward / input-gradient sweeps, +9 % / +5 % on the tangent / adjoint sweeps (two stored
+//    operands and two outputs per layer: with row-major buffers each 16-byte-per-lane access touches 32 different 128-byte
+//    lines); with the BLOCKED layout of nudf.h addressed instead (timing only) -8 / -10 / -7 / -4 %.  Over a whole train step
+//    the forward / gradient gain is inside the noise (3.95 vs 3.98 ms of chain time), so the default stays mlp_chain_kernel:
+//    =1 uses the transposed form for launches with at most one stored operand, =2 for every launch.
+//  NUDF_CHAIN_PAIR: 0 (default) = independent 64-point workgroups; 1 = launches of at least 32 768 points that already go to
+//    the transposed-product kernel (blocked state: the UDF sweeps) run as paired tiles (mlp_chain_pair_kernel); 2 = every fp32
+//    launch of at least 32 768 points that meets that kernel's contract does (colour / NeRF chains, coarse forward).  MEASURED
+//    (round 3, profiles/r03_chain_pair.txt): not faster -- a K loop alone on the pipe next to the partner's epilogue reaches
+//    only 77 % of the pipe rate (two in-phase K loops together 95 %), and the epilogue beside a K loop takes 1.8x as long; the
+//    kernel stays as the measured counter-example to "enforce anti-phase".
+//  NUDF_CHAIN_T16=0 / nudf_set_chain_t16: keep the fp32-tile kernel in the 16-bit mode (A/B; the two are bit-identical).
+//  NUDF_CHAIN_WIN2=3: the wave-private kernel's operand window (tiles in flight per stored-state operand) is 4 with one
+//    operand and 2 with two (3 makes the register allocator spill ~100 values per step; =3 selects that build for measurements).
+struct ChainSettings { int rows_auto, quad, pair, t16, win2; };
+static ChainSettings& chain_settings() {
+  static ChainSettings s = [] {
+    auto env = [](const char* name) { const char* e = getenv(name); return e ? e : ""; };
+    return ChainSettings{env("NUDF_CHAIN_ROWS")[0] == '1', atoi(env("NUDF_CHAIN_QUAD")), atoi(env("NUDF_CHAIN_PAIR")),
+                         env("NUDF_CHAIN_T16")[0] != '0', env("NUDF_CHAIN_WIN2")[0] == '3' ? 3 : 2};
   }();
-  return on != 0;
-}
-
-// The transposed-product form of the 64-point tile (mlp_chain_rows.hip, tile_rows = 66: 16-byte epilogue accesses).
-// Measured at 65 536 points against mlp_chain_kernel<64> (profiles/r02_chain_timeline.txt): per-wave time -8 % / -6 % on
-// the UDF forward / input-gradient sweeps, +9 % / +5 % on the tangent / adjoint sweeps (two stored operands and two
-// outputs per layer: with row-major buffers each 16-byte-per-lane access touches 32 different 128-byte lines); with the
-// BLOCKED layout of nudf.h addressed instead (timing only) -8 / -10 / -7 / -4 %.  Over a whole train step the
-// forward / gradient gain is inside the noise (3.95 vs 3.98 ms of chain time), so the default stays mlp_chain_kernel:
-// NUDF_CHAIN_QUAD=1 uses the transposed form for launches with at most one stored operand, =2 for every launch.
-static int nudf_chain_quad_mode() {
-  static const int mode = [] {
-    const char* e = getenv("NUDF_CHAIN_QUAD");
-    return e ? atoi(e) : 0;
-  }();
-  return mode;
-}
-
-static int g_chain_t16 = -1;     // NUDF_CHAIN_T16 / nudf_set_chain_t16
-static bool nudf_chain_t16_enabled() {
-  if (g_chain_t16 < 0) {
-    const char* e = getenv("NUDF_CHAIN_T16");
-    g_chain_t16 = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_chain_t16 != 0;
+  return s;
 }
 extern "C" int nudf_set_chain_t16(int on) {
-  const int old = nudf_chain_t16_enabled() ? 1 : 0;
-  g_chain_t16 = on ? 1 : 0;
+  const int old = chain_settings().t16;
+  chain_settings().t16 = on ? 1 : 0;
   return old;
 }
 
 extern "C" int nudf_chain_max_steps(void) { return NUDF_CH_MAX_STEPS; }
 
-extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
-  const NudfChain& p = *args;
-  if (p.P <= 0 || p.n_steps <= 0) return 0;
+// what the check learns about a descriptor on its way and the selection needs
+struct ChainFacts {
+  bool fused, any16, any3;   // a SEED step (two sweeps in one launch); a 16-bit step or 16-bit stored state; a split-mode step
+  bool roww, blocked;        // a SIGMOIDN step composites in its epilogue (row_w / row_sums); a buffer in the blocked layout
+  int cls;                   // operand class of the transposed-product kernels (nudf_chain_rows_class), -1: contract not met
+};
+
+static bool chain_tile_transposed(int tile_rows) {
+  return tile_rows == NUDF_CH_TILE_TQ || tile_rows == NUDF_CH_TILE_ROWS || tile_rows == NUDF_CH_TILE_PAIR;
+}
+
+// Check: 0, or the error (text set).  Dereferences nothing the descriptor points to.
+static int chain_check(const NudfChain& p, ChainFacts& f) {
   bool bad = p.n_steps > NUDF_CH_MAX_STEPS || (p.k0 & 3) || p.k0 > 288 || p.x_div < 1;
   // SEED (two sweeps in one launch) contracts nothing and exists in mlp_chain_kernel<TM, 2> only: checked on its own
-  bool fused = false;
+  f.fused = false;
   for (int i = 0; i < p.n_steps && !bad; ++i) {
     const NudfChainStep& s = p.step[i];
     if (s.epi == NUDF_CH_SEED) {
@@ -1625,7 +1638,7 @@ extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
         }
         bad = j == 0;
       }
-      fused = true;
+      f.fused = true;
       continue;
     }
     bad = (s.K & 15) || s.K <= 0 || s.K > 288 || s.N <= 0 || s.N > 256 || (((uintptr_t)s.Bp) & 15) ||
@@ -1635,30 +1648,22 @@ extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
           ((s.layout & NUDF_CH_P4_X1) && s.epi != NUDF_CH_MULMASK && s.epi != NUDF_CH_ADDMASK) ||
           ((s.layout & NUDF_CH_P4_C1) && s.epi != NUDF_CH_RELU && s.epi != NUDF_CH_MULMASK && s.epi != NUDF_CH_ADDMASK) ||
           ((s.layout & (NUDF_CH_P4_X1 | NUDF_CH_P4_C1)) && s.prec == 0) ||
-          (s.X3 && (s.epi != NUDF_CH_BWD || s.prec == 0 || !s.X2 || !s.X1 || p.tile_rows == 66 || p.tile_rows == 128 ||
-                    p.tile_rows == 130));
+          (s.X3 && (s.epi != NUDF_CH_BWD || s.prec == 0 || !s.X2 || !s.X1 || chain_tile_transposed(p.tile_rows)));
   }
-  if (bad) {
-    nudf_set_error("nudf_mlp_chain: K%16, K<=288, N<=256, x_div>=1, 16-byte aligned packed weights required; SEED behind the "
-                   "head of a forward sweep", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  bool any16 = false, any3 = false;
+  if (bad)
+    return nudf_refuse("nudf_mlp_chain: K%16, K<=288, N<=256, x_div>=1, 16-byte aligned packed weights required; SEED behind the "
+                        "head of a forward sweep");
+  f.any16 = f.any3 = false;
   for (int i = 0; i < p.n_steps; ++i) {
     if (p.step[i].epi == NUDF_CH_SEED) continue;     // (contracts nothing: no operand mode)
-    any3 = any3 || p.step[i].prec >= 3;        // the split modes (bf16x3, f16x2) share the MODE 2 instantiation
-    any16 = any16 || (p.step[i].prec != 0 && p.step[i].prec < 3) ||
-            (p.step[i].layout & (NUDF_CH_STATE16 | NUDF_CH_P4_X1 | NUDF_CH_P4_C1));
+    f.any3 = f.any3 || p.step[i].prec >= 3;
+    f.any16 = f.any16 || (p.step[i].prec != 0 && p.step[i].prec < 3) ||
+              (p.step[i].layout & (NUDF_CH_STATE16 | NUDF_CH_P4_X1 | NUDF_CH_P4_C1));
   }
-  if (fused && (!any3 || any16 || (p.tile_rows != 0 && p.tile_rows != 32 && p.tile_rows != 64))) {
-    nudf_set_error("nudf_mlp_chain: a SEED step needs a split-mode chain on the 32- / 64-point workgroup-shared tiles", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
-  if (any3 && any16) {
-    nudf_set_error("nudf_mlp_chain: split steps (prec 3 / 4) do not mix with 16-bit steps / 16-bit stored state", hipErrorInvalidValue);
-    return (int)hipErrorInvalidValue;
-  }
+  if (f.fused && (!f.any3 || f.any16 || (p.tile_rows != 0 && p.tile_rows != 32 && p.tile_rows != 64)))
+    return nudf_refuse("nudf_mlp_chain: a SEED step needs a split-mode chain on the 32- / 64-point workgroup-shared tiles");
+  if (f.any3 && f.any16)
+    return nudf_refuse("nudf_mlp_chain: split steps (prec 3 / 4) do not mix with 16-bit steps / 16-bit stored state");
   if (p.tile_scale || p.tile_amax_in || p.tile_amax_out) {      // include/nudf.h: NudfChain.tile_scale
     bool ok = true;      // (every step in a split mode: the launch runs on mlp_chain_kernel<TM, 2> whatever tile_rows asks for)
     if (p.tile_scale)
@@ -1671,81 +1676,91 @@ extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
              (s.epi == NUDF_CH_NONE || s.epi == NUDF_CH_MULSP || s.epi == NUDF_CH_TANGENT || s.epi == NUDF_CH_BWD ||
               s.epi == NUDF_CH_MULMASK || s.epi == NUDF_CH_ADDMASK);
     }
-    if (!ok) {
-      nudf_set_error("nudf_mlp_chain: tile_scale / tile_amax_* need a linear sweep in a split mode (INIT_LOAD or the JVP encoding; "
-                     "NONE / MULSP / TANGENT / BWD / MULMASK / ADDMASK steps of prec 3 / 4 without bias)", hipErrorInvalidValue);
-      return (int)hipErrorInvalidValue;
-    }
+    if (!ok)
+      return nudf_refuse("nudf_mlp_chain: tile_scale / tile_amax_* need a linear sweep in a split mode (INIT_LOAD or the JVP "
+                          "encoding; NONE / MULSP / TANGENT / BWD / MULMASK / ADDMASK steps of prec 3 / 4 without bias)");
   }
-  // Large launches: wave-private 32-point tiles (mlp_chain_rows.hip), one free-running wave per SIMD.  A "round" of
-  // that kernel is 1024 waves = 32 768 points, so it is chosen when the last round is at least ~80 % full; the
-  // up-sampling rounds (5-8 k points) and awkward sizes keep the workgroup-shared tiles below.
-  bool roww = false;
+  f.roww = false;
   for (int i = 0; i < p.n_steps; ++i) {
     const NudfChainStep& s = p.step[i];
     if (!s.row_w) continue;
-    roww = true;
-    if (s.epi != NUDF_CH_SIGMOIDN || !s.row_sums || p.tile_rows == 66 || p.tile_rows == 128 || p.tile_rows == 130) {
-      nudf_set_error("nudf_mlp_chain: row_w / row_sums belong to SIGMOIDN steps of the workgroup-shared kernel", hipErrorInvalidValue);
-      return (int)hipErrorInvalidValue;
-    }
+    f.roww = true;
+    if (s.epi != NUDF_CH_SIGMOIDN || !s.row_sums || chain_tile_transposed(p.tile_rows))
+      return nudf_refuse("nudf_mlp_chain: row_w / row_sums belong to SIGMOIDN steps of the workgroup-shared kernel");
   }
-  bool rows_ok = !roww && !fused && (p.tile_rows == 128 || p.tile_rows == 0);
-  if (rows_ok && p.tile_rows == 0) {
+  f.blocked = (p.init_state16 & 12) != 0;
+  for (int i = 0; i < p.n_steps; ++i) f.blocked = f.blocked || (p.step[i].layout & 31) != 0;
+  f.cls = nudf_chain_rows_class(p, f.blocked);
+  // only the transposed-product shared tile addresses the blocked layout
+  if (f.blocked && (f.cls < 0 || (p.tile_rows != NUDF_CH_TILE_TQ && p.tile_rows != NUDF_CH_TILE_PAIR && p.tile_rows != 0)))
+    return nudf_refuse("nudf_mlp_chain: blocked-layout buffers need the transposed-product kernel (tile_rows 0 / 66, fp32 "
+                        "steps, 16-byte aligned rows)");
+  return 0;
+}
+
+// Select: the table row of a checked descriptor -- a pure function of the descriptor, what the check learned and the settings.
+static int chain_select(const NudfChain& p, const ChainFacts& f, const ChainSettings& set) {
+  const int tile = p.tile_rows;
+  // the transposed-product shared tile, as paired tiles on request (tile_rows) or for large launches with NUDF_CHAIN_PAIR
+  auto tq = [&](bool pair) { return ((pair || (set.pair > 0 && p.P >= 32768)) ? CK_PAIR : CK_TQ) + f.cls; };
+  // Large launches: wave-private 32-point tiles (mlp_chain_rows.hip), one free-running wave per SIMD.  A "round" of
+  // that kernel is 1024 waves = 32 768 points, so it is chosen when the last round is at least ~80 % full; the
+  // up-sampling rounds (5-8 k points) and awkward sizes keep the workgroup-shared tiles below.
+  bool rows_ok = !f.roww && !f.fused && !f.blocked && (tile == NUDF_CH_TILE_ROWS || tile == 0);
+  if (rows_ok && tile == 0) {
     const long long round = 1024LL * 32, rounds = (p.P + round - 1) / round;
-    rows_ok = nudf_chain_rows_auto() && p.P >= 24576 && (double)p.P >= 0.8 * (double)(rounds * round);
+    rows_ok = set.rows_auto && p.P >= 24576 && (double)p.P >= 0.8 * (double)(rounds * round);
   }
-  if (rows_ok) {
-    const int cls = nudf_chain_rows_class(p);
-    if (cls >= 0) return nudf_mlp_chain_rows_launch(p, cls, st);
-    // contract of the wave-private kernel not met (16-bit operands, unaligned row buffers): workgroup-shared tiles
+  // (contract of the wave-private kernel not met -- 16-bit operands, unaligned row buffers: workgroup-shared tiles)
+  if (rows_ok && f.cls >= 0) return f.cls < 2 ? CK_ROWS + f.cls : set.win2 == 3 ? CK_ROWS_2_WIN3 : CK_ROWS_2_WIN2;
+  if (f.blocked) return tq(tile == NUDF_CH_TILE_PAIR);
+  if (f.cls >= 0) {
+    if (tile == NUDF_CH_TILE_PAIR) return tq(true);     // paired tiles requested explicitly (tests, A/B): any size
+    if (!f.roww && !f.fused && (tile == NUDF_CH_TILE_TQ || (tile == 0 && p.P > 256 * 64 && set.quad > 0)) &&
+        (tile == NUDF_CH_TILE_TQ || f.cls <= 1 || set.quad >= 2))
+      return tq(false);
+    // NUDF_CHAIN_PAIR=2: paired tiles for every fp32 launch of at least 32 768 points that meets that kernel's contract
+    if (!f.roww && tile == 0 && p.P >= 32768 && !f.any16 && !f.any3 && set.pair >= 2) return tq(false);
   }
-  bool blocked = (p.init_state16 & 12) != 0;
-  for (int i = 0; i < p.n_steps; ++i) blocked = blocked || (p.step[i].layout & 31) != 0;
-  if (blocked) {   // only the transposed-product shared tile addresses the blocked layout
-    const int cls = nudf_chain_rows_class(p, true);
-    if (cls < 0 || (p.tile_rows != 66 && p.tile_rows != 130 && p.tile_rows != 0)) {
-      nudf_set_error("nudf_mlp_chain: blocked-layout buffers need the transposed-product kernel (tile_rows 0 / 66, fp32 "
-                     "steps, 16-byte aligned rows)", hipErrorInvalidValue);
-      return (int)hipErrorInvalidValue;
-    }
-    return nudf_mlp_chain_tq_launch(p, cls, st, p.tile_rows == 130);
-  }
-  if (p.tile_rows == 130) {     // paired tiles requested explicitly (tests, A/B): any size
-    const int cls = nudf_chain_rows_class(p);
-    if (cls >= 0) return nudf_mlp_chain_tq_launch(p, cls, st, 1);
-  }
-  if (!roww && !fused && (p.tile_rows == 66 || (p.tile_rows == 0 && p.P > 256 * 64 && nudf_chain_quad_mode() > 0))) {
-    const int cls = nudf_chain_rows_class(p);
-    if (cls >= 0 && (p.tile_rows == 66 || cls <= 1 || nudf_chain_quad_mode() >= 2)) return nudf_mlp_chain_tq_launch(p, cls, st);
-  }
-  // NUDF_CHAIN_PAIR=2: paired tiles (mlp_chain_pair_kernel, reached through the transposed-product launcher) for every
-  // fp32 launch of at least 32 768 points that meets that kernel's contract -- a measured counter-example, off by default
-  if (!roww && p.tile_rows == 0 && p.P >= 32768 && !any16 && !any3 && nudf_chain_pair_mode() >= 2) {
-    const int cls = nudf_chain_rows_class(p);
-    if (cls >= 0) return nudf_mlp_chain_tq_launch(p, cls, st);
-  }
+  // small launches: 32-point tiles fill the 256 CUs sooner (up-sampling rounds are 5-8 k points)
+  const bool small = tile == 32 || (tile != 64 && p.P <= 256 * 64);
   // 16-bit mode, 64-point tiles: the 16-bit-TILE kernel (MODE 3) when every step contracts in the same 16-bit type (the
-  // tile holds ONE type): the UDF network's four sweeps with the 16-bit head, the colour / NeRF chains.  NUDF_CHAIN_T16=0
-  // keeps the fp32-tile kernel (A/B; the two are bit-identical).
-  bool t16 = any16 && !roww && nudf_chain_t16_enabled();
+  // tile holds ONE type): the UDF network's four sweeps with the 16-bit head, the colour / NeRF chains; MODE 4 has room for
+  // the three operands of a TANGENT step or an X3
+  bool t16 = f.any16 && !f.roww && !small && set.t16;
   bool t16_tangent = false;
   for (int i = 0; i < p.n_steps && t16; ++i) {
     t16 = (p.step[i].prec == 1 || p.step[i].prec == 2) && p.step[i].prec == p.step[0].prec;
-    t16_tangent = t16_tangent || p.step[i].epi == NUDF_CH_TANGENT || p.step[i].X3 != nullptr;   // (MODE 4: room for 3 operands)
+    t16_tangent = t16_tangent || p.step[i].epi == NUDF_CH_TANGENT || p.step[i].X3 != nullptr;
   }
-  // small launches: 32-point tiles fill the 256 CUs sooner (up-sampling rounds are 5-8 k points)
-  if (p.tile_rows == 32 || (p.tile_rows != 64 && p.P <= 256 * 64)) {
-    if (any3) hipLaunchKernelGGL((mlp_chain_kernel<32, 2>), dim3((p.P + 31) / 32), dim3(CH_THREADS), 0, st, p);
-    else if (any16) hipLaunchKernelGGL((mlp_chain_kernel<32, 1>), dim3((p.P + 31) / 32), dim3(CH_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((mlp_chain_kernel<32, 0>), dim3((p.P + 31) / 32), dim3(CH_THREADS), 0, st, p);
-  } else {
-    if (any3) hipLaunchKernelGGL((mlp_chain_kernel<64, 2>), dim3((p.P + 63) / 64), dim3(CH_THREADS), 0, st, p);
-    else if (t16 && t16_tangent) hipLaunchKernelGGL((mlp_chain_kernel<64, 4>), dim3((p.P + 63) / 64), dim3(CH_THREADS), 0, st, p);
-    else if (t16) hipLaunchKernelGGL((mlp_chain_kernel<64, 3>), dim3((p.P + 63) / 64), dim3(CH_THREADS), 0, st, p);
-    else if (any16) hipLaunchKernelGGL((mlp_chain_kernel<64, 1>), dim3((p.P + 63) / 64), dim3(CH_THREADS), 0, st, p);
-    else hipLaunchKernelGGL((mlp_chain_kernel<64, 0>), dim3((p.P + 63) / 64), dim3(CH_THREADS), 0, st, p);
-  }
+  if (small) return f.any3 ? CK_32_M2 : f.any16 ? CK_32_M1 : CK_32_M0;
+  return f.any3 ? CK_64_M2 : t16 ? (t16_tangent ? CK_64_M4 : CK_64_M3) : f.any16 ? CK_64_M1 : CK_64_M0;
+}
+
+// check + select; 0 with id < 0 for an empty launch
+static int chain_plan(const NudfChain& p, int& id) {
+  id = -1;
+  if (p.P <= 0 || p.n_steps <= 0) return 0;
+  ChainFacts f;
+  const int err = chain_check(p, f);
+  if (!err) id = chain_select(p, f, chain_settings());
+  return err;
+}
+
+extern "C" int nudf_mlp_chain_plan(const NudfChain* args, char* name, int capacity, int32_t* out) {
+  int id;
+  const int err = chain_plan(*args, id);
+  const ChainKernel* k = id >= 0 ? &chain_kernel(id) : nullptr;
+  nudf_report_kernel(name, capacity, out, k ? k->name : nullptr, k ? (args->P + k->points - 1) / k->points : 0, k ? k->threads : 0, 0);
+  return err;
+}
+
+extern "C" int nudf_mlp_chain(const NudfChain* args, void* stream) {
+  int id;
+  const int err = chain_plan(*args, id);
+  if (err || id < 0) return err;
+  const ChainKernel& k = chain_kernel(id);
+  k.launch(*args, (args->P + k.points - 1) / k.points, (hipStream_t)stream);
   NUDF_CHECK_LAUNCH("nudf_mlp_chain");
   return 0;
 }

@@ -1082,42 +1082,27 @@ __global__ __launch_bounds__(512, 2) void mlp_chain_pair_kernel(NudfChain p_arg)
   if (dbg && lane == 0) dbg[63] = wall_clock64();
 }
 
-// NUDF_CHAIN_PAIR: 0 (default) = independent 64-point workgroups; 1 = launches of at least 32 768 points that already go
-// to the transposed-product kernel (blocked state: the UDF sweeps) run as paired tiles; 2 = every fp32 launch of at least
-// 32 768 points that meets that kernel's contract does (colour / NeRF chains, coarse forward).  MEASURED (round 3,
-// profiles/r03_chain_pair.txt): not faster -- a K loop alone on the pipe next to the partner's epilogue reaches only 77 %
-// of the pipe rate (two in-phase K loops together 95 %), and the epilogue beside a K loop takes 1.8x as long; the
-// kernel stays as the measured counter-example to "enforce anti-phase".
-int nudf_chain_pair_mode() {
-  static const int mode = [] {
-    const char* e = getenv("NUDF_CHAIN_PAIR");
-    return e ? atoi(e) : 0;
-  }();
-  return mode;
-}
-
-int nudf_mlp_chain_tq_launch(const NudfChain& p, int cls, hipStream_t st, int force_pair) {
-  const dim3 grid((p.P + 63) / 64), block(256);
-  // forward sweeps (no stored-state operand): three register sets in the K loop, two k groups of operand reads in flight
-  // (tq_mma_ring; measured 629 -> 605 us at 65 536 points against two sets).
-  if (force_pair || (nudf_chain_pair_mode() > 0 && p.P >= 32768)) {   // paired tiles: tile_rows 130 / NUDF_CHAIN_PAIR
-    const dim3 pgrid((p.P + 127) / 128), pblock(512);
-    if (cls == 0) hipLaunchKernelGGL((mlp_chain_pair_kernel<0>), pgrid, pblock, 0, st, p);
-    else if (cls == 1) hipLaunchKernelGGL((mlp_chain_pair_kernel<1>), pgrid, pblock, 0, st, p);
-    else hipLaunchKernelGGL((mlp_chain_pair_kernel<2>), pgrid, pblock, 0, st, p);
-    NUDF_CHECK_LAUNCH("nudf_mlp_chain(pair)");
-    return 0;
-  }
-  if (cls == 0) hipLaunchKernelGGL((mlp_chain_tq_kernel<0, 3>), grid, block, 0, st, p);
-  // input-gradient sweeps: X1 streamed one tile ahead frees the registers for the third operand set (197 VGPRs, 646-652 ->
-  // 637 us at 65 536 points).  The tangent / adjoint instantiation gets SLOWER with a streamed X1, with two or three operand
-  // sets (tangent 675 -> 703 us, adjoint 692-750 -> 727-775: two more exposed operand requests per tile): it keeps the
-  // whole-step prefetch and two sets.
-  else if (cls == 1) hipLaunchKernelGGL((mlp_chain_tq_kernel<1, 3, true>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((mlp_chain_tq_kernel<2>), grid, block, 0, st, p);
-  NUDF_CHECK_LAUNCH("nudf_mlp_chain(tq)");
-  return 0;
-}
+// The rows of nudf_mlp_chain's kernel table (mlp_chain_shared.h: ChainKernelId CK_PAIR ...) that this file instantiates.
+static const ChainKernel g_tq_kernels[CK_COUNT - CK_PAIR] = {
+    CH_KERNEL(128, 512, mlp_chain_pair_kernel<0>),
+    CH_KERNEL(128, 512, mlp_chain_pair_kernel<1>),
+    CH_KERNEL(128, 512, mlp_chain_pair_kernel<2>),
+    // forward sweeps (no stored-state operand): three register sets in the K loop, two k groups of operand reads in flight
+    // (tq_mma_ring; measured 629 -> 605 us at 65 536 points against two sets).
+    CH_KERNEL(64, 256, mlp_chain_tq_kernel<0, 3>),
+    // input-gradient sweeps: X1 streamed one tile ahead frees the registers for the third operand set (197 VGPRs, 646-652 ->
+    // 637 us at 65 536 points).  The tangent / adjoint instantiation gets SLOWER with a streamed X1, with two or three operand
+    // sets (tangent 675 -> 703 us, adjoint 692-750 -> 727-775: two more exposed operand requests per tile): it keeps the
+    // whole-step prefetch and two sets.
+    CH_KERNEL(64, 256, mlp_chain_tq_kernel<1, 3, true>),
+    CH_KERNEL(64, 256, mlp_chain_tq_kernel<2>),
+    // one workgroup = 4 waves = 128 points; the second argument is the operand window (tiles in flight per stored-state operand)
+    CH_KERNEL(CHR_WAVES * CHR_ROWS, CHR_WAVES * 64, mlp_chain_rows_kernel<0, 4>),
+    CH_KERNEL(CHR_WAVES * CHR_ROWS, CHR_WAVES * 64, mlp_chain_rows_kernel<1, 4>),
+    CH_KERNEL(CHR_WAVES * CHR_ROWS, CHR_WAVES * 64, mlp_chain_rows_kernel<2, 3>),
+    CH_KERNEL(CHR_WAVES * CHR_ROWS, CHR_WAVES * 64, mlp_chain_rows_kernel<2, 2>),
+};
+const ChainKernel& nudf_chain_tq_kernel(int id) { return g_tq_kernels[id - CK_PAIR]; }
 
 // The launch-time contract above; also picks the operand class.  Returns -1 when the workgroup-shared kernel must run.
 int nudf_chain_rows_class(const NudfChain& p, bool allow_blocked) {
@@ -1145,21 +1130,4 @@ int nudf_chain_rows_class(const NudfChain& p, bool allow_blocked) {
     if (s.r1_row && ((e != NUDF_CH_BWD && e != NUDF_CH_MULMASK) || !s.r1_col)) return -1;
   }
   return cls;
-}
-
-// launch (argument checks are done by nudf_mlp_chain): one workgroup = 4 waves = 128 points
-int nudf_mlp_chain_rows_launch(const NudfChain& p, int cls, hipStream_t st) {
-  const dim3 grid((p.P + CHR_WAVES * CHR_ROWS - 1) / (CHR_WAVES * CHR_ROWS)), block(CHR_WAVES * 64);
-  // operand window (tiles in flight per stored-state operand): 4 with one operand; 2 with two operands (3 makes the
-  // register allocator spill ~100 values per step; NUDF_CHAIN_WIN2=3 selects that build for measurements)
-  static const int win2 = [] {
-    const char* e = getenv("NUDF_CHAIN_WIN2");
-    return (e && e[0] == '3') ? 3 : 2;
-  }();
-  if (cls == 0) hipLaunchKernelGGL((mlp_chain_rows_kernel<0, 4>), grid, block, 0, st, p);
-  else if (cls == 1) hipLaunchKernelGGL((mlp_chain_rows_kernel<1, 4>), grid, block, 0, st, p);
-  else if (win2 == 3) hipLaunchKernelGGL((mlp_chain_rows_kernel<2, 3>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((mlp_chain_rows_kernel<2, 2>), grid, block, 0, st, p);
-  NUDF_CHECK_LAUNCH("nudf_mlp_chain(rows)");
-  return 0;
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #define NUDF_WAVE 64
 
@@ -19,6 +20,18 @@ extern "C" int32_t* nudf_status_flag(void);     // nudf_api.hip: the caller's no
       return (int)_e;                                    \
     }                                                    \
   } while (0)
+
+// a launcher's refusal of its arguments: the text for nudf_last_error, the value to return
+static inline int nudf_refuse(const char* why) {
+  nudf_set_error(why, hipErrorInvalidValue);
+  return (int)hipErrorInvalidValue;
+}
+// what the host-only dispatch reports (nudf_mlp_chain_plan, nudf_gemm_tn_grouped_kernel) hand back; kernel == NULL: none
+static inline void nudf_report_kernel(char* name, int capacity, int32_t* out, const char* kernel, int grid, int threads,
+                                      int reduce_grid) {
+  if (name && capacity > 0) snprintf(name, capacity, "%s", kernel ? kernel : "");
+  if (out) out[0] = kernel ? grid : 0, out[1] = kernel ? threads : 0, out[2] = kernel ? reduce_grid : 0, out[3] = 0;
+}
 
 // ---- wave-level scans (64 lanes) on DPP -------------------------------------------------------------
 // Cross-lane steps are DPP modifiers of the VALU op itself (row_shr within the 16-lane rows, then row_bcast:15 /

@@ -272,7 +272,6 @@ class ChainBuilder:
         self.xflops = 0.0
         self.nbytes = 0.0          # algorithmic HBM bytes: every stored-state operand / output of every step, once
         self.epis = []
-        self.blocked = False
         self.keep = []
 
     # ---- recording front end -------------------------------------------------------------------------------------------
@@ -467,7 +466,6 @@ class ChainBuilder:
                 if t is not None:
                     self.nbytes += float(self.c.P) * (min(n_true, t.shape[1]) if t.dim() == 2 else 1) * t.element_size()
             self.epis.append(epi)
-            self.blocked = self.blocked or (s.layout & 31) != 0
 
     def launch(self):
         global chain_memo_hits
@@ -512,44 +510,14 @@ class ChainBuilder:
         self.keep = []
 
     def _label(self):
-        """kernel instantiation nudf_mlp_chain dispatches this launch to (mirrors csrc/mlp_chain.hip) + the sweep."""
-        P, e = self.c.P, set(self.epis)
-        x1 = bool(e & {"MULSP", "TANGENT", "BWD", "MULMASK", "ADDMASK"})
-        x2 = bool(e & {"TANGENT", "BWD", "ADDMASK", "RELUADD"})
-        pair = int(os.environ.get("NUDF_CHAIN_PAIR", "0"))
-        if self.c.tile_rows == 130 or ((self.blocked or self.c.tile_rows == 66) and pair >= 1 and P >= 32768):
-            kern = "mlp_chain_pair_kernel<%d>" % (2 if x2 else (1 if x1 else 0))
-        elif self.c.tile_rows == 0 and pair >= 2 and P >= 32768 and PRECISION == "fp32":
-            kern = "mlp_chain_pair_kernel<%d>" % (2 if x2 else (1 if x1 else 0))
-        elif self.blocked or self.c.tile_rows == 66:
-            kern = "mlp_chain_tq_kernel<%d>" % (2 if x2 else (1 if x1 else 0))
-        elif self.c.tile_rows == 128:
-            kern = "mlp_chain_rows_kernel"
-        else:
-            mode = {"fp32": 0, "mixed16": 1, "bf16x3": 2}[PRECISION]
-            t32 = self.c.tile_rows == 32 or (self.c.tile_rows != 64 and P <= 256 * 64)
-            roww = any(self.c.step[i].row_w for i in range(self.n))
-            if mode == 1 and not t32 and not roww and _chain_t16_now():
-                precs = {int(self.c.step[i].prec) for i in range(self.n)}
-                if len(precs) == 1 and precs <= {1, 2}:
-                    x3 = any(self.c.step[i].X3 for i in range(self.n))
-                    mode = 4 if ("TANGENT" in e or x3) else 3      # the 16-bit-tile kernel (one operand type in every step)
-            kern = "mlp_chain_kernel<%d, %d>" % (32 if t32 else 64, mode)
+        """kernel instantiation nudf_mlp_chain dispatches this launch to (the library's own report) + the sweep."""
+        e = set(self.epis)
         sweep = ("udf-forward+input-gradient" if "SEED" in e
                  else "tangent" if ("TANGENT" in e or ("MULSP" in e and self.init == "POSENC")) else "adjoint" if "BWD" in e
                  else "input-gradient" if "MULSP" in e
                  else "relu-backward" if e & {"MULMASK", "ADDMASK"} else "udf-forward" if "SOFTPLUS" in e
                  else "relu-forward")
-        return "%s %s P=%d" % (kern, sweep, P)
-
-
-def _chain_t16_now():
-    """the library's CURRENT 16-bit-tile setting (env NUDF_CHAIN_T16 at load, nudf_set_chain_t16 afterwards): the setter
-    returns the old value, so set-and-restore reads it (host side only; used by the profiling labels)"""
-    L = _lib.lib()
-    old = int(L.nudf_set_chain_t16(1))
-    L.nudf_set_chain_t16(old)
-    return bool(old)
+        return "%s %s P=%d" % (_lib.kernel_of("nudf_mlp_chain_plan", self.c)[0], sweep, self.c.P)
 
 
 # scratch of the weight-gradient GEMMs' deterministic two-pass reduction (every workgroup's partial tile, ~33 MB at the
@@ -607,7 +575,7 @@ def gemm_tn_grouped(jobs, M, assign=False, rows_per_block=0, f16x2=False, amax_a
         g.assign = 1 if assign else 0
         if PROFILE is not None:
             _timed("gemm_tn", flops, lambda: call("nudf_gemm_tn_grouped", g),
-                   "gemm_tn%s_group_kernel %d problems M=%d (%.1f GFLOP)" % ({3: "3", 4: "2"}.get(int(g.prec), ""), len(chunk), M, flops / 1e9),
+                   "%s %d problems M=%d (%.1f GFLOP)" % (_lib.kernel_of("nudf_gemm_tn_grouped_kernel", g)[0], len(chunk), M, flops / 1e9),
                    nbytes, flops * MFMA_PRODUCTS.get(int(g.prec), 1) if (int(g.prec) != 3 or TN_SPLIT) else flops)
         else:
             call("nudf_gemm_tn_grouped", g)

@@ -63,6 +63,34 @@ def test_rows_kernel_is_the_one_that_ran(dev):
     assert float((a["feat"] - b["feat"]).abs().max()) < 2e-5 * float(a["feat"].abs().max())
 
 
+@pytest.mark.parametrize("precision,tile,kernel", [
+    ("fp32", 0, "mlp_chain_kernel<32, 0>"),
+    ("fp32", 128, "mlp_chain_rows_kernel<0, 4>"),
+    ("fp32", 66, "mlp_chain_tq_kernel<0, 3>"),
+    ("bf16x3", 128, "mlp_chain_kernel<32, 2>"),        # split steps do not meet the wave-private kernel's contract: 32-point tiles
+])
+def test_profile_label_names_the_kernel_the_library_chose(dev, precision, tile, kernel):
+    """the profiler label of a chain launch is the library's own report of its selection (nudf_mlp_chain_plan), fall-backs
+    included"""
+    import os
+    from chain_sweeps import engines
+    from neuraludf_amd import mlp
+    if any(v in os.environ for v in ("NUDF_CHAIN_ROWS", "NUDF_CHAIN_QUAD", "NUDF_CHAIN_PAIR", "NUDF_CHAIN_T16", "NUDF_CHAIN_WIN2")):
+        pytest.skip("a NUDF_CHAIN_* setting is in force: the kernels named here are the default selection")
+    eng = engines(dev)["eng"]
+    mlp.set_precision(precision)
+    x = (torch.rand(256, 3, generator=torch.Generator().manual_seed(1)) * 2 - 1).to(dev)
+    old_tile, mlp.CHAIN_TILE = mlp.CHAIN_TILE, tile
+    mlp.PROFILE = []
+    try:
+        eng.forward(x, need_grad_state=False, udf_only=True)
+        torch.cuda.synchronize()
+        labels = [r[4] for r in mlp.PROFILE if r[0] == "mlp_chain"]
+    finally:
+        mlp.PROFILE, mlp.CHAIN_TILE = None, old_tile
+    assert labels and all(s.startswith(kernel + " udf-forward P=256") for s in labels), labels
+
+
 # ---- the workgroup-shared 64-point tile with the transposed product (tile_rows = 66, mlp_chain_tq_kernel) ---------------
 @pytest.mark.parametrize("P", [1, 63, 65, 129, 1000, 4133])
 def test_tq_kernel_matches_shared_kernel_ragged_sizes(dev, P):
