@@ -196,8 +196,8 @@ def gemm_tn(A1, na1, B1, C, NA, NB, M, dbias=None, A2=None, na2=0, B2=None):
     for t in (A1, B1, A2, B2):
         if t is not None and (_is16(t) or _isblk(t)):
             raise _lib.NudfError("gemm_tn: bf16-stored / blocked-layout operands need gemm_tn_grouped (per-problem "
-                                 "NUDF_TN_A16 / _B16 / _A_BLK / _B_BLK flags); set NUDF_STATE16=0 / NUDF_BLOCKED_STATE=0 "
-                                 "with NUDF_UDF_TN_GROUPED=0")
+                                 "NUDF_TN_A16 / _B16 / _A_BLK / _B_BLK flags): the per-layer path (USE_CHAIN = False) "
+                                 "stores row-major fp32 state")
     a = GemmTN()
     a.A1, a.lda1, a.na1 = ptr(A1), A1.shape[1], na1
     a.B1, a.ldb1 = ptr(B1), B1.shape[1]
@@ -220,8 +220,6 @@ def gemm_tn(A1, na1, B1, C, NA, NB, M, dbias=None, A2=None, na2=0, B2=None):
 USE_CHAIN = os.environ.get("NUDF_CHAIN", "1") != "0"     # 0: per-layer GEMM launches (A/B measurements, cross-checks)
 CHAIN_DEBUG = None     # int64 tensor [blocks * 4, 32]: per-wave timeline written by the kernel (scripts/chain_timeline.py)
 CHAIN_TILE = int(os.environ.get("NUDF_CHAIN_TILE", "0"))  # 0 = auto, 32 / 64 force the points-per-workgroup tile
-# the colour net's three chains alone ("" = as CHAIN_TILE; A/B switch: its 128-wide layers behave differently from the UDF net's)
-COLOR_TILE = int(os.environ.get("NUDF_COLOR_TILE", "0"))
 
 
 def k8(n: int) -> int:
@@ -242,15 +240,6 @@ _PLAIN_TYPES = frozenset((int, float, str, bool, type(None)))
 _CHAIN_MEMO = {}
 CHAIN_MEMO = os.environ.get("NUDF_CHAIN_MEMO", "1") != "0" and _lib.HOST_FAST
 chain_memo_hits = 0
-
-
-def _memo_token(engine):
-    """identity of a call site's owner in the descriptor memo: an object the engine owns (id() of a collected engine could be
-    reused by another one while its entries are still in the memo; an object held by the key cannot)"""
-    t = engine.__dict__.get("_site_token")
-    if t is None:
-        t = engine.__dict__["_site_token"] = object()
-    return t
 
 
 class ChainBuilder:
@@ -312,7 +301,7 @@ class ChainBuilder:
         """-> (structure, pointers): the record with every tensor replaced by its element count, and the tensors' addresses
         in record order; (None, None) if a tensor is not a contiguous device tensor (the filling path raises the error)."""
         T, PT, plain = torch.Tensor, torch.nn.Parameter, _PLAIN_TYPES
-        sig = [self.P, self.init, self.k0, self.tile_rows, PRECISION, FWD_F16X2, BWD_F16X2, HEAD16, STATE16, BLOCKED_STATE, TN_SPLIT]
+        sig = [self.P, self.init, self.k0, self.tile_rows, PRECISION, FWD_F16X2, BWD_F16X2, HEAD16]
         ptrs = []
         add, addp = sig.append, ptrs.append
         for kind, a, kw in self.rec:
@@ -538,11 +527,12 @@ def _tn_workspace(g, dev):
 
 
 TN_ASSIGN = os.environ.get("NUDF_TN_ASSIGN", "1") == "1"     # A/B + tests: 0 = zero-filled gradient buffers, accumulate
+_TN_ATOMIC = bool(int(os.environ.get("NUDF_TN_FLAGS", "0")) & 8)     # (the library reads the same variable, once as well)
 
 
 def tn_can_assign():
     """the weight-gradient launches can ASSIGN their outputs (two-pass deterministic reduction; not the atomic A/B path)"""
-    return TN_ASSIGN and TN_DETERMINISTIC and not (int(os.environ.get("NUDF_TN_FLAGS", "0")) & 8)
+    return TN_ASSIGN and TN_DETERMINISTIC and not _TN_ATOMIC
 
 
 def gemm_tn_grouped(jobs, M, assign=False, rows_per_block=0, f16x2=False, amax_a=None, amax_b=None):
@@ -576,7 +566,7 @@ def gemm_tn_grouped(jobs, M, assign=False, rows_per_block=0, f16x2=False, amax_a
         if PROFILE is not None:
             _timed("gemm_tn", flops, lambda: call("nudf_gemm_tn_grouped", g),
                    "%s %d problems M=%d (%.1f GFLOP)" % (_lib.kernel_of("nudf_gemm_tn_grouped_kernel", g)[0], len(chunk), M, flops / 1e9),
-                   nbytes, flops * MFMA_PRODUCTS.get(int(g.prec), 1) if (int(g.prec) != 3 or TN_SPLIT) else flops)
+                   nbytes, flops * MFMA_PRODUCTS.get(int(g.prec), 1))
         else:
             call("nudf_gemm_tn_grouped", g)
 
@@ -618,29 +608,6 @@ class PackedLinear:
             self._frags = {}
             if self._perm_list is not None:
                 self.perm = torch.tensor(self._perm_list, dtype=torch.int32, device=dev)
-
-    def pack(self):
-        """(re)pack if the parameters changed; returns self."""
-        ps = self.params()
-        v = ps[0]
-        ver = tuple((p.data_ptr(), p._version) for p in ps[:-1])
-        if ver == self._ver and self.W is not None and self.W.device == v.device:
-            return self
-        dev = v.device
-        if self.W is None or self.W.device != dev:
-            self.W = torch.zeros(self.out_pad, self.in_pad, device=dev)
-            self.Wt = torch.zeros(self.in_pad, self.out_pad, device=dev)
-            self.inv_norm = torch.empty(self.out, device=dev)
-            self.Wt.k_true, self.W.k_true = self.inp, self.out      # unpadded reduction lengths (flop accounting)
-            if self._perm_list is not None:
-                self.perm = torch.tensor(self._perm_list, dtype=torch.int32, device=dev)
-        g = ps[1] if self.weight_norm else None
-        call("nudf_weightnorm_pack", ptr(v.detach().contiguous()), ptr(g.detach().contiguous()) if g is not None else None,
-             self.out, self.inp, ptr(self.perm), ptr(self.W), self.in_pad, ptr(self.Wt), self.out_pad,
-             ptr(self.inv_norm))
-        self._ver = ver
-        self._frags = {}
-        return self
 
     def invalidate(self):
         """forget the packed weights.  The cache is keyed on the parameters' (data_ptr, _version); in-place writes
@@ -686,21 +653,6 @@ class PackedLinear:
         dev = self.W.device
         return torch.zeros(self.out_pad, self.in_pad, device=dev), torch.zeros(self.out, device=dev)
 
-    def unpack_grads(self, dW, db):
-        """packed dW/db -> gradients in params() order."""
-        ps = self.params()
-        v = ps[0].detach().contiguous()
-        dv = torch.empty_like(v)
-        if self.weight_norm:
-            g = ps[1].detach().contiguous()
-            dg = torch.empty_like(g)
-            call("nudf_weightnorm_unpack_grad", ptr(dW), self.in_pad, ptr(v), ptr(g), ptr(self.inv_norm), self.out,
-                 self.inp, ptr(self.perm), ptr(dv), ptr(dg))
-            return [dv, dg, db]
-        call("nudf_weightnorm_unpack_grad", ptr(dW), self.in_pad, ptr(v), None, None, self.out, self.inp,
-             ptr(self.perm), ptr(dv), None)
-        return [dv, db]
-
 
 # MFMA operand precision of the fused chains.  "fp32" is the exact fp32 MFMA path (v_mfma_f32_32x32x2_f32).  "mixed16" is
 # BASELINE config 5 (16-bit MLP weights on the CDNA4 matrix cores): fp16 operands in the forward sweeps (value,
@@ -735,9 +687,11 @@ BWD_F16X2 = os.environ.get("NUDF_BWD_F16X2", "1") != "0"
 EX_FLY = os.environ.get("NUDF_EX_FLY", "1") != "0"
 # bf16x3 mode: the weight-gradient GEMMs of the UDF and colour networks on THREE fp16 products (NudfGemmTNGroup.prec 4,
 # gemm_tn2_group_kernel) -- the side of every problem that holds loss adjoints is scaled by a power of two taken from the
-# maximum the producing sweeps report (NudfChain.absmax_out), the activation side is used as it is.  0 = bf16x3 GEMMs (A/B).
-TN_F16X2 = os.environ.get("NUDF_TN_F16X2", "1") != "0"
-TN_SPLIT = os.environ.get("NUDF_TN_SPLIT", "1") != "0"      # bf16x3 mode: the weight-gradient GEMMs take split operands too
+# maximum the producing sweeps report (NudfChain.absmax_out), the activation side is used as it is.
+# Settled, no longer switches: bench.py and the tests report them as what the arithmetic is.
+TN_F16X2 = True
+TN_SPLIT = True           # bf16x3 mode: the weight-gradient GEMMs take split operands too
+BLOCKED_STATE = True      # fp32 mode, large launches: saved state in the blocked layout (`_state_blocked`)
 
 
 # The UDF value sweep and the input-gradient sweep that follows it over the same points as ONE launch (bf16x3 mode,
@@ -755,21 +709,23 @@ def set_fuse_sweeps(on):
     return old
 
 
+def _shared_split(state=None, mixed16=False):
+    """will a chain launch over the saved state `state` run on the workgroup-shared split-mode kernel (mlp_chain_kernel<TM, 2>)?
+    bf16x3 mode (mixed16 = True: the 16-bit mode's launches count as well), the automatic or a forced 32 / 64 point tile, and
+    row-major state -- the blocked layout belongs to the fp32 transposed-product kernel."""
+    return (PRECISION != "fp32" if mixed16 else PRECISION == "bf16x3") and CHAIN_TILE in (0, 32, 64) and not _isblk(state)
+
+
 def _fuse():
-    return FUSE_SWEEPS and PRECISION == "bf16x3" and CHAIN_TILE in (0, 32, 64)
+    return FUSE_SWEEPS and _shared_split()
 
 
 def _tn_prec():
     if PRECISION == "fp32":
         return 0
-    if PRECISION == "bf16x3":
-        return 3 if TN_SPLIT else 0
-    return 2
+    return 3 if PRECISION == "bf16x3" else 2
 
 
-# 16-bit mode: the UDF engine's saved-for-backward arrays (X, DA, R, EX, ABAR) are stored as bf16 -- half the HBM
-# traffic of the sweeps and of the weight-gradient GEMMs that read them.  STATE16 = False keeps them fp32 (A-B).
-STATE16 = os.environ.get("NUDF_STATE16", "1") != "0"
 # 16-bit mode: the abs-head column (K = 256, N = 1) contracts in fp16 like every other step of the forward sweep, so that the
 # whole sweep has ONE operand type and runs on the 16-bit-TILE chain kernel (mlp_chain_kernel<64, 3>: the LDS activation tile IS
 # the fp16 operand, three workgroups per CU).  The activations the head sees are the fp16-rounded ones every hidden layer sees;
@@ -782,20 +738,18 @@ def _head_kind():
     return "fwd_head0@f16" if (PRECISION == "mixed16" and HEAD16) else "fwd_head0"
 
 
-# fp32 mode, large launches: the UDF engine's saved state in the BLOCKED layout + the transposed-product chain kernel
-# (1 KB of contiguous memory per wave instruction in the epilogues, 16 KB contiguous operand tiles in the weight-gradient
-# GEMM).  NUDF_BLOCKED_STATE=0 keeps row-major buffers and the default kernel (A-B).
-BLOCKED_STATE = os.environ.get("NUDF_BLOCKED_STATE", "1") != "0"
-
-
 def _state_blocked(P):
+    """fp32 mode, large launches: the UDF engine's saved state in the BLOCKED layout + the transposed-product chain kernel
+    (1 KB of contiguous memory per wave instruction in the epilogues, 16 KB contiguous operand tiles in the weight-gradient GEMM)."""
     # (bf16x3: measured with the split K loop ported into the transposed-product kernel -- chains 2.752 vs 2.758 ms, and the
     # weight-gradient GEMM loses its split-image kernel on blocked operands, 1.14 -> 2.09 ms: row-major state there)
-    return BLOCKED_STATE and PRECISION == "fp32" and USE_CHAIN and CHAIN_TILE in (0, 66, 130) and P > 256 * 64
+    return PRECISION == "fp32" and USE_CHAIN and CHAIN_TILE in (0, 66, 130) and P > 256 * 64
 
 
 def _state_dtype():
-    return torch.bfloat16 if (PRECISION == "mixed16" and STATE16) else torch.float32
+    """16-bit mode: the UDF engine's saved-for-backward arrays (X, DA, R, EX, ABAR) and the colour net's hidden layers are
+    stored as bf16 -- half the HBM traffic of the sweeps and of the weight-gradient GEMMs that read them."""
+    return torch.bfloat16 if PRECISION == "mixed16" else torch.float32
 
 
 def set_precision(name):
@@ -1066,13 +1020,86 @@ def unpack_group(layers, grads, slot=None):
     return [t for lay in out_per_layer for t in lay]
 
 
+def _tn_jobs(specs, layers, grads, bias=True):
+    """[(D, X, layer index[, first row, end row])] -> the job tuples of `gemm_tn_grouped`: dW (and db) of that layer, or of
+    the given rows of it, from the adjoint D and the layer input X"""
+    jobs = []
+    for D, X, i, *rows in specs:
+        pl, (dW, db) = layers[i], grads[i]
+        r0, r1 = rows or (0, pl.out)
+        if rows:
+            dW, db = dW[r0:r1], db[r0:r1]
+        jobs.append((D, r1 - r0, X, pl.in_pad, dW, db if bias else None))
+    return jobs
+
+
+class Engine:
+    """What the engines of the three networks share: the life cycle of the packed weights, the fragment kinds per operand
+    mode, the call-site keys of the chain-descriptor memo and the tail of a chain backward.  A subclass names its
+    PackedLinears in `_all()` and the fragment copies its sweeps read in `_frag_kinds_build()`."""
+
+    def __init__(self, net):
+        self.net = net
+        self._kinds_cache = {}
+        # identity of this engine's call sites in the descriptor memo: an object the engine owns (id() of a collected engine
+        # could be reused by another one while its entries are still in the memo; an object held by the key cannot)
+        self._site_token = object()
+
+    def _all(self):
+        """the engine's PackedLinears in the registration order of the nn.Module (the order of params() and of the gradients)"""
+        return self.layers
+
+    def params(self):
+        out = []
+        for pl in self._all():
+            out += pl.params()
+        return out
+
+    def invalidate(self):
+        for pl in self._all():
+            pl.invalidate()
+
+    def mark_stale(self):
+        """re-pack the weights at the next use, keeping the buffers (train.GraphedStep: the pack launch must be part of
+        the captured step even when a forward-only render packed the current weights just before the capture)."""
+        for pl in self._all():
+            pl._ver = None
+
+    def _frag_kinds(self):
+        """fragment-ordered weight copies each layer needs for the engine's sweeps, in its pack_group order (cached per
+        operand mode)."""
+        k = self._kinds_cache.get(_mode_key())
+        if k is None:
+            k = self._kinds_cache[_mode_key()] = tuple(tuple(dict.fromkeys(ks)) for ks in self._frag_kinds_build())
+        return k
+
+    def _site(self, name):
+        return (name, self._site_token)
+
+    def backward(self, st, *adjoints):
+        """through the path that made the saved state `st`"""
+        return (self._backward_chain if "chain" in st else self._backward_layers)(st, *adjoints)
+
+    def _weight_grads(self, P, first, second=(), f16x2=False, amax_a=None, amax_b=None):
+        """tail of a chain backward: every weight gradient in one grouped GEMM over the `_tn_jobs` specs `first` (with the
+        bias sums; it ASSIGNS where it can, so the buffer is then not filled), a second one over `second` accumulating into the
+        same dW, and the unpack into parameter gradients -> gradients in params() order.
+        f16x2: amax_a / amax_b = the maximum of the adjoint side of `first` / of `second` (`gemm_tn_grouped`)."""
+        layers = self._all()
+        assign = tn_can_assign()
+        grads = alloc_grads(layers, zero=not assign)
+        gemm_tn_grouped(_tn_jobs(first, layers, grads), P, assign=assign, f16x2=f16x2, amax_a=amax_a)
+        if second:
+            gemm_tn_grouped(_tn_jobs(second, layers, grads, bias=False), P, f16x2=f16x2, amax_b=amax_b)
+        return unpack_group(layers, grads, claim_grad_slot(self, layers))
+
 
 # =========================================================================================
 # UDF network
 # =========================================================================================
-class UDFEngine:
+class UDFEngine(Engine):
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.L = net.num_layers - 2                     # index of the last linear layer
         self.E = net.embed_dim
         self.layers = [PackedLinear(getattr(net, f"lin{l}")) for l in range(self.L + 1)]
@@ -1081,22 +1108,6 @@ class UDFEngine:
         # udf_out (fields.py:184-190): the head kernels store f(h0) / scale and the multiplier f'(h0) ("sign" below: sign h0,
         # 2 h0 or 1) that every sweep behind the head uses
         self.head_type = {"abs": 0, "square": 1, "sdf": 2}[getattr(net, "udf_type", "abs")]
-
-    def params(self):
-        out = []
-        for pl in self.layers:
-            out += pl.params()
-        return out
-
-    def invalidate(self):
-        for pl in self.layers:
-            pl.invalidate()
-
-    def mark_stale(self):
-        """re-pack the weights at the next use, keeping the buffers (train.GraphedStep: the pack launch must be part of
-        the captured step even when a forward-only render packed the current weights just before the capture)."""
-        for pl in self.layers:
-            pl._ver = None
 
     def _embed(self, x, P, X, tangent=None):
         net = self.net
@@ -1146,14 +1157,6 @@ class UDFEngine:
             return self._backward_chain(x, st, DA, d_udf, d_feat, d_feat_ld, d_g)
         return self._backward_layers(x, st, DA, d_udf, d_feat, d_feat_ld, d_g)
 
-    def _frag_kinds(self):
-        """fragment-ordered weight copies each layer needs for the four sweeps (cached per operand mode)."""
-        kc = self.__dict__.setdefault("_kinds_cache", {})
-        k = kc.get(_mode_key())
-        if k is None:
-            k = kc[_mode_key()] = tuple(tuple(dict.fromkeys(ks)) for ks in self._frag_kinds_build())
-        return k
-
     def _frag_kinds_build(self):
         kinds = []
         for l, pl in enumerate(self.layers):
@@ -1187,7 +1190,7 @@ class UDFEngine:
         blk = _state_blocked(P)
         X = ([_buf(P, self.layers[0].inp, dev, zero=False)] +
              [_buf(P, pl.inp, dev, zero=False, dtype=sd, blocked=blk) for pl in self.layers[1:]]) if need_grad_state else None
-        cb = ChainBuilder(P, "POSENC", k8(self.E), site=("udf_fwd_grad" if with_grad else "udf_fwd", _memo_token(self)))
+        cb = ChainBuilder(P, "POSENC", k8(self.E), site=self._site("udf_fwd_grad" if with_grad else "udf_fwd"))
         cb.posenc(x, net.multires, float(net.scale))
         if need_grad_state:
             cb.init_store(X[0])
@@ -1270,7 +1273,7 @@ class UDFEngine:
         net = self.net
         DA = self._gradient_buffers(P, X, dev)
         plL = self.layers[L]
-        cb = ChainBuilder(P, "SEED", k8(self.layers[L - 1].out), site=("udf_grad", _memo_token(self)))
+        cb = ChainBuilder(P, "SEED", k8(self.layers[L - 1].out), site=self._site("udf_grad"))
         cb.init_seed(X[L], X[L].shape[1], st["sign"], plL.W, 1.0 / float(net.scale), self._xs(L - 1))
         cb.init_store(DA[L - 1])
         demb0, demb_skip = self._gradient_steps(cb, P, X, DA, dev)
@@ -1283,20 +1286,15 @@ class UDFEngine:
         X, sign = st["X"], st["sign"]
         layers = self.layers
         net = self.net
-        grouped = os.environ.get("NUDF_UDF_TN_GROUPED", "1") == "1"      # A/B switches (profiling)
-        head4_path = grouped and os.environ.get("NUDF_UDF_HEAD4", "1") == "1"
-        assign = head4_path and tn_can_assign()       # the first grouped launch writes every gradient element: no fill
-        grads = alloc_grads(layers, zero=not assign)
         second = d_g is not None and DA is not None
         R = EX = None
         # EX_FLY: the second-order term EX[l] = (R[l] W^T) * DA[l] * softplus'' / softplus' is not stored by the tangent sweep
         # and re-read by the adjoint sweep -- the adjoint sweep forms it from R[l + 1] and DA[l], arrays that exist anyway
         # (NudfChainStep.X3).  The tangent sweep is then MULSP steps: one array in (X), one out (R) per layer instead of
         # two and two.  Split / 16-bit modes on the workgroup-shared kernel (the fp32 kernels keep the stored form).
-        ex_fly = second and EX_FLY and PRECISION != "fp32" and not _isblk(X[L]) and CHAIN_TILE in (0, 32, 64)
+        ex_fly = second and EX_FLY and _shared_split(X[L], mixed16=True)
         # f16x2 weight-gradient GEMMs: [max |adjoint-sweep arrays|, max |tangent-sweep arrays|], raised by the two sweeps
-        tn2 = (TN_F16X2 and PRECISION == "bf16x3" and TN_SPLIT and grouped and head4_path and not _isblk(X[L]) and not _is16(X[L])
-               and CHAIN_TILE in (0, 32, 64))
+        tn2 = _shared_split(X[L]) and not _is16(X[L])
         amax = torch.zeros(2, device=dev) if tn2 else None
         # f16x2 backward sweeps: per-tile scaling; the tangent sweep's per-tile maxima bound what its R arrays add to the adjoint
         bsc = _sweep_dtype("bwd") == "f16x2"
@@ -1306,7 +1304,7 @@ class UDFEngine:
             R = ([_buf(P, layers[0].inp, dev, zero=False)] +
                  [_buf(P, pl.inp, dev, zero=False, dtype=sd, blocked=blk) for pl in layers[1:]])
             EX = None if ex_fly else [_buf(P, layers[l].out, dev, zero=False, dtype=sd, blocked=blk) for l in range(L)]
-            cb = ChainBuilder(P, "POSENC", k8(self.E), site=("udf_tangent", _memo_token(self)))
+            cb = ChainBuilder(P, "POSENC", k8(self.E), site=self._site("udf_tangent"))
             cb.posenc(x, net.multires, float(net.scale), tangent=d_g.contiguous())
             cb.init_store(R[0])
             if tn2:
@@ -1329,34 +1327,23 @@ class UDFEngine:
                             pe_dst=R[l + 1] if nxt_skip else None)
             cb.launch()
         inv_scale = 1.0 / float(net.scale)
-        if second and not head4_path:
-            call("nudf_signed_colsum", ptr(sign), ptr(R[L]), R[L].shape[1], P, layers[L].inp, inv_scale, ptr(grads[L][0]))
         plL = layers[L]
         F = plL.out - 1
-        ABAR = [None] * (L + 1)
-        if head4_path:
-            # the head's adjoint is [sign * d udf / scale | d feat]: d feat is used where it lies (tile load, GEMM operand)
-            # and column 0 travels as a 4-wide operand -- no [P, 257] copy (52 us), no separate column-sum kernel (36 us)
-            head4 = torch.empty(pad_rows(P), 4, device=dev)
-            # (the second-order weight gradient's operand sign / scale comes out of the same launch)
-            sg4 = torch.empty(pad_rows(P), 4, device=dev) if second else None
-            if d_udf is not None:      # column 0 = sign * d udf / scale, the rest zero: one launch
-                call("nudf_col0_seed4", ptr(sign), ptr(d_udf.reshape(-1).contiguous()), float(inv_scale), P, pad_rows(P),
-                     ptr(head4), ptr(sg4))
-            else:
-                head4.zero_()
-                if second:
-                    call("nudf_col0_seed4", ptr(sign), None, float(inv_scale), P, pad_rows(P), ptr(sg4), None)
-            r1, ldr1 = head4, 4
+        # the head's adjoint is [sign * d udf / scale | d feat]: d feat is used where it lies (tile load, GEMM operand)
+        # and column 0 travels as a 4-wide operand -- no [P, 257] copy (52 us), no separate column-sum kernel (36 us)
+        head4 = torch.empty(pad_rows(P), 4, device=dev)
+        # (the second-order weight gradient's operand sign / scale comes out of the same launch)
+        sg4 = torch.empty(pad_rows(P), 4, device=dev) if second else None
+        if d_udf is not None:      # column 0 = sign * d udf / scale, the rest zero: one launch
+            call("nudf_col0_seed4", ptr(sign), ptr(d_udf.reshape(-1).contiguous()), float(inv_scale), P, pad_rows(P),
+                 ptr(head4), ptr(sg4))
         else:
-            ABAR[L] = _buf(P, plL.out, dev, zero=False)
-            call("nudf_udf_head_bwd", ptr(sign), ptr(d_udf), ptr(d_feat), d_feat_ld, P, F, inv_scale, ptr(ABAR[L]),
-                 ABAR[L].shape[1])
-            r1, ldr1 = ABAR[L], ABAR[L].shape[1]
-        for l in range(L):
-            ABAR[l] = _buf(P, layers[l].out, dev, zero=False, dtype=X[L].dtype, blocked=_isblk(X[L]))
-        # adjoint sweep: the tile starts as d feat (ABAR[L] columns 1..F); column 0 enters as a rank-1 term
-        cb = ChainBuilder(P, "LOAD", k8(F), site=("udf_adjoint", _memo_token(self)))
+            head4.zero_()
+            if second:
+                call("nudf_col0_seed4", ptr(sign), None, float(inv_scale), P, pad_rows(P), ptr(sg4), None)
+        ABAR = [_buf(P, layers[l].out, dev, zero=False, dtype=X[L].dtype, blocked=_isblk(X[L])) for l in range(L)]
+        # adjoint sweep: the tile starts as d feat (the head's adjoint, columns 1..F); column 0 enters as a rank-1 term
+        cb = ChainBuilder(P, "LOAD", k8(F), site=self._site("udf_adjoint"))
         if d_feat is None:
             d_feat, d_feat_ld = torch.zeros(P, k8(F), device=dev), k8(F)
         cb.init_load(d_feat, d_feat_ld)
@@ -1371,44 +1358,26 @@ class UDFEngine:
             x3 = DA[l - 1] if ex_fly else None
             if l == L:
                 cb.step("BWD", pl.frag(_kind("bwd_feat", "bwd")), k8(F), layers[l - 1].out, X1=X[l], X2=x2, X3=x3,
-                        C1=ABAR[l - 1], r1_row=r1, ldr1=ldr1, r1_col=pl.W, scale=sc,
+                        C1=ABAR[l - 1], r1_row=head4, ldr1=4, r1_col=pl.W, scale=sc,
                         xscale=self._xs(l - 1))
             else:
                 n_hid = layers[l - 1].out           # the skip layer's embedding columns carry no parameter gradient
                 cb.step("BWD", pl.frag(_kind("bwd" if n_hid == pl.inp else "bwd_hid:%d" % n_hid, "bwd")), k8(pl.out),
                         n_hid, X1=X[l], X2=x2, X3=x3, C1=ABAR[l - 1], scale=sc, xscale=self._xs(l - 1))
         cb.launch()
-        if grouped:
-            # two grouped launches (adjoint pairs, then the second-order pairs accumulating into the same dW): each
-            # is one resident wave of ~500 workgroups with 14-17 row chunks per tile instead of 128 -- 9x fewer
-            # atomics per output element and 2 launch tails instead of 9 (1.67 -> 1.56 ms per step; ONE launch of all
-            # 17 problems fills only 462 of the 512 slots and was slower).  The head layer enters as two problems:
-            # rows 1.. of dW from d feat, row 0 from the 4-wide column-0 operand.
-            dWL, dbL = grads[L]
-            jobs = [(ABAR[l], layers[l].out, X[l], layers[l].in_pad, grads[l][0], grads[l][1]) for l in range(L)]
-            if head4_path:
-                assert d_feat.shape[1] == d_feat_ld and d_feat.is_contiguous()
-                jobs.append((d_feat, F, X[L], plL.in_pad, dWL[1:], dbL[1:]))
-                jobs.append((head4, 1, X[L], plL.in_pad, dWL[:1], dbL[:1]))
-            else:
-                jobs.append((ABAR[L], plL.out, X[L], plL.in_pad, dWL, dbL))
-            # (f16x2: the A side -- ABAR, d feat, the head's column-0 operand -- carries the adjoint sweep's maximum, X is used as it is)
-            gemm_tn_grouped(jobs, P, assign=assign, f16x2=tn2, amax_a=amax[0:1] if tn2 else None)
-            if second:
-                jobs = [(DA[l], layers[l].out, R[l], layers[l].in_pad, grads[l][0], None) for l in range(L)]
-                if head4_path:
-                    # d (row 0 of the head) through the d udf / dx path: sign^T R_L / scale
-                    jobs.append((sg4, 1, R[L], plL.in_pad, dWL[:1], None))
-                # (f16x2: the B side -- R -- carries the tangent sweep's maximum; DA and sign / scale are used as they are)
-                gemm_tn_grouped(jobs, P, f16x2=tn2, amax_b=amax[1:2] if tn2 else None)
-            return unpack_group(layers, grads, claim_grad_slot(self, layers))
-        for l, pl in enumerate(layers):
-            dW, db = grads[l]
-            if second and l < L:
-                gemm_tn(ABAR[l], pl.out, X[l], dW, pl.out, pl.in_pad, P, dbias=db, A2=DA[l], na2=pl.out, B2=R[l])
-            else:
-                gemm_tn(ABAR[l], pl.out, X[l], dW, pl.out, pl.in_pad, P, dbias=db)
-        return unpack_group(layers, grads, claim_grad_slot(self, layers))
+        # two grouped launches (adjoint pairs, then the second-order pairs accumulating into the same dW): each
+        # is one resident wave of ~500 workgroups with 14-17 row chunks per tile instead of 128 -- 9x fewer
+        # atomics per output element and 2 launch tails instead of 9 (1.67 -> 1.56 ms per step; ONE launch of all
+        # 17 problems fills only 462 of the 512 slots and was slower).  The head layer enters as two problems:
+        # rows 1.. of dW from d feat, row 0 from the 4-wide column-0 operand.
+        assert d_feat.shape[1] == d_feat_ld and d_feat.is_contiguous()
+        first = [(ABAR[l], X[l], l) for l in range(L)] + [(d_feat, X[L], L, 1, plL.out), (head4, X[L], L, 0, 1)]
+        # d (row 0 of the head) through the d udf / dx path: sign^T R_L / scale
+        sec = [(DA[l], R[l], l) for l in range(L)] + [(sg4, R[L], L, 0, 1)] if second else ()
+        # f16x2: the A side of `first` -- ABAR, d feat, the head's column-0 operand -- carries the adjoint sweep's maximum, X is
+        # used as it is; the B side of `sec` -- R -- carries the tangent sweep's maximum, DA and sign / scale are used as they are
+        return self._weight_grads(P, first, sec, f16x2=tn2, amax_a=amax[0:1] if tn2 else None,
+                                  amax_b=amax[1:2] if tn2 else None)
 
     def _forward_layers(self, x, need_grad_state, feat_ld=0, udf_only=False):
         """per-layer GEMM launches.  x [P,3] -> dict(udf [P], sign [P], feat [P, max(feat_ld, F)], state...).
@@ -1503,15 +1472,13 @@ class UDFEngine:
             sc = self.inv_sqrt2 if l in self.skip else 1.0
             gemm_nn(ABAR[l], pl.W, P, layers[l - 1].out, pl.out_pad, "BWD", C1=ABAR[l - 1], X1=X[l],
                     X2=EX[l - 1] if second else None, scale=sc, xscale=self._xs(l - 1))
-        out = []
         for l, pl in enumerate(layers):
             dW, db = grads[l]
             if second and l < L:
                 gemm_tn(ABAR[l], pl.out, X[l], dW, pl.out, pl.in_pad, P, dbias=db, A2=DA[l], na2=pl.out, B2=R[l])
             else:
                 gemm_tn(ABAR[l], pl.out, X[l], dW, pl.out, pl.in_pad, P, dbias=db)
-            out += pl.unpack_grads(dW, db)
-        return out
+        return unpack_group(layers, grads)
 
 
 # =========================================================================================
@@ -1546,12 +1513,12 @@ def relu_chain_bwd(layers, inputs, outs, D_last, P, first_needs_input_grad, add_
     return grads, d_in0
 
 
-class ColorEngine:
+class ColorEngine(Engine):
     """ResidualRenderingNetwork: mode 'no_normal' (every shipped conf) and the reference's other branch (any other mode
     string, fields.py:456-461): the base input also carries the DETACHED unit normal and its negative."""
 
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         n = net.num_layers - 1
         self.n = n
         F, H, dout = net.d_feature, net.d_hidden, net.d_out
@@ -1565,19 +1532,8 @@ class ColorEngine:
         self.base = [PackedLinear(getattr(net, f"lin_base{l}"), perm_b0 if l == 0 else None) for l in range(n)]
         self.view = [PackedLinear(getattr(net, f"lin{l}"), perm_v0 if l == 0 else None) for l in range(n)]
 
-    def params(self):
-        out = []
-        for pl in self.view + self.base:               # registration order: lin*, then lin_base*
-            out += pl.params()
-        return out
-
-    def invalidate(self):
-        for pl in self.view + self.base:
-            pl.invalidate()
-
-    def mark_stale(self):
-        for pl in self.view + self.base:
-            pl._ver = None
+    def _all(self):
+        return self.view + self.base                   # registration order: lin*, then lin_base*
 
     @property
     def cin_ld(self):
@@ -1591,14 +1547,7 @@ class ColorEngine:
         ok = ok and self.view[n - 1].out <= 32 and self.dout <= 32
         return ok
 
-    def _kinds(self):
-        kc = self.__dict__.setdefault("_kinds_cache", {})
-        k = kc.get(_mode_key())
-        if k is None:
-            k = kc[_mode_key()] = tuple(tuple(dict.fromkeys(ks)) for ks in self._kinds_build())
-        return k
-
-    def _kinds_build(self):
+    def _frag_kinds_build(self):
         """fragment copies per layer, in the order base + view (the pack_group order)."""
         fw, bw = _kind("fwd", "fwd"), _kind("bwd", "bwd")
         kinds = [(fw, _kind("bwd_hid:%d" % self.F, "bwd"))]     # d CIN: only the feature columns carry a gradient
@@ -1613,11 +1562,6 @@ class ColorEngine:
             raise _lib.NudfError("the compositing sum inside the colour heads needs the fused chain launch")
         return self._forward_layers(CIN, rays_d, S, P, keep_state)
 
-    def backward(self, st, color_base, color, d_cb, d_color, d_logits):
-        if "chain" in st:
-            return self._backward_chain(st, color_base, color, d_cb, d_color, d_logits)
-        return self._backward_layers(st, color_base, color, d_cb, d_color, d_logits)
-
     def _forward_chain(self, CIN, rays_d, S, P, keep_state=True, row_w=None):
         """one launch: base branch (ReLU x4, sigmoid head) -> [hidden | PE(dir) | color_base] assembled in the LDS
         tile -> view branch (ReLU x4, sigmoid + logits head)   (fields.py:452-495).
@@ -1628,13 +1572,13 @@ class ColorEngine:
         fused = row_w is not None
         assert not (fused and keep_state)
         H, npe, dout = self.H, self.npe, self.dout
-        pack_group(self.base + self.view, self._kinds())
+        pack_group(self.base + self.view, self._frag_kinds())
         Pp = pad_rows(P)
         VIN = torch.empty(Pp, pad32(H + npe + dout), device=dev) if keep_state else None
         sd = _state_dtype()     # hidden activations: bf16 (4-point packed) in the 16-bit mode; CIN / VIN stay fp32
         HB = [CIN] + [_buf(P, H, dev, zero=False, dtype=sd) for _ in range(n - 1)] if keep_state else None
         HV = [VIN] + [_buf(P, H, dev, zero=False, dtype=sd) for _ in range(n - 1)] if keep_state else None
-        cb = ChainBuilder(P, "LOAD", k8(self.base[0].inp), tile_rows=COLOR_TILE, site=("col_fwd", _memo_token(self)))
+        cb = ChainBuilder(P, "LOAD", k8(self.base[0].inp), site=self._site("col_fwd"))
         cb.init_load(CIN, CIN.shape[1])
         cb.posenc(rays_d, self.net.multires_view, 1.0, x_div=S)
         for l in range(n - 1):
@@ -1670,8 +1614,6 @@ class ColorEngine:
         HB, HV = st["HB"], st["HV"]
         dev = color.device
         H, npe, dout = self.H, self.npe, self.dout
-        assign = tn_can_assign()
-        grads = alloc_grads(self.view + self.base, zero=not assign)
         plv = self.view[n - 1]
         nb = plv.out - dout
         sd = HV[1].dtype        # adjoints of the hidden layers follow the saved activations (bf16 in the 16-bit mode)
@@ -1679,9 +1621,10 @@ class ColorEngine:
         call("nudf_sigmoid_head_bwd", ptr(color), ptr(d_color), None, 0, dout, ptr(d_logits), max(nb, 1), nb, P,
              ptr(Dv[n - 1]), Dv[n - 1].shape[1])
         dVIN = _buf(P, self.view[0].inp, dev, zero=False)
-        tn2 = TN_F16X2 and PRECISION == "bf16x3" and TN_SPLIT and not _is16(HV[1]) and COLOR_TILE in (0, 32, 64)
+        # (no condition on the tile: the ReLU chains of a split mode run on the workgroup-shared kernel whatever CHAIN_TILE asks for)
+        tn2 = PRECISION == "bf16x3" and not _is16(HV[1])
         amax = torch.zeros(1, device=dev) if tn2 else None      # max |Dv, Db| (NudfChain.absmax_out of both reverse sweeps)
-        cb = ChainBuilder(P, "LOAD", k8(plv.out), tile_rows=COLOR_TILE, site=("col_bwd_view", _memo_token(self)))
+        cb = ChainBuilder(P, "LOAD", k8(plv.out), site=self._site("col_bwd_view"))
         cb.init_load(Dv[n - 1], Dv[n - 1].shape[1])
         if tn2:
             cb.absmax(amax)
@@ -1701,7 +1644,7 @@ class ColorEngine:
         call("nudf_sigmoid_head_bwd", ptr(color_base), ptr(d_cb), ptr(dVIN) + 4 * (H + npe), dVIN.shape[1],
              dout, None, 0, 0, P, ptr(Db[n - 1]), Db[n - 1].shape[1])
         dCIN = torch.empty(pad_rows(P), self.cin_ld, device=dev)
-        cb = ChainBuilder(P, "LOAD", k8(plb.out), tile_rows=COLOR_TILE, site=("col_bwd_base", _memo_token(self)))
+        cb = ChainBuilder(P, "LOAD", k8(plb.out), site=self._site("col_bwd_base"))
         cb.init_load(Db[n - 1], Db[n - 1].shape[1])
         if tn2:
             cb.absmax(amax)
@@ -1716,13 +1659,8 @@ class ColorEngine:
         pb0 = self.base[0]
         cb.step("NONE", pb0.frag(_kind("bwd_hid:%d" % self.F, "bwd")), k8(pb0.out), self.F, C1=dCIN, act_write=0)
         cb.launch()
-        jobs = []
-        for i, pl in enumerate(self.view):
-            jobs.append((Dv[i], pl.out, HV[i], pl.in_pad, grads[i][0], grads[i][1]))
-        for i, pl in enumerate(self.base):
-            jobs.append((Db[i], pl.out, HB[i], pl.in_pad, grads[n + i][0], grads[n + i][1]))
-        gemm_tn_grouped(jobs, P, assign=assign, f16x2=tn2, amax_a=amax)
-        return unpack_group(self.view + self.base, grads, claim_grad_slot(self, self.view + self.base)), dCIN[:P]
+        jobs = [(Dv[i], HV[i], i) for i in range(n)] + [(Db[i], HB[i], n + i) for i in range(n)]
+        return self._weight_grads(P, jobs, f16x2=tn2, amax_a=amax), dCIN[:P]
 
     def _forward_layers(self, CIN, rays_d, S, P, keep_state=True):
         """CIN [P, pad(F+3)] = [feature F | pts 3 | 0] (written by the UDF head + nudf_copy_cols)."""
@@ -1780,21 +1718,15 @@ class ColorEngine:
         return unpack_group(self.view + self.base, gv + gb), dCIN[:P]
 
 
-class PlainColorEngine:
+class PlainColorEngine(Engine):
     """RenderingNetwork (fields.py:325-397): one ReLU chain over an input assembled by the caller, sigmoid colour head
     (+ raw blending logits).  Not instantiated by any shipped conf (the runner uses the residual variant), so it runs on
     the per-layer GEMM launches: any input width / mode, no fused chain."""
 
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         self.layers = [PackedLinear(getattr(net, f"lin{l}")) for l in range(net.num_layers - 1)]
         self.dout = net.d_out
-
-    def params(self):
-        out = []
-        for pl in self.layers:
-            out += pl.params()
-        return out
 
     def forward(self, Xin, P, keep_state=True):
         """Xin [P, width] -> (out [P, last.out] with the first d_out columns through the sigmoid when squeeze_out)."""
@@ -1844,11 +1776,11 @@ class PlainColorEngine:
         return unpack_group(self.layers, grads), dX[:P, :self.layers[0].inp]
 
 
-class NerfEngine:
+class NerfEngine(Engine):
     """Background NeRF with view directions (fields.py:541-628)."""
 
     def __init__(self, net):
-        self.net = net
+        super().__init__(net)
         # (use_viewdirs=False never gets here: the reference's forward asserts False for it, and so does models.fields.NeRF)
         assert net.use_viewdirs, "NeRF(use_viewdirs=False) has no forward in the reference (fields.py:629-630)"
         self.D, self.W = net.D, net.W
@@ -1873,20 +1805,6 @@ class NerfEngine:
         # registration order of nn.Module: pts_linears, views_linears, feature_linear, alpha_linear, rgb_linear
         return self.pts + [self.views, self.feature, self.alpha, self.rgb]
 
-    def params(self):
-        out = []
-        for pl in self._all():
-            out += pl.params()
-        return out
-
-    def invalidate(self):
-        for pl in self._all():
-            pl.invalidate()
-
-    def mark_stale(self):
-        for pl in self._all():
-            pl._ver = None
-
     # -- dispatch: fused LDS-resident chains (default) or per-layer GEMM launches -------------------
     def _skip_layer(self):
         """index of the pts layer whose input is cat([input_pts, h]) (fields.py:607-609), or -1."""
@@ -1896,20 +1814,12 @@ class NerfEngine:
     def _chain_ok(self):
         net = self.net
         sk = [i for i in self.skips if 0 <= i < self.D]
-        ok = USE_CHAIN and os.environ.get("NUDF_NERF_CHAIN", "1") != "0"      # A/B switch for profiling
-        ok = ok and self.W <= 256 and self.W % 32 == 0 and self.D + 5 <= CH_MAX_STEPS and len(sk) <= 1
+        ok = USE_CHAIN and self.W <= 256 and self.W % 32 == 0 and self.D + 5 <= CH_MAX_STEPS and len(sk) <= 1
         ok = ok and (not sk or sk[0] < self.D - 1) and k8(self.e) <= 288 and k8(self.W + self.ev) <= 288
         ok = ok and net.d_in_view == 3 and self.ev == 3 * (2 * net.multires_view + 1) and self.views.out <= 256
         return ok
 
-    def _kinds(self):
-        kc = self.__dict__.setdefault("_kinds_cache", {})
-        k = kc.get(_mode_key())
-        if k is None:
-            k = kc[_mode_key()] = tuple(tuple(dict.fromkeys(ks)) for ks in self._kinds_build())
-        return k
-
-    def _kinds_build(self):
+    def _frag_kinds_build(self):
         """fragment copies per layer in _all() order (pts, views, feature, alpha, rgb)."""
         fw, bw = _kind("fwd", "fwd"), _kind("bwd", "bwd")
         W, e, j = self.W, self.e, self._skip_layer()
@@ -1928,11 +1838,6 @@ class NerfEngine:
             return self._forward_chain(pts4, rays_d, S, P, keep_state)
         return self._forward_layers(pts4, rays_d, S, P, keep_state)
 
-    def backward(self, st, d_sigma, d_rgb):
-        if "chain" in st:
-            return self._backward_chain(st, d_sigma, d_rgb)
-        return self._backward_layers(st, d_sigma, d_rgb)
-
     def _forward_chain(self, pts4, rays_d, S, P, keep_state=True):
         """the whole background network (fields.py:599-628) as one launch: PE(pts) tile -> 8 ReLU layers (the skip
         layer's cat([input_pts, h]) is 340 wide, more than the 288-column LDS tile, so its PE part is multiplied by
@@ -1942,7 +1847,7 @@ class NerfEngine:
         net = self.net
         fw = _kind("fwd", "fwd")
         j = self._skip_layer()
-        pack_group(self._all(), self._kinds())
+        pack_group(self._all(), self._frag_kinds())
         Hin = [_buf(P, self.pts[0].inp, dev)]
         if keep_state:
             Hin += [_buf(P, pl.inp, dev) for pl in self.pts[1:]]
@@ -1956,7 +1861,7 @@ class NerfEngine:
         hv = _buf(P, self.views.out, dev, zero=False) if keep_state else None
         sigma = torch.empty(Pp, 1, device=dev)
         rgb = torch.empty(Pp, 3, device=dev)
-        cb = ChainBuilder(P, "LOAD", k8(e), site=("nerf_fwd", _memo_token(self)))
+        cb = ChainBuilder(P, "LOAD", k8(e), site=self._site("nerf_fwd"))
         cb.init_load(Hin[0], Hin[0].shape[1])
         cb.posenc(rays_d, net.multires_view, 1.0, x_div=S)
         SK = None
@@ -1989,9 +1894,6 @@ class NerfEngine:
         dev = VIN.device
         bw = _kind("bwd", "bwd")
         j = self._skip_layer()
-        layers = self._all()
-        assign = tn_can_assign()
-        grads = alloc_grads(layers, zero=not assign)
         Pp = pad_rows(P)
         Drgb = torch.zeros(Pp, 32, device=dev)
         call("nudf_copy_cols", ptr(d_rgb), 3, 1, ptr(Drgb), 32, 3, P, 1.0)
@@ -2000,7 +1902,7 @@ class NerfEngine:
         Dv = _buf(P, self.views.out, dev, zero=False)
         dF = _buf(P, W, dev, zero=False)
         Dp = [_buf(P, W, dev, zero=False) for _ in range(D)]
-        cb = ChainBuilder(P, "LOAD", k8(3), site=("nerf_bwd", _memo_token(self)))
+        cb = ChainBuilder(P, "LOAD", k8(3), site=self._site("nerf_bwd"))
         cb.init_load(Drgb, Drgb.shape[1])
         if _sweep_dtype("bwd") == "f16x2":
             cb.tile_scale()
@@ -2013,13 +1915,9 @@ class NerfEngine:
             kind = _kind("bwd_hid:%d" % W, "bwd") if i == j else bw
             cb.step("MULMASK", pl.frag(kind), k8(pl.out), W, X1=Hin[i], C1=Dp[i - 1], act_write=1 if i > 1 else 0)
         cb.launch()
-        jobs = [(Dp[i], pl.out, Hin[i], pl.in_pad, grads[i][0], grads[i][1]) for i, pl in enumerate(self.pts)]
-        jobs.append((Dv, self.views.out, VIN, self.views.in_pad, grads[D][0], grads[D][1]))
-        jobs.append((dF, self.feature.out, h_last, self.feature.in_pad, grads[D + 1][0], grads[D + 1][1]))
-        jobs.append((Dsig, 1, h_last, self.alpha.in_pad, grads[D + 2][0], grads[D + 2][1]))
-        jobs.append((Drgb, 3, hv, self.rgb.in_pad, grads[D + 3][0], grads[D + 3][1]))
-        gemm_tn_grouped(jobs, P, assign=assign)
-        return unpack_group(layers, grads, claim_grad_slot(self, layers))
+        # (_all() order: pts, views, feature, alpha, rgb)
+        jobs = [(Dp[i], Hin[i], i) for i in range(D)] + [(Dv, VIN, D), (dF, h_last, D + 1), (Dsig, h_last, D + 2), (Drgb, hv, D + 3)]
+        return self._weight_grads(P, jobs)
 
     def _forward_layers(self, pts4, rays_d, S, P, keep_state=True):
         dev = pts4.device
