@@ -222,6 +222,9 @@ CHAIN_DEBUG = None     # int64 tensor [blocks * 4, 32]: per-wave timeline writte
 CHAIN_TILE = int(os.environ.get("NUDF_CHAIN_TILE", "0"))  # 0 = auto, 32 / 64 force the points-per-workgroup tile
 
 
+PV_MAXE = 96           # widest encoding nudf_posenc_vjp takes (PV_MAXE of csrc/rays_embed.hip; tests/test_arch_gates.py)
+
+
 def k8(n: int) -> int:
     """reduction length of a chain step: the K loop runs two groups of 8 per iteration."""
     return (n + 15) // 16 * 16
@@ -1136,7 +1139,17 @@ class UDFEngine(Engine):
             return self._forward_chain(x, need_grad_state, feat_ld, udf_only, feat_buf)
         return self._forward_layers(x, need_grad_state, feat_ld, udf_only)
 
+    def _gradient_guard(self):
+        """what no path of d udf / dx serves, refused BEFORE the first launch (the sweeps would otherwise run up to the step
+        that cannot go on): a second skip layer, and an encoding wider than nudf_posenc_vjp stages per point."""
+        if len(self.skip) > 1:
+            raise NotImplementedError("more than one skip layer")
+        if self.E > PV_MAXE:
+            raise _lib.NudfError("nudf_posenc_vjp: encoding wider than %d (multires %d gives %d columns)"
+                                 % (PV_MAXE, self.net.multires, self.E))
+
     def gradient(self, x, st):
+        self._gradient_guard()
         if self._chain_ok():
             return self._gradient_chain(x, st)
         return self._gradient_layers(x, st)
@@ -1144,6 +1157,7 @@ class UDFEngine(Engine):
     def forward_gradient(self, x, feat_ld=0, feat_buf=None):
         """value (with saved state) and d udf / dx of the same points -> (st, g, DA): what forward(need_grad_state=True)
         followed by gradient() returns, as ONE chain launch where the mode has it (FUSE_SWEEPS)."""
+        self._gradient_guard()
         if self._chain_ok() and _fuse() and 2 * self.L + 3 <= CH_MAX_STEPS:
             st = self._forward_chain(x, True, feat_ld, False, feat_buf, with_grad=True)
             g, DA = st.pop("g"), st.pop("DA")
@@ -1174,6 +1188,15 @@ class UDFEngine(Engine):
             kinds.append(tuple(ks))
         return kinds
 
+    def _blocked(self, P):
+        """saved state in the blocked layout (`_state_blocked`)?  Only where the last hidden width is a multiple of 16: the
+        transposed-product kernels' seed reads k8(width) columns of X[L] and their stores leave the columns behind the width
+        unwritten, so any other width keeps row-major state, whose pad columns `_forward_chain` clears.
+        (Widths other than the shipped conf's have run on the workgroup-shared kernels only -- tests/test_gpu_arch_sweep.py,
+        up to 349 points; the transposed-product / blocked kernels of fp32 launches above 16 384 points and the wave-private
+        kernel of NUDF_CHAIN_ROWS=1 above 24 576 have never run off the shipped shapes.)"""
+        return _state_blocked(P) and k8(self.layers[self.L].inp) == self.layers[self.L].inp
+
     def _skip_col(self, l):
         """tile column where PE(x)/sqrt(2) starts in the input of skip layer l."""
         return self.layers[l].inp - self.E
@@ -1187,9 +1210,14 @@ class UDFEngine(Engine):
         net = self.net
         pack_group(self.layers, self._frag_kinds())
         sd = _state_dtype()     # X[0] (the encoding, written by the tile initialisation) stays fp32, row-major
-        blk = _state_blocked(P)
+        blk = self._blocked(P)
         X = ([_buf(P, self.layers[0].inp, dev, zero=False)] +
              [_buf(P, pl.inp, dev, zero=False, dtype=sd, blocked=blk) for pl in self.layers[1:]]) if need_grad_state else None
+        if need_grad_state and k8(self.layers[L].inp) != self.layers[L].inp:
+            # the input-gradient sweep's seed (NUDF_CH_INIT_SEED) reads k8(width) columns of X[L] and multiplies softplus' of
+            # them by zero weights: the columns behind a width that is no multiple of 16 must hold finite values
+            # (row-major state at such a width: `_blocked`)
+            X[L] = _buf(P, self.layers[L].inp, dev, dtype=sd)
         cb = ChainBuilder(P, "POSENC", k8(self.E), site=self._site("udf_fwd_grad" if with_grad else "udf_fwd"))
         cb.posenc(x, net.multires, float(net.scale))
         if need_grad_state:
@@ -1346,6 +1374,12 @@ class UDFEngine(Engine):
         cb = ChainBuilder(P, "LOAD", k8(F), site=self._site("udf_adjoint"))
         if d_feat is None:
             d_feat, d_feat_ld = torch.zeros(P, k8(F), device=dev), k8(F)
+        elif d_feat_ld < k8(F) or d_feat_ld % 4:
+            # the tile load reads k8(F) columns of every row as 16-byte words and the weight-gradient GEMM takes rows of whole
+            # float4: an adjoint of exactly F columns (evaluate(feat_ld=0) with F % 16 != 0) moves into a zero-padded buffer
+            padded = torch.zeros(P, pad32(F), device=dev)
+            padded[:, :F] = d_feat[:, :F]
+            d_feat, d_feat_ld = padded, pad32(F)
         cb.init_load(d_feat, d_feat_ld)
         if tn2:
             cb.absmax(amax[0:1])
@@ -1545,6 +1579,8 @@ class ColorEngine(Engine):
         ok = USE_CHAIN and n >= 2 and 2 * n <= CH_MAX_STEPS and self.H <= 256 and self.net.embedview_fn is not None
         ok = ok and k8(self.base[0].inp) <= 288 and k8(self.H + self.npe + self.dout) <= 288 and self.F % 4 == 0
         ok = ok and self.view[n - 1].out <= 32 and self.dout <= 32
+        # the base head writes its 32-column tile behind [hidden | PE(dir)] of the view branch's input: inside the 288 columns
+        ok = ok and self.H + self.npe + pad32(self.dout) <= 288
         return ok
 
     def _frag_kinds_build(self):
@@ -1644,6 +1680,8 @@ class ColorEngine(Engine):
         call("nudf_sigmoid_head_bwd", ptr(color_base), ptr(d_cb), ptr(dVIN) + 4 * (H + npe), dVIN.shape[1],
              dout, None, 0, 0, P, ptr(Db[n - 1]), Db[n - 1].shape[1])
         dCIN = torch.empty(pad_rows(P), self.cin_ld, device=dev)
+        if k8(self.F) != self.F:     # (the UDF adjoint sweep loads k8(F) columns of d feat: finite zeros behind the features)
+            _zero_cols(dCIN, self.F)
         cb = ChainBuilder(P, "LOAD", k8(plb.out), site=self._site("col_bwd_base"))
         cb.init_load(Db[n - 1], Db[n - 1].shape[1])
         if tn2:
@@ -1965,7 +2003,7 @@ class NerfEngine(Engine):
         gemm_nn(Drgb, self.rgb.W, P, self.views.out, self.rgb.out_pad, "MULMASK", C1=Dv, X1=hv)
         g_views = self.views.new_grad_buffers()
         gemm_tn(Dv, self.views.out, VIN, g_views[0], self.views.out, self.views.in_pad, P, dbias=g_views[1])
-        dVIN = _buf(P, self.views.inp, dev, zero=False)  # only its first `feature.out` columns are read
+        dVIN = _buf(P, self.views.inp, dev)  # (the feature layer's GEMM contracts pad32(feature.out) columns: finite pads)
         gemm_nn(Dv, self.views.W, P, self.views.inp, self.views.out_pad, "NONE", C1=dVIN)
         # feature / alpha heads share h = outs[-1]
         g_feat = self.feature.new_grad_buffers()
