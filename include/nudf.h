@@ -1203,6 +1203,80 @@ int nudf_meshorient_check(const NudfMeshOrient* args, void* stream);       /* on
 int nudf_meshorient_outward(const NudfMeshOrient* args, void* stream);     /* one wavefront per component     */
 int nudf_meshorient_normals(const NudfMeshOrient* args, void* stream);     /* one thread per vertex           */
 
+/* ------------------------------------------------------------------------------------
+ * Triangle rasteriser with a depth buffer (neuraludf_amd/meshrender.py rasterize, vertex_visibility, color_vertices): depth,
+ * face and barycentric maps of a mesh from the dataset cameras, depth-tested vertex visibility and vertex colours blended
+ * from the source images.  A struct of its own: the layouts of NudfMeshTopo and NudfMeshOrient are pinned.  float64 without
+ * contracted multiply-adds, integer atomics only: every result is identical from run to run.  A view is rows 0..2 of a world
+ * matrix P, as `proj` of NudfMeshTopo; pixel (x, y) is the sample point with exactly those integer coordinates.  One struct;
+ * each entry point reads the fields its comment names.  The caller passes `n_views` views at a time (a chunk of them, with
+ * every per-view array pointing at the chunk's first view).
+ *   project     one thread per (view, vertex): q = P p, each row as ((P0 x + P1 y) + P2 z) + P3;
+ *               scr[view, v] = (q.x / q.z, q.y / q.z, q.z).  A vertex is valid in a view when all three are finite and
+ *               q.z > 0;
+ *   bounds      one thread per (view, face): npix[view, f] = (xmax - xmin + 1) (ymax - ymin + 1) with xmin = max(ceil(min x_i),
+ *               0), xmax = min(floor(max x_i), W - 1), the same in y; 0 when a vertex index is out of range, the face repeats
+ *               a vertex, a vertex is invalid in the view (no near-plane clipping), the signed area A = (x1 - x0)(y2 - y0) -
+ *               (x2 - x0)(y1 - y0) is 0 or not finite, or the box is empty;
+ *   draw_small  one thread per entry e of `entries` (view * n_faces + f, a (view, face) with npix > 0): every pixel (x, y) of
+ *               the box, row-major.  The per-pixel function: w0 = (x1 - x)(y2 - y) - (x2 - x)(y1 - y), w1 = (x2 - x)(y0 - y) -
+ *               (x0 - x)(y2 - y), w2 = (x0 - x)(y1 - y) - (x1 - x)(y0 - y); covered when all three are >= 0 or all three are
+ *               <= 0 (two-sided, edges inclusive) and s = (w0 + w1) + w2 is finite and not 0; b_i = w_i / s; z = 1 / ((b0 / z0
+ *               + b1 / z1) + b2 / z2); key = (uint64)bits(float32(z)) << 32 | f; zbuf[view, y, x] = min(zbuf, key) (64-bit
+ *               unsigned atomicMin; the caller fills zbuf with all-ones).  Depth ties go to the smaller face index;
+ *   draw_large  one wavefront per entry: lane l takes the pixels l, l + 64, ... of the box in row-major order, the same
+ *               per-pixel function;
+ *   resolve     one thread per pixel: all-ones -> depth +inf, face -1, bary (0, 0, 0); otherwise depth = the float32 of the
+ *               key's high word, face = its low word, bary = float32(b_i) of the per-pixel function of that face at that
+ *               pixel.  face and bary may be NULL (not written);
+ *   visible     one thread per (view, vertex): vis[view, v] = 1 when the vertex is valid, (px, py) = round-half-even of
+ *               scr.xy lies in [0, W - 1] x [0, H - 1], and float32(scr.z) <= m + min_gap (float32 sum), m = the maximum of
+ *               depth[view] over [px - 1, px + 1] x [py - 1, py + 1] clamped to the image; else 0;
+ *   colour      one thread per vertex, over the views in ascending order where vis[view, v] is set: (u, w, .) = the projection
+ *               as in `project` (recomputed), x0 = floor(u), fx = u - x0, y0 = floor(w), fy = w - y0, taps at x0, x0 + 1 and
+ *               y0, y0 + 1 clamped to the image, c = ((1 - fx)(1 - fy) c00 + fx (1 - fy) c10) + ((1 - fx) fy c01 + fx fy c11)
+ *               per channel in float64, c10 the tap at x0 + 1 (uint8 taps are divided by 255 first); the weight g = 1 without
+ *               normals, else pow(|n . d|, power), d = (cam_pos[view] - p) / |cam_pos[view] - p|, dot products and squared
+ *               lengths summed as (x + y) + z; S = S + g, C = C + g c.  colors[v] = float32(C / S) and n_seen[v] = the number
+ *               of such views; where S is not finite or not > 0, colors[v] = fill and n_seen[v] = 0.
+ * ---------------------------------------------------------------------------------- */
+typedef struct NudfMeshRaster {
+  const double* pos;         /* [n_verts, 3] vertex positions (project, colour)                                      */
+  const int64_t* faces;      /* [n_faces, 3] (bounds, draw_*, resolve)                                               */
+  const double* proj;        /* [n_views, 3, 4] rows 0..2 of each world matrix (project, colour)                     */
+  double* scr;               /* [n_views, n_verts, 3] (project: written; bounds, draw_*, resolve, visible: read)     */
+  int32_t* npix;             /* [n_views, n_faces] (bounds)                                                          */
+  const int64_t* entries;    /* [n_entries] view * n_faces + f, ascending (draw_*)                                   */
+  uint64_t* zbuf;            /* [n_views, H, W] keys, all-ones = empty (draw_*: atomicMin; resolve: read)            */
+  float* depth;              /* [n_views, H, W] (resolve: written; visible: read)                                    */
+  int32_t* face;             /* [n_views, H, W] or NULL (resolve)                                                    */
+  float* bary;               /* [n_views, H, W, 3] or NULL (resolve)                                                 */
+  uint8_t* vis;              /* [n_views, n_verts] (visible: written; colour: read)                                  */
+  const void* images;        /* [n_views, H, W, 3] uint8 or float32 (colour)                                         */
+  const double* normals;     /* [n_verts, 3] unit vertex normals or NULL: weight 1 (colour)                          */
+  const double* cam_pos;     /* [n_views, 3] camera centres, read with normals only (colour)                         */
+  float* colors;             /* [n_verts, 3] (colour)                                                                */
+  int32_t* n_seen;           /* [n_verts] (colour)                                                                   */
+  int64_t n_faces;
+  int64_t n_verts;
+  int64_t n_entries;
+  double power;              /* colour: exponent of |n . d|                                                          */
+  float fill[3];             /* colour: the colour of a vertex no view contributes to                                */
+  float min_gap;             /* visible: least camera-depth distance at which an occluder hides a vertex             */
+  int32_t n_views;
+  int32_t H;
+  int32_t W;
+  int32_t image_f32;         /* colour: 1 = float32 images, 0 = uint8                                                */
+} NudfMeshRaster;
+int nudf_meshraster_struct_size(void);                                     /* sizeof(NudfMeshRaster)          */
+int nudf_meshraster_project(const NudfMeshRaster* args, void* stream);     /* one thread per (view, vertex)   */
+int nudf_meshraster_bounds(const NudfMeshRaster* args, void* stream);      /* one thread per (view, face)     */
+int nudf_meshraster_draw_small(const NudfMeshRaster* args, void* stream);  /* one thread per entry            */
+int nudf_meshraster_draw_large(const NudfMeshRaster* args, void* stream);  /* one wavefront per entry         */
+int nudf_meshraster_resolve(const NudfMeshRaster* args, void* stream);     /* one thread per pixel            */
+int nudf_meshraster_visible(const NudfMeshRaster* args, void* stream);     /* one thread per (view, vertex)   */
+int nudf_meshraster_colour(const NudfMeshRaster* args, void* stream);      /* one thread per vertex           */
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,14 @@ class MeshOrient(C.Structure):
                 ("n_verts", C.c_int64), ("n_medges", C.c_int64), ("n_comps", C.c_int64)]
 
 
+class MeshRaster(C.Structure):
+    _fields_ = [("pos", c_fp), ("faces", c_fp), ("proj", c_fp), ("scr", c_fp), ("npix", c_fp), ("entries", c_fp),
+                ("zbuf", c_fp), ("depth", c_fp), ("face", c_fp), ("bary", c_fp), ("vis", c_fp), ("images", c_fp),
+                ("normals", c_fp), ("cam_pos", c_fp), ("colors", c_fp), ("n_seen", c_fp), ("n_faces", C.c_int64),
+                ("n_verts", C.c_int64), ("n_entries", C.c_int64), ("power", C.c_double), ("fill", f32 * 3),
+                ("min_gap", f32), ("n_views", i32), ("H", i32), ("W", i32), ("image_f32", i32)]
+
+
 # float offsets of the device loss-weight vector (include/nudf.h NUDF_LW_*)
 LW = dict(color_base=0, color=1, color_pixel=2, color_patch=3, igr=4, igr_ns=5, sparse=6, mask=7, color_sum=8)
 LW_COUNT = 16
@@ -283,6 +291,8 @@ SYMBOLS = [
     "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump", "nudf_meshtopo_views",
     "nudf_meshorient_struct_size", "nudf_meshorient_hook", "nudf_meshorient_jump", "nudf_meshorient_check",
     "nudf_meshorient_outward", "nudf_meshorient_normals",
+    "nudf_meshraster_struct_size", "nudf_meshraster_project", "nudf_meshraster_bounds", "nudf_meshraster_draw_small",
+    "nudf_meshraster_draw_large", "nudf_meshraster_resolve", "nudf_meshraster_visible", "nudf_meshraster_colour",
 ]
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
@@ -365,6 +375,10 @@ _ARGTYPES = {
                                               "nudf_meshtopo_views")},
     **{n: [C.POINTER(MeshOrient), _P] for n in ("nudf_meshorient_hook", "nudf_meshorient_jump", "nudf_meshorient_check",
                                                 "nudf_meshorient_outward", "nudf_meshorient_normals")},
+    **{n: [C.POINTER(MeshRaster), _P] for n in ("nudf_meshraster_project", "nudf_meshraster_bounds",
+                                                "nudf_meshraster_draw_small", "nudf_meshraster_draw_large",
+                                                "nudf_meshraster_resolve", "nudf_meshraster_visible",
+                                                "nudf_meshraster_colour")},
 }
 
 _lib = None
@@ -410,7 +424,8 @@ def lib():
                             "rebuild with `python -m neuraludf_amd.build --force`")
         for name, mirror in (("nudf_isosurface_struct_size", IsoSurface),
                              ("nudf_isosurface_sparse_struct_size", IsoSurfaceSparse),       # (the same, for the level-set mesher
-                             ("nudf_meshorient_struct_size", MeshOrient)):                   # and the face orientation)
+                             ("nudf_meshorient_struct_size", MeshOrient),                    # the face orientation
+                             ("nudf_meshraster_struct_size", MeshRaster)):                   # and the rasteriser)
             size = getattr(_lib, name, None)
             if size is None or int(size()) != C.sizeof(mirror):
                 v, _lib = (None if size is None else int(size())), None

@@ -1,0 +1,256 @@
+// Triangle rasteriser with a depth buffer (include/nudf.h NudfMeshRaster, neuraludf_amd/meshrender.py): depth, face and
+// barycentric maps of a mesh from the dataset cameras, depth-tested vertex visibility, vertex colours from the images.
+//   project    -- one thread per (view, vertex): screen coordinates and camera depth, float64;
+//   bounds     -- one thread per (view, face): the number of pixels of its clamped box, 0 for a face that draws nothing;
+//   draw_small -- one thread per (view, face) of the small list: every pixel of its box (most faces of a 512^3 mesh cover
+//                 a pixel or two at 1600 x 1200);
+//   draw_large -- one wavefront per (view, face) of the large list, lanes striding the box row-major;
+//   resolve    -- one thread per pixel: depth, face and barycentrics from the winning key;
+//   visible    -- one thread per (view, vertex): the depth test against the 3 x 3 maximum around its pixel;
+//   colour     -- one thread per vertex over the views in ascending order: weighted mean of bilinear samples.
+// The depth buffer holds one 64-bit key per pixel, (bits of the float32 depth) << 32 | face: positive floats order as their
+// bits, so a 64-bit unsigned atomicMin keeps the nearest face and, among equal depths, the smallest face index -- whatever
+// the order in which the atomics land.  No floating-point atomics, no kernel waits on another workgroup.  The float64
+// expressions follow the numpy restatement (tests/meshraster_ref.py) operation by operation: products and sums go through
+// mul / add / sub under the pragma, as in meshorient.hip.
+#pragma clang fp contract(off)
+
+#include "meshraster_pixel.h"
+
+#define MR_BLOCK 256
+#define MR_WAVE 64
+
+// ---- (a) projection and boxes ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MR_BLOCK) void mr_project_kernel(NudfMeshRaster a) {
+  const int64_t i = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
+  if (i >= (int64_t)a.n_views * a.n_verts) return;
+  const int64_t view = i / a.n_verts, v = i - view * a.n_verts;
+  mr_project(a.proj + 12 * view, a.pos + 3 * v, a.scr + 3 * i);
+}
+
+__global__ __launch_bounds__(MR_BLOCK) void mr_bounds_kernel(NudfMeshRaster a) {
+  const int64_t i = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
+  if (i >= (int64_t)a.n_views * a.n_faces) return;
+  const int64_t view = i / a.n_faces, f = i - view * a.n_faces;
+  MrFace t;
+  mr_face(a, view, f, &t);
+  a.npix[i] = t.bw * t.bh;                           // <= H * W < 2^31
+}
+
+// ---- (b) drawing -------------------------------------------------------------------------------------------------------
+// the (view, face) of entry e; false when the entry is out of range
+__device__ __forceinline__ bool mr_entry(const NudfMeshRaster& a, int64_t e, int64_t* view, int64_t* f) {
+  const int64_t id = a.entries[e];
+  if (id < 0 || id >= (int64_t)a.n_views * a.n_faces) return false;
+  *view = id / a.n_faces;
+  *f = id - *view * a.n_faces;
+  return true;
+}
+
+__global__ __launch_bounds__(MR_BLOCK) void mr_draw_small_kernel(NudfMeshRaster a) {
+  const int64_t e = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
+  if (e >= a.n_entries) return;
+  int64_t view, f;
+  MrFace t;
+  if (!mr_entry(a, e, &view, &f) || !mr_face(a, view, f, &t)) return;
+  const int32_t n = t.bw * t.bh;
+  for (int32_t i = 0; i < n; ++i) mr_draw(a, t, view, f, i);
+}
+
+__global__ __launch_bounds__(MR_BLOCK) void mr_draw_large_kernel(NudfMeshRaster a) {
+  const int64_t e = (int64_t)blockIdx.x * (MR_BLOCK / MR_WAVE) + threadIdx.x / MR_WAVE;
+  const int lane = threadIdx.x % MR_WAVE;
+  if (e >= a.n_entries) return;
+  int64_t view, f;
+  MrFace t;
+  if (!mr_entry(a, e, &view, &f) || !mr_face(a, view, f, &t)) return;
+  const int32_t n = t.bw * t.bh;
+  for (int32_t i = lane; i < n; i += MR_WAVE) mr_draw(a, t, view, f, i);
+}
+
+// ---- (c) resolve -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MR_BLOCK) void mr_resolve_kernel(NudfMeshRaster a) {
+  const int64_t i = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
+  const int64_t hw = (int64_t)a.H * a.W;
+  if (i >= a.n_views * hw) return;
+  const unsigned long long key = a.zbuf[i];
+  const int64_t f = (int64_t)(key & 0xffffffffULL);
+  float depth = HUGE_VALF, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+  int32_t face = -1;
+  if (key != MR_EMPTY && f < a.n_faces) {
+    const int64_t view = i / hw, p = i - view * hw;
+    depth = __uint_as_float((unsigned)(key >> 32));
+    face = (int32_t)f;
+    if (a.bary) {
+      MrFace t;
+      double b[3], z;
+      if (mr_face(a, view, f, &t) && mr_pixel(t, (int32_t)(p % a.W), (int32_t)(p / a.W), b, &z))
+        b0 = (float)b[0], b1 = (float)b[1], b2 = (float)b[2];
+    }
+  }
+  a.depth[i] = depth;
+  if (a.face) a.face[i] = face;
+  if (a.bary) a.bary[3 * i] = b0, a.bary[3 * i + 1] = b1, a.bary[3 * i + 2] = b2;
+}
+
+// ---- (d) visibility ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(MR_BLOCK) void mr_visible_kernel(NudfMeshRaster a) {
+  const int64_t i = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
+  if (i >= (int64_t)a.n_views * a.n_verts) return;
+  const int64_t view = i / a.n_verts;
+  const double* s = a.scr + 3 * i;
+  uint8_t seen = 0;
+  if (mr_valid(s) && fabs(s[0]) < 0x1p52 && fabs(s[1]) < 0x1p52) {
+    const double px = rint(s[0]), py = rint(s[1]);   // rint: half to even, as np.round
+    if (px >= 0.0 && px <= (double)(a.W - 1) && py >= 0.0 && py <= (double)(a.H - 1)) {
+      const int32_t ix = (int32_t)px, iy = (int32_t)py;
+      const int32_t xa = ix > 0 ? ix - 1 : 0, xb = ix < a.W - 1 ? ix + 1 : a.W - 1;
+      const int32_t ya = iy > 0 ? iy - 1 : 0, yb = iy < a.H - 1 ? iy + 1 : a.H - 1;
+      const float* d = a.depth + view * a.H * (int64_t)a.W;
+      float m = d[(int64_t)ya * a.W + xa];
+      for (int32_t y = ya; y <= yb; ++y)
+        for (int32_t x = xa; x <= xb; ++x) m = fmaxf(m, d[(int64_t)y * a.W + x]);
+      seen = (float)s[2] <= m + a.min_gap;
+    }
+  }
+  a.vis[i] = seen;
+}
+
+// ---- (e) vertex colours ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double mr_tap(const NudfMeshRaster& a, int64_t pixel, int c) {
+  if (a.image_f32) return (double)((const float*)a.images)[3 * pixel + c];
+  return __ddiv_rn((double)((const uint8_t*)a.images)[3 * pixel + c], 255.0);
+}
+
+__global__ __launch_bounds__(MR_BLOCK) void mr_colour_kernel(NudfMeshRaster a) {
+  const int64_t v = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
+  if (v >= a.n_verts) return;
+  const double* p = a.pos + 3 * v;
+  double sw = 0.0, sc[3] = {0.0, 0.0, 0.0};
+  int32_t n = 0;
+  for (int64_t view = 0; view < a.n_views; ++view) {
+    if (!a.vis[view * a.n_verts + v]) continue;
+    double s[3];
+    mr_project(a.proj + 12 * view, p, s);
+    const double fx0 = floor(s[0]), fy0 = floor(s[1]);
+    // (vis is the caller's: the clamps below keep every tap inside the image whatever the projection is, NaN included)
+    const double fx = mr_sub(s[0], fx0), fy = mr_sub(s[1], fy0);
+    const double wmax = (double)(a.W - 1), hmax = (double)(a.H - 1);
+    const int64_t xa = (int64_t)fmin(fmax(fx0, 0.0), wmax), xb = (int64_t)fmin(fmax(mr_add(fx0, 1.0), 0.0), wmax);
+    const int64_t ya = (int64_t)fmin(fmax(fy0, 0.0), hmax), yb = (int64_t)fmin(fmax(mr_add(fy0, 1.0), 0.0), hmax);
+    const int64_t base = view * a.H * (int64_t)a.W;
+    const int64_t p00 = base + ya * a.W + xa, p10 = base + ya * a.W + xb;
+    const int64_t p01 = base + yb * a.W + xa, p11 = base + yb * a.W + xb;
+    const double gx = mr_sub(1.0, fx), gy = mr_sub(1.0, fy);
+    const double w00 = mr_mul(gx, gy), w10 = mr_mul(fx, gy), w01 = mr_mul(gx, fy), w11 = mr_mul(fx, fy);
+    double g = 1.0;
+    if (a.normals) {
+      const double* cam = a.cam_pos + 3 * view;
+      const double* nv = a.normals + 3 * v;
+      const double dx = mr_sub(cam[0], p[0]), dy = mr_sub(cam[1], p[1]), dz = mr_sub(cam[2], p[2]);
+      const double len = __dsqrt_rn(mr_add(mr_add(mr_mul(dx, dx), mr_mul(dy, dy)), mr_mul(dz, dz)));
+      const double dot = mr_add(mr_add(mr_mul(nv[0], __ddiv_rn(dx, len)), mr_mul(nv[1], __ddiv_rn(dy, len))),
+                                mr_mul(nv[2], __ddiv_rn(dz, len)));
+      g = pow(fabs(dot), a.power);
+    }
+    for (int c = 0; c < 3; ++c) {
+      const double col = mr_add(mr_add(mr_mul(w00, mr_tap(a, p00, c)), mr_mul(w10, mr_tap(a, p10, c))),
+                                mr_add(mr_mul(w01, mr_tap(a, p01, c)), mr_mul(w11, mr_tap(a, p11, c))));
+      sc[c] = mr_add(sc[c], mr_mul(g, col));
+    }
+    sw = mr_add(sw, g);
+    ++n;
+  }
+  const bool ok = sw > 0.0 && sw < HUGE_VAL;
+  for (int c = 0; c < 3; ++c) a.colors[3 * v + c] = ok ? (float)__ddiv_rn(sc[c], sw) : a.fill[c];
+  a.n_seen[v] = ok ? n : 0;
+}
+
+// ---- launchers --------------------------------------------------------------------------------------------------------
+#define MR_MAX_THREADS (1LL << 38)                   // one-dimensional grids of MR_BLOCK threads: < 2^31 blocks
+
+static unsigned blocks(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+static int refuse(const char* where) {
+  nudf_set_error(where, hipErrorInvalidValue);
+  return (int)hipErrorInvalidValue;
+}
+
+static bool sizes_ok(const NudfMeshRaster& a) {
+  if (a.n_faces < 0 || a.n_faces >= (1LL << 31) || a.n_verts < 0 || a.n_verts >= (1LL << 31)) return false;
+  if (a.n_views < 0 || a.H < 0 || a.W < 0 || a.n_entries < 0) return false;
+  if ((int64_t)a.H * a.W >= (1LL << 31)) return false;                   // npix is int32
+  if ((int64_t)a.n_views * a.H * a.W > MR_MAX_THREADS) return false;    // n_views < 2^31, H W < 2^31: no overflow
+  if (a.n_views * a.n_faces > MR_MAX_THREADS || a.n_views * a.n_verts > MR_MAX_THREADS) return false;
+  return a.n_entries <= a.n_views * a.n_faces;
+}
+
+#define MR_BAD_SIZES(name) \
+  name ": bad sizes (n_faces, n_verts and H * W must be < 2^31, n_views * H * W, n_views * n_faces and n_views * n_verts " \
+       "<= 2^38, n_entries <= n_views * n_faces, nothing negative)"
+
+#define MR_LAUNCH(kernel, n, per_block, name)                                                             \
+  hipLaunchKernelGGL(kernel, dim3(blocks(n, per_block)), dim3(MR_BLOCK), 0, (hipStream_t)stream, a);      \
+  NUDF_CHECK_LAUNCH(name);                                                                                \
+  return 0
+
+// an image is needed as soon as there is something to do per view
+#define MR_NEED_IMAGE(name) \
+  if (a.H < 1 || a.W < 1) return refuse(name ": H and W must be >= 1")
+
+extern "C" int nudf_meshraster_struct_size(void) { return (int)sizeof(NudfMeshRaster); }
+
+extern "C" int nudf_meshraster_project(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_project"));
+  if (a.n_views <= 0 || a.n_verts <= 0) return 0;
+  MR_LAUNCH(mr_project_kernel, a.n_views * a.n_verts, MR_BLOCK, "nudf_meshraster_project");
+}
+
+extern "C" int nudf_meshraster_bounds(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_bounds"));
+  if (a.n_views <= 0 || a.n_faces <= 0) return 0;
+  MR_NEED_IMAGE("nudf_meshraster_bounds");
+  MR_LAUNCH(mr_bounds_kernel, a.n_views * a.n_faces, MR_BLOCK, "nudf_meshraster_bounds");
+}
+
+extern "C" int nudf_meshraster_draw_small(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_draw_small"));
+  if (a.n_entries <= 0) return 0;
+  MR_NEED_IMAGE("nudf_meshraster_draw_small");
+  MR_LAUNCH(mr_draw_small_kernel, a.n_entries, MR_BLOCK, "nudf_meshraster_draw_small");
+}
+
+extern "C" int nudf_meshraster_draw_large(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_draw_large"));
+  if (a.n_entries <= 0) return 0;
+  MR_NEED_IMAGE("nudf_meshraster_draw_large");
+  MR_LAUNCH(mr_draw_large_kernel, a.n_entries, MR_BLOCK / MR_WAVE, "nudf_meshraster_draw_large");
+}
+
+extern "C" int nudf_meshraster_resolve(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_resolve"));
+  if (a.n_views <= 0) return 0;
+  MR_NEED_IMAGE("nudf_meshraster_resolve");
+  MR_LAUNCH(mr_resolve_kernel, (int64_t)a.n_views * a.H * a.W, MR_BLOCK, "nudf_meshraster_resolve");
+}
+
+extern "C" int nudf_meshraster_visible(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_visible"));
+  if (a.n_views <= 0 || a.n_verts <= 0) return 0;
+  MR_NEED_IMAGE("nudf_meshraster_visible");
+  MR_LAUNCH(mr_visible_kernel, a.n_views * a.n_verts, MR_BLOCK, "nudf_meshraster_visible");
+}
+
+extern "C" int nudf_meshraster_colour(const NudfMeshRaster* args, void* stream) {
+  const NudfMeshRaster& a = *args;
+  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_colour"));
+  if (a.n_verts <= 0) return 0;
+  if (a.n_views > 0) { MR_NEED_IMAGE("nudf_meshraster_colour"); }
+  MR_LAUNCH(mr_colour_kernel, a.n_verts, MR_BLOCK, "nudf_meshraster_colour");
+}

@@ -514,7 +514,9 @@ class Trainer:
         keep_largest), all off by default, and its sparse=True, block, lipschitz (query and mesh only the blocks near the
         surface: the same mesh as long as the UDF is no steeper than `lipschitz`, resolutions up to 4096), and
         orient=True / outward_from=(x, y, z) in the box's coordinates (wind the faces of every orientable component
-        consistently as the last step, away from that point when given)."""
+        consistently as the last step, away from that point when given), and color_from=(world_mats, images) -- the pair
+        meshrender.dataset_views gives for the training source --, which colours the vertices from the images and adds the
+        colours, np.float32 [V, 3], as a third value."""
         from . import meshing
         if world_space and scale_mat is None:
             raise ValueError("world_space=True needs scale_mat (the dataset's scale_mats_np[0])")
