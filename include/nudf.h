@@ -83,8 +83,6 @@ typedef struct NudfGemmNN {
 
 /* C[M,N] = epilogue(A[M,K] B[K,N]) */
 int nudf_gemm_nn(const NudfGemmNN* args, void* stream);
-/* tuning hook: 0 = auto tile choice (default), 1..4 force a tile/buffering variant; returns the old value */
-int nudf_set_gemm_variant(int variant);
 
 typedef struct NudfGemmTN {
   const float* A1; int32_t lda1; int32_t na1;   /* [M, na1]                               */
@@ -160,7 +158,7 @@ int64_t nudf_gemm_tn_grouped_workspace(const NudfGemmTNGroup* args);
 int nudf_gemm_tn_grouped_plan(const NudfGemmTNGroup* args, int32_t* out, int capacity);
 /* which kernel nudf_gemm_tn_grouped gives this group (host code only: the launcher's own plan, checks and selection; nothing
  * the group points to is read, nothing is launched).  name (capacity bytes) receives gemm_tn_group_kernel (the generic fp32-image
- * kernel), gemm_tn16_group_kernel, gemm_tn3_group_kernel, gemm_tn3w_group_kernel or gemm_tn2_group_kernel, and out[0..3] =
+ * kernel), gemm_tn16_group_kernel, gemm_tn3_group_kernel or gemm_tn2_group_kernel, and out[0..3] =
  * {grid.x, block.x, grid.x of the tn_reduce_kernel launch that follows (workspace path) or 0, 0}.  Returns what
  * nudf_gemm_tn_grouped would return before launching: 0, or the error of a refused group (text in nudf_last_error, empty
  * name, zero grids).  An empty group gives 0, an empty name and zero grids. */
@@ -170,9 +168,8 @@ int nudf_gemm_tn_grouped_kernel(const NudfGemmTNGroup* args, char* name, int cap
  * tiles, 64 = tile-major workgroup order instead of the XCD-aware one, 128 = full fp32 tiles through the generic k-loop
  * instead of the interleaved one, 256 = 16-bit MFMA mode (prec != 0) through the generic kernel's fp32 LDS image instead of
  * the packed k-pair image (bit-identical C either way), 512 = bf16x3 mode through the generic kernel (split on the way out of
- * the fp32 image), 1024 = bf16x3 mode through the WIDE kernel (one 8-wave workgroup per pair of vertically adjacent tiles,
- * double-buffered split image; bit-identical on equal row chunks, measured slower: opt-in), 2048 = bf16x3 split-image kernel:
- * every k-step through the generic staging.  Bits 2 and 4 (once timing-only: wrong results) are retired and ignored.
+ * the fp32 image), 2048 = bf16x3 split-image kernel: every k-step through the generic staging.  Bits 2 and 4 (once
+ * timing-only: wrong results) and 1024 (the wide bf16x3 kernel: measured slower, deleted) are retired and ignored.
  * Default 0 (env NUDF_TN_FLAGS). */
 int nudf_set_tn_flags(int flags);
 /* tuning only: device buffer of >= 4 int64 per workgroup receiving {start, end} (wall_clock64, 100 MHz), tile layout * 16
@@ -267,10 +264,6 @@ int nudf_partial_sums(const float* ws, int nblk, int K, float* out, void* stream
 int nudf_composite_colour_finish(const float* sums_color, const float* sums_color_base, int N, int S,
                                  const float* background_rgb, const float* wsum_all, float* out_color,
                                  float* out_color_base, void* stream);
-/* Layout of the FULL case (S = 128 / 256 / 512 inside samples, no outside samples, no diagnostics): 1 = lane l owns
- * S/64 consecutive samples (16-byte vector accesses), 0 (default) = sample i in lane i % 64 for every shape.  Same
- * arithmetic, different association of the two product scans; A-B switch (the two measure the same on MI355X). */
-void nudf_set_composite_blocked(int on);
 
 /* ------------------------------------------------------------------------------------
  * Hierarchical importance re-sampling (no autograd), one wavefront per ray.
@@ -462,7 +455,6 @@ int nudf_posenc_vjp(const float* x, int xld, int D, int L, float in_scale, int P
                     float scale1, const float* src2, int ld2, float scale2, float* g, void* stream);
 int nudf_copy_cols(const float* src, int lds, int sdiv, float* dst, int ldd, int ncols, int P, float scale,
                    void* stream);
-int nudf_add_cols(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int P, int C, void* stream);
 
 /* heads of the MLP chains */
 int nudf_udf_grad_seed(const float* sign, const float* w_row0, const float* h, int ldh, float hscale, int P, int C,
@@ -634,9 +626,8 @@ typedef struct NudfChain {
   int32_t x_div;                   /* x row of point p is p / x_div (samples per ray for per-ray directions; >= 1) */
   int32_t tile_rows;               /* 0 = choose; 32 / 64 points per workgroup (shared tile); 66 = 64-point shared tile,
                                       transposed product (16-byte epilogue accesses); 128 = prefer the wave-private
-                                      kernel (4 waves x 32 points); 130 = two 64-point tiles per workgroup run in
-                                      anti-phase (mlp_chain_pair_kernel: opt-in, a measured counter-example -- NUDF_CHAIN_PAIR);
-                                      66 / 128 / 130 need fp32 steps and 16-byte aligned rows and fall back
+                                      kernel (4 waves x 32 points);
+                                      66 / 128 need fp32 steps and 16-byte aligned rows and fall back
                                       to 64 otherwise (NUDF_CH_TILE_* below; nudf_mlp_chain_plan tells what a launch gets) */
   int32_t lda0, ldg0;
   int32_t pe_L, pe_jvp;            /* positional encoding: frequencies, 1 = JVP with tangent v       */
@@ -680,7 +671,6 @@ typedef struct NudfChain {
 } NudfChain;
 #define NUDF_CH_TILE_TQ 66            /* NudfChain.tile_rows: the transposed-product shared tile (mlp_chain_tq_kernel)  */
 #define NUDF_CH_TILE_ROWS 128         /* ... the wave-private kernel (mlp_chain_rows_kernel)                            */
-#define NUDF_CH_TILE_PAIR 130         /* ... paired transposed-product tiles (mlp_chain_pair_kernel)                    */
 #if defined(__cplusplus)
 static_assert(sizeof(NudfChain) <= 4096, "NudfChain travels by value: the kernel-argument segment holds 4 KB");
 #endif
@@ -690,7 +680,7 @@ int nudf_mlp_chain(const NudfChain* args, void* stream);
  * source -- "mlp_chain_kernel<64, 2>", "mlp_chain_tq_kernel<1, 3, true>", ... -- and out[0..3] = {grid.x, block.x, 0, 0}.
  * Returns what nudf_mlp_chain would return before launching: 0, or the error of a refused descriptor (text in
  * nudf_last_error, empty name, zero grid).  An empty launch (P <= 0 or no steps) gives 0, an empty name and a zero grid.
- * The choice depends on the process-wide settings NUDF_CHAIN_ROWS / _QUAD / _PAIR / _T16 / _WIN2. */
+ * The choice depends on the process-wide settings NUDF_CHAIN_ROWS / _QUAD / _T16 / _WIN2. */
 int nudf_mlp_chain_plan(const NudfChain* args, char* name, int capacity, int32_t* out);
 /* NUDF_CH_MAX_STEPS of the header the library was compiled against: the array bound sets sizeof(NudfChain), so a caller that
  * passes the struct by reference checks it as it checks nudf_version() (the Python loader refuses a library that differs). */

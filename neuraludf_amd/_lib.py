@@ -266,9 +266,9 @@ EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMO
 
 # every symbol include/nudf.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
-    "nudf_version", "nudf_chain_max_steps", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_set_gemm_variant", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_gemm_tn_grouped_kernel", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
-    "nudf_composite_bwd", "nudf_partial_sums", "nudf_composite_colour_finish", "nudf_set_composite_blocked", "nudf_upsample", "nudf_merge", "nudf_merge_points", "nudf_coarse_z", "nudf_coarse_start", "nudf_outside_z",
-    "nudf_ray_points", "nudf_posenc", "nudf_posenc_vjp", "nudf_copy_cols", "nudf_add_cols",
+    "nudf_version", "nudf_chain_max_steps", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_gemm_tn_grouped_kernel", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
+    "nudf_composite_bwd", "nudf_partial_sums", "nudf_composite_colour_finish", "nudf_upsample", "nudf_merge", "nudf_merge_points", "nudf_coarse_z", "nudf_coarse_start", "nudf_outside_z",
+    "nudf_ray_points", "nudf_posenc", "nudf_posenc_vjp", "nudf_copy_cols",
     "nudf_udf_grad_seed", "nudf_udf_head_bwd", "nudf_signed_colsum", "nudf_sigmoid_head_bwd",
     "nudf_weightnorm_pack", "nudf_weightnorm_unpack_grad",
     "nudf_pixel_blend_fwd", "nudf_pixel_blend_bwd", "nudf_pixel_composite_fwd", "nudf_pixel_composite_bwd",
@@ -319,7 +319,6 @@ _ARGTYPES = {
     "nudf_posenc": [_P, _I, _I, _P, _I, _I, _F, _I, _P, _I, _F, _P, _I, _F, _P],
     "nudf_posenc_vjp": [_P, _I, _I, _I, _F, _I, _P, _I, _F, _P, _I, _F, _P, _P],
     "nudf_copy_cols": [_P, _I, _I, _P, _I, _I, _I, _F, _P],
-    "nudf_add_cols": [_P, _I, _P, _I, _P, _I, _I, _I, _P],
     "nudf_udf_grad_seed": [_P, _P, _P, _I, _F, _I, _I, _F, _P, _I, _P],
     "nudf_udf_head_bwd": [_P, _P, _P, _I, _I, _I, _F, _P, _I, _P],
     "nudf_signed_colsum": [_P, _P, _I, _I, _I, _F, _P, _P],

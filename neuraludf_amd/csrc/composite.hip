@@ -744,375 +744,6 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(NudfComposite p, Nud
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// "blocked" layout of the FULL case (S = 64 * PER inside samples, no outside samples, no diagnostics): lane l owns
-// the PER CONSECUTIVE samples l * PER .. l * PER + PER - 1 instead of samples l, l + 64, ...  Every per-sample array
-// of a ray is then read / written as 16-byte vectors by 64 lanes = whole contiguous kilobytes (the [S,3] arrays
-// were 12-byte-per-lane loads before: the access pattern, not the arithmetic, capped the kernel at 5.6 TB/s,
-// scripts/ubench/stream_probe.hip).  The scans become a lane-local sequential product / sum over PER values plus one
-// DPP scan of the lane totals -- the same association as torch.cumprod inside a lane.
-// ------------------------------------------------------------------------------------------
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// K contiguous floats starting at (wave-uniform base) + off; K in {2, 4, 6, 8, 12, 24}: 8-byte alignment for K = 2 / 6,
-// 16-byte otherwise (row length S * {1,3} * 4 bytes with S a multiple of 128)
-template <int K>
-__device__ __forceinline__ void blk_load(const float* __restrict__ base, unsigned off, float (&d)[K]) {
-  if (K % 4 == 0) {
-#pragma unroll
-    for (int j = 0; j < K / 4; ++j) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(base + (off + 4u * j));
-      d[4 * j] = v[0]; d[4 * j + 1] = v[1]; d[4 * j + 2] = v[2]; d[4 * j + 3] = v[3];
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < K / 2; ++j) {
-      const f32x2 v = *reinterpret_cast<const f32x2*>(base + (off + 2u * j));
-      d[2 * j] = v[0]; d[2 * j + 1] = v[1];
-    }
-  }
-}
-template <int K>
-__device__ __forceinline__ void blk_store(float* __restrict__ base, unsigned off, const float (&d)[K]) {
-  if (K % 4 == 0) {
-#pragma unroll
-    for (int j = 0; j < K / 4; ++j) {
-      const f32x4 v = {d[4 * j], d[4 * j + 1], d[4 * j + 2], d[4 * j + 3]};
-      *reinterpret_cast<f32x4*>(base + (off + 4u * j)) = v;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < K / 2; ++j) {
-      const f32x2 v = {d[2 * j], d[2 * j + 1]};
-      *reinterpret_cast<f32x2*>(base + (off + 2u * j)) = v;
-    }
-  }
-}
-// exclusive prefix products over the ray's samples in order: q[c] of lane l precedes q[c + 1], lane l precedes l + 1
-template <int PER>
-__device__ __forceinline__ void blk_excl_cumprod(const float (&q)[PER], float (&ex)[PER]) {
-  float lp = 1.0f;
-#pragma unroll
-  for (int c = 0; c < PER; ++c) {
-    ex[c] = lp;
-    lp *= q[c];
-  }
-  const float E = wave_shift_up1(wave_incl_scan_mul(lp), 1.0f);
-#pragma unroll
-  for (int c = 0; c < PER; ++c) ex[c] *= E;
-}
-// exclusive suffix sums: out[c] = sum of v over all samples AFTER (l, c)
-template <int PER>
-__device__ __forceinline__ void blk_excl_rsum(const float (&v)[PER], float (&out)[PER]) {
-  float ls = 0.0f;
-#pragma unroll
-  for (int c = PER - 1; c >= 0; --c) {
-    out[c] = ls;
-    ls += v[c];
-  }
-  const float after = wave_incl_rscan_add(ls) - ls;      // lanes > l
-#pragma unroll
-  for (int c = 0; c < PER; ++c) out[c] += after;
-}
-
-template <int PER>
-__global__ __launch_bounds__(256) void composite_fwd_blk_kernel(NudfComposite p, int32_t* status) {
-  NUDF_COMPOSITE_SCHED(p)
-  const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int ray = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-  __shared__ float red[4][5];
-  float s_relax_n = 0.f, s_relax_d = 0.f, s_near_n = 0.f, s_near_d = 0.f, s_sparse = 0.f;
-  if (ray < p.N) {
-    const int S = p.S;
-    RayConst rc;
-    rc.ox = p.rays_o[ray * 3 + 0]; rc.oy = p.rays_o[ray * 3 + 1]; rc.oz = p.rays_o[ray * 3 + 2];
-    rc.dx = p.rays_d[ray * 3 + 0]; rc.dy = p.rays_d[ray * 3 + 1]; rc.dz = p.rays_d[ray * 3 + 2];
-    comp_scalars(p, rc.inv_s, rc.beta, rc.gamma); rc.sdist = p.sample_dist[0];
-    const RayRows rr = ray_rows(p, ray);
-    const unsigned o1 = (unsigned)l * PER, o3 = (unsigned)l * PER * 3u;
-    float zv[PER], uv[PER], gv[3 * PER], cv[3 * PER], bv[3 * PER];
-    blk_load<PER>(rr.z, o1, zv);
-    blk_load<PER>(rr.udf, o1, uv);
-    blk_load<3 * PER>(rr.grad, o3, gv);
-    blk_load<3 * PER>(rr.color, o3, cv);
-    blk_load<3 * PER>(rr.color_base, o3, bv);
-    const float z_nl = wave_shift_down1(zv[0], 0.0f);          // first sample of the next lane
-
-    float tcv[PER], aocc[PER], apv[PER], amv[PER], flipv[PER], midv[PER];
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const int i = l * PER + c;
-      RawSample r;
-      r.z = zv[c]; r.zn = (c + 1 < PER) ? zv[(c + 1 < PER) ? c + 1 : c] : z_nl;
-      r.u = uv[c]; r.gx = gv[3 * c]; r.gy = gv[3 * c + 1]; r.gz = gv[3 * c + 2];
-      PerSample s;
-      eval_sample(p, rc, i, r, s);
-      tcv[c] = s.tc; aocc[c] = s.aocc; flipv[c] = s.flip; midv[c] = s.mid;
-      const float ic = iter_cos_of(-fabsf(s.tc), p.has_anneal, p.cos_anneal);
-      apv[c] = clip01(alpha_raw_f(p.alpha_type, s.u, ic, s.dist, rc.inv_s));
-      amv[c] = clip01(alpha_raw_f(p.alpha_type, -s.u, ic, s.dist, rc.inv_s));
-      const float pn = CSQRT(s.px * s.px + s.py * s.py + s.pz * s.pz);
-      const float ge = (s.gm - 1.0f) * (s.gm - 1.0f);
-      if (pn < 1.2f) { s_relax_n += ge; s_relax_d += 1.0f; }
-      if (s.u < 0.05f) { s_near_n += ge; s_near_d += 1.0f; }
-      s_sparse += CEXP(-p.sparse_scale * s.u);
-    }
-    // visibility probability (:400-412)
-    const float tc_nl = wave_shift_down1(tcv[0], 0.0f);
-    float q[PER], ex[PER], alpha[PER];
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const int i = l * PER + c;
-      const float tnext = (c + 1 < PER) ? tcv[(c + 1 < PER) ? c + 1 : c] : tc_nl;
-      const float vm = (i < S - 1) ? ((tnext < 0.01f) ? 1.0f : 0.0f) : 1.0f;
-      q[c] = clip01(1.0f - aocc[c] + p.flip_saturation * vm) + 1e-7f;
-    }
-    blk_excl_cumprod<PER>(q, ex);
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const float vis = clip01(ex[c]);
-      alpha[c] = apv[c] * vis + amv[c] * (1.0f - vis);
-      q[c] = 1.0f - alpha[c] + 1e-7f;
-    }
-    // transmittance + weighted sums (:508-526, 568)
-    blk_excl_cumprod<PER>(q, ex);
-    float w[PER];
-    float a[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      w[c] = alpha[c] * ex[c];
-      a[0] += w[c] * cv[3 * c]; a[1] += w[c] * cv[3 * c + 1]; a[2] += w[c] * cv[3 * c + 2];
-      a[3] += w[c] * bv[3 * c]; a[4] += w[c] * bv[3 * c + 1]; a[5] += w[c] * bv[3 * c + 2];
-      a[6] += w[c] * midv[c];
-      a[7] += w[c] * flipv[c] * gv[3 * c]; a[8] += w[c] * flipv[c] * gv[3 * c + 1]; a[9] += w[c] * flipv[c] * gv[3 * c + 2];
-      a[10] += w[c];
-    }
-    blk_store<PER>(p.weights + (size_t)ray * S, o1, w);
-    a[11] = a[10];
-    wave_sum_n<12>(a);
-    if (l == 0) {
-      float bgr = 0.f, bgg = 0.f, bgb = 0.f;
-      if (p.background_rgb) {
-        bgr = p.background_rgb[0] * (1.0f - a[11]);
-        bgg = p.background_rgb[1] * (1.0f - a[11]);
-        bgb = p.background_rgb[2] * (1.0f - a[11]);
-      }
-      p.out_color[ray * 3 + 0] = a[0] + bgr; p.out_color[ray * 3 + 1] = a[1] + bgg; p.out_color[ray * 3 + 2] = a[2] + bgb;
-      p.out_color_base[ray * 3 + 0] = a[3]; p.out_color_base[ray * 3 + 1] = a[4]; p.out_color_base[ray * 3 + 2] = a[5];
-      p.out_depth[ray] = a[6];
-      p.out_normals[ray * 3 + 0] = a[7]; p.out_normals[ray * 3 + 1] = a[8]; p.out_normals[ray * 3 + 2] = a[9];
-      p.out_wsum[ray] = a[10];
-      p.out_wsum_all[ray] = a[11];
-      if (status && !(fabsf(((a[11] + a[6]) + (a[0] + a[1])) + ((a[2] + a[3]) + (a[4] + a[5]))) <= 3.0e38f))
-        atomicOr(status, NUDF_STATUS_NONFINITE_RENDER);
-    }
-  }
-  {
-    float r[5] = {s_relax_n, s_relax_d, s_near_n, s_near_d, s_sparse};
-    wave_sum_n<5>(r);
-    if (l == 0) {
-      red[wave][0] = r[0]; red[wave][1] = r[1]; red[wave][2] = r[2]; red[wave][3] = r[3]; red[wave][4] = r[4];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-    if (p.ws) p.ws[(size_t)blockIdx.x * 5 + threadIdx.x] = t;
-    else atomicAdd(p.sums + threadIdx.x, t);
-  }  comp_scalars_out(p, status);
-}
-
-template <int PER>
-__global__ __launch_bounds__(256) void composite_bwd_blk_kernel(NudfComposite p, NudfCompositeGrad g) {
-  NUDF_COMPOSITE_SCHED(p)
-  const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
-  const int ray = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-  __shared__ float red[4][3];
-  float d_invs = 0.f, d_beta = 0.f, d_gamma = 0.f;
-  if (ray < p.N) {
-    const int S = p.S;
-    RayConst rc;
-    rc.ox = p.rays_o[ray * 3 + 0]; rc.oy = p.rays_o[ray * 3 + 1]; rc.oz = p.rays_o[ray * 3 + 2];
-    rc.dx = p.rays_d[ray * 3 + 0]; rc.dy = p.rays_d[ray * 3 + 1]; rc.dz = p.rays_d[ray * 3 + 2];
-    comp_scalars(p, rc.inv_s, rc.beta, rc.gamma); rc.sdist = p.sample_dist[0];
-    const float dCr = g.d_color ? g.d_color[ray * 3 + 0] : 0.f, dCg = g.d_color ? g.d_color[ray * 3 + 1] : 0.f,
-                dCb = g.d_color ? g.d_color[ray * 3 + 2] : 0.f;
-    const float dBr = g.d_color_base ? g.d_color_base[ray * 3 + 0] : 0.f,
-                dBg = g.d_color_base ? g.d_color_base[ray * 3 + 1] : 0.f,
-                dBb = g.d_color_base ? g.d_color_base[ray * 3 + 2] : 0.f;
-    const float dDepth = g.d_depth ? g.d_depth[ray] : 0.f;
-    const float dNx = g.d_normals ? g.d_normals[ray * 3 + 0] : 0.f, dNy = g.d_normals ? g.d_normals[ray * 3 + 1] : 0.f,
-                dNz = g.d_normals ? g.d_normals[ray * 3 + 2] : 0.f;
-    const float dWs = g.d_wsum ? g.d_wsum[ray] : 0.f;
-    float dWall = g.d_wsum_all ? g.d_wsum_all[ray] : 0.f;
-    if (p.background_rgb && g.d_color)
-      dWall -= dCr * p.background_rgb[0] + dCg * p.background_rgb[1] + dCb * p.background_rgb[2];
-    const float k_relax = g.d_sums ? g.d_sums[0] : 0.f, k_near = g.d_sums ? g.d_sums[2] : 0.f,
-                k_sparse = g.d_sums ? g.d_sums[4] : 0.f;
-
-    const RayRows rr = ray_rows(p, ray);
-    const unsigned o1 = (unsigned)l * PER, o3 = (unsigned)l * PER * 3u;
-    float zv[PER], uv[PER], gv[3 * PER], dwup[PER], cdot[PER];
-    blk_load<PER>(rr.z, o1, zv);
-    blk_load<PER>(rr.udf, o1, uv);
-    blk_load<3 * PER>(rr.grad, o3, gv);
-    {
-      float cv[3 * PER], bv[3 * PER];
-      blk_load<3 * PER>(rr.color, o3, cv);
-      blk_load<3 * PER>(rr.color_base, o3, bv);
-#pragma unroll
-      for (int c = 0; c < PER; ++c)      // the colours only enter the backward through <upstream, colour>
-        cdot[c] = dCr * cv[3 * c] + dCg * cv[3 * c + 1] + dCb * cv[3 * c + 2] + dBr * bv[3 * c] + dBg * bv[3 * c + 1] +
-                  dBb * bv[3 * c + 2];
-    }
-    if (g.d_weights) {
-      blk_load<PER>(g.d_weights + (size_t)ray * S, o1, dwup);
-    } else {
-#pragma unroll
-      for (int c = 0; c < PER; ++c) dwup[c] = 0.f;
-    }
-    const float z_nl = wave_shift_down1(zv[0], 0.0f);
-
-    PerSample ps[PER];
-    float icv[PER], q[PER], inner[PER], Vraw[PER], vis[PER], ap_raw[PER], am_raw[PER], alpha[PER], f[PER], T[PER], w[PER],
-        dw[PER];
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const int i = l * PER + c;
-      RawSample r;
-      r.z = zv[c]; r.zn = (c + 1 < PER) ? zv[(c + 1 < PER) ? c + 1 : c] : z_nl;
-      r.u = uv[c]; r.gx = gv[3 * c]; r.gy = gv[3 * c + 1]; r.gz = gv[3 * c + 2];
-      eval_sample(p, rc, i, r, ps[c]);
-      icv[c] = iter_cos_of(-fabsf(ps[c].tc), p.has_anneal, p.cos_anneal);
-    }
-    const float tc_nl = wave_shift_down1(ps[0].tc, 0.0f);
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const int i = l * PER + c;
-      const float tnext = (c + 1 < PER) ? ps[(c + 1 < PER) ? c + 1 : c].tc : tc_nl;
-      const float vm = (i < S - 1) ? ((tnext < 0.01f) ? 1.0f : 0.0f) : 1.0f;
-      inner[c] = 1.0f - ps[c].aocc + p.flip_saturation * vm;
-      q[c] = clip01(inner[c]) + 1e-7f;
-    }
-    blk_excl_cumprod<PER>(q, Vraw);
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      vis[c] = clip01(Vraw[c]);
-      ap_raw[c] = alpha_raw_f(p.alpha_type, ps[c].u, icv[c], ps[c].dist, rc.inv_s);
-      am_raw[c] = alpha_raw_f(p.alpha_type, -ps[c].u, icv[c], ps[c].dist, rc.inv_s);
-      alpha[c] = clip01(ap_raw[c]) * vis[c] + clip01(am_raw[c]) * (1.0f - vis[c]);
-      f[c] = 1.0f - alpha[c] + 1e-7f;
-    }
-    blk_excl_cumprod<PER>(f, T);
-    float ocol[3 * PER], ocb[3 * PER];
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      w[c] = alpha[c] * T[c];
-      dw[c] = dWall + dwup[c] + cdot[c] + dWs + dDepth * ps[c].mid +
-              ps[c].flip * (dNx * ps[c].gx + dNy * ps[c].gy + dNz * ps[c].gz);
-      ocol[3 * c] = w[c] * dCr; ocol[3 * c + 1] = w[c] * dCg; ocol[3 * c + 2] = w[c] * dCb;
-      ocb[3 * c] = w[c] * dBr; ocb[3 * c + 1] = w[c] * dBg; ocb[3 * c + 2] = w[c] * dBb;
-    }
-    if (g.o_d_color) blk_store<3 * PER>(g.o_d_color + (size_t)ray * S * 3, o3, ocol);
-    if (g.o_d_color_base) blk_store<3 * PER>(g.o_d_color_base + (size_t)ray * S * 3, o3, ocb);
-
-    // reverse scan 1: d alpha through the transmittance product
-    float tmp[PER], excl[PER], dalpha[PER], dV_V[PER];
-#pragma unroll
-    for (int c = 0; c < PER; ++c) tmp[c] = dw[c] * w[c];
-    blk_excl_rsum<PER>(tmp, excl);
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      dalpha[c] = dw[c] * T[c] - excl[c] * CRCP(f[c]);
-      const float dvis = dalpha[c] * (clip01(ap_raw[c]) - clip01(am_raw[c]));
-      const float dV = (Vraw[c] >= 0.0f && Vraw[c] <= 1.0f) ? dvis : 0.0f;
-      dV_V[c] = dV * Vraw[c];
-    }
-    // reverse scan 2 through the visibility product, then the local backward
-    blk_excl_rsum<PER>(dV_V, excl);
-    float oud[PER], ogd[3 * PER];
-#pragma unroll
-    for (int c = 0; c < PER; ++c) {
-      const PerSample& s = ps[c];
-      const float dq = excl[c] * CRCP(q[c]);
-      const float daocc = (inner[c] >= 0.0f && inner[c] <= 1.0f) ? -dq : 0.0f;
-      const float rrl = fmaxf(s.raw, 0.0f);
-      const float draw = (s.raw > 0.0f) ? daocc * s.E_occ * rc.gamma * s.dist : 0.0f;
-      d_gamma += daocc * s.E_occ * rrl * s.dist;
-      float ll, dl;
-      logistic_pdf_terms(rc.beta, s.u, ll, dl);
-      float du = draw * rc.beta * rc.beta * dl;
-      d_beta += draw * (ll + rc.beta * s.u * dl);
-      float dic = 0.f;
-      const float dap = dalpha[c] * vis[c], dam = dalpha[c] * (1.0f - vis[c]);
-#pragma unroll
-      for (int sgn = 0; sgn < 2; ++sgn) {
-        const float sign = sgn ? -1.0f : 1.0f;
-        const float a_raw = sgn ? am_raw[c] : ap_raw[c];
-        const float da = sgn ? dam : dap;
-        if (a_raw >= 0.0f && a_raw <= 1.0f) alpha_bwd_f(p.alpha_type, sign, s.u, icv[c], s.dist, rc.inv_s, da, d_invs, du, dic);
-      }
-      const float cc = -fabsf(s.tc);
-      float dic_dc = 1.0f;
-      if (p.has_anneal) dic_dc = 0.5f * (1.0f - p.cos_anneal) + ((cc < 0.0f) ? p.cos_anneal : 0.0f);
-      const float sgn_tc = (s.tc > 0.0f) ? 1.0f : ((s.tc < 0.0f) ? -1.0f : 0.0f);
-      const float dtc = dic * dic_dc * (-sgn_tc);
-      float dgx, dgy, dgz;
-      if (p.use_norm_grad) {
-        const float rg = CRCP(s.gm + 1e-5f);
-        const float dotg = dtc * (rc.dx * s.gx + rc.dy * s.gy + rc.dz * s.gz);
-        const float k2 = (s.gm > 0.0f) ? dotg * CRCP(s.gm) * rg * rg : 0.0f;
-        dgx = dtc * rc.dx * rg - s.gx * k2;
-        dgy = dtc * rc.dy * rg - s.gy * k2;
-        dgz = dtc * rc.dz * rg - s.gz * k2;
-      } else {
-        dgx = dtc * rc.dx; dgy = dtc * rc.dy; dgz = dtc * rc.dz;
-      }
-      dgx += w[c] * s.flip * dNx; dgy += w[c] * s.flip * dNy; dgz += w[c] * s.flip * dNz;
-      const float pn = CSQRT(s.px * s.px + s.py * s.py + s.pz * s.pz);
-      float dgm = 0.f;
-      if (pn < 1.2f) dgm += k_relax * 2.0f * (s.gm - 1.0f);
-      if (s.u < 0.05f) dgm += k_near * 2.0f * (s.gm - 1.0f);
-      if (s.gm > 0.0f) {
-        const float t = dgm * CRCP(s.gm);
-        dgx += t * s.gx; dgy += t * s.gy; dgz += t * s.gz;
-      }
-      du += k_sparse * (-p.sparse_scale) * CEXP(-p.sparse_scale * s.u);
-      oud[c] = du;
-      ogd[3 * c] = dgx; ogd[3 * c + 1] = dgy; ogd[3 * c + 2] = dgz;
-    }
-    blk_store<PER>(g.o_d_udf + (size_t)ray * S, o1, oud);
-    blk_store<3 * PER>(g.o_d_grad + (size_t)ray * S * 3, o3, ogd);
-  }
-  {
-    float r[3] = {d_invs, d_beta, d_gamma};
-    wave_sum_n<3>(r);
-    if (l == 0) { red[wave][0] = r[0]; red[wave][1] = r[1]; red[wave][2] = r[2]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3 && (g.o_d_scal || g.ws)) {
-    float t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-    if (g.ws) g.ws[(size_t)blockIdx.x * 3 + threadIdx.x] = t;
-    else atomicAdd(g.o_d_scal + threadIdx.x, t);
-  }
-}
-
-// The blocked layout is the "float4 SoA" probe VERDICT r1 asked for: with EVERY access a coalesced 16-byte vector it
-// measures the same as the strided kernels (32768 x 256: 82.8 vs 82.5 us forward, 159 vs 148 us backward;
-// profiles/r02_composite_layouts.txt) -- the 12-byte-per-lane loads were not what keeps the pair at 61 % of 8 TB/s.
-// Kept as an A/B switch (NUDF_COMPOSITE_BLOCKED=1 or nudf_set_composite_blocked(1)) and as a second implementation the
-// tests hold against the first; the default stays the strided kernels.
-static int g_composite_blocked = -1;
-static bool composite_blocked_enabled() {
-  if (g_composite_blocked < 0) {
-    const char* e = getenv("NUDF_COMPOSITE_BLOCKED");
-    g_composite_blocked = (e && e[0] == '1') ? 1 : 0;
-  }
-  return g_composite_blocked != 0;
-}
-extern "C" void nudf_set_composite_blocked(int on) { g_composite_blocked = on ? 1 : 0; }
-static bool ptr16(const void* q) { return (((uintptr_t)q) & 15) == 0; }
-
 #define NUDF_MAX_CHUNKS 8
 
 extern "C" int nudf_composite_fwd(const NudfComposite* args, void* stream) {
@@ -1141,15 +772,6 @@ extern "C" int nudf_composite_fwd(const NudfComposite* args, void* stream) {
   const bool diag = p.o_alpha_occ || p.o_raw_occ || p.o_true_cos || p.o_grad_mag || p.o_mid_z || p.o_dists ||
                     p.o_inside || p.o_flip || p.o_vis_prob || p.o_alpha || p.o_alpha_plus || p.o_alpha_minus;
   const bool full = (p.S == 64 * nc) && p.n_out == 0 && p.s_nominal >= p.S;
-  if (full && !diag && p.color && (nc == 2 || nc == 4 || nc == 8) && composite_blocked_enabled() && ptr16(p.z) && ptr16(p.udf) &&
-      ptr16(p.grad) && ptr16(p.color) && ptr16(p.color_base) && ptr16(p.weights)) {
-    if (nc == 2) hipLaunchKernelGGL(composite_fwd_blk_kernel<2>, grid, block, 0, st, p, status);
-    else if (nc == 4) hipLaunchKernelGGL(composite_fwd_blk_kernel<4>, grid, block, 0, st, p, status);
-    else hipLaunchKernelGGL(composite_fwd_blk_kernel<8>, grid, block, 0, st, p, status);
-    if (p.ws && !p.defer_sums) hipLaunchKernelGGL(partial_sums_kernel, dim3(1), dim3(1024), 0, st, p.ws, (int)grid.x, 5, p.sums);
-    NUDF_CHECK_LAUNCH("nudf_composite_fwd");
-    return 0;
-  }
 #define NUDF_CF_LAUNCH(NCV)                                                                                   \
   if (diag) hipLaunchKernelGGL((composite_fwd_kernel<NCV, true, false>), grid, block, 0, st, p, status);      \
   else if (full) hipLaunchKernelGGL((composite_fwd_kernel<NCV, false, true>), grid, block, 0, st, p, status); \
@@ -1192,16 +814,6 @@ extern "C" int nudf_composite_bwd(const NudfComposite* args, const NudfComposite
   dim3 grid((p.N + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
   const bool full = (p.S == 64 * nc) && p.n_out == 0 && p.s_nominal >= p.S;
-  if (full && (nc == 2 || nc == 4 || nc == 8) && composite_blocked_enabled() && ptr16(p.z) && ptr16(p.udf) && ptr16(p.grad) &&
-      ptr16(p.color) && ptr16(p.color_base) && ptr16(grads->d_weights) && ptr16(grads->o_d_udf) && ptr16(grads->o_d_grad) &&
-      ptr16(grads->o_d_color) && ptr16(grads->o_d_color_base) && grads->o_d_udf && grads->o_d_grad) {
-    if (nc == 2) hipLaunchKernelGGL(composite_bwd_blk_kernel<2>, grid, block, 0, st, p, *grads);
-    else if (nc == 4) hipLaunchKernelGGL(composite_bwd_blk_kernel<4>, grid, block, 0, st, p, *grads);
-    else hipLaunchKernelGGL(composite_bwd_blk_kernel<8>, grid, block, 0, st, p, *grads);
-    composite_bwd_reduce(p, *grads, (int)grid.x, st);
-    NUDF_CHECK_LAUNCH("nudf_composite_bwd");
-    return 0;
-  }
 #define NUDF_CB_LAUNCH(NCV)                                                                         \
   if (full) hipLaunchKernelGGL((composite_bwd_kernel<NCV, true>), grid, block, 0, st, p, *grads);   \
   else hipLaunchKernelGGL((composite_bwd_kernel<NCV, false>), grid, block, 0, st, p, *grads)

@@ -3,28 +3,21 @@
 //   gemm_nn : C[M,N]   = epilogue( A[M,K] * B[K,N] )         A,B row-major, K % 32 == 0
 //   (the weight-gradient contraction gemm_tn lives in gemm_tn_f32_mfma.hip)
 //
-// v_mfma_f32_32x32x2_f32 (exact fp32, == an fmaf chain), block tiles up to 128x128x32,
-// 4 waves (2x2), each wave up to a 64x64 sub-tile = 2x2 MFMA tiles, double-buffered LDS.
+// v_mfma_f32_32x32x2_f32 (exact fp32, == an fmaf chain), 64x64x32 block tiles, 4 waves (2x2), each wave one
+// 32x32 MFMA tile, single LDS buffer + register prefetch.
 // These replace the chains of F.linear / weight_norm / Softplus / ReLU / autograd ops of
 // models/fields.py:192-231 (UDFNetwork), :452-495 (ResidualRenderingNetwork), :599-628 (NeRF)
 // and their (double-)backward.  MFMA peak for this instruction: 157.3 TFLOP/s.
 #include "nudf_common.h"
 #include "../../include/nudf.h"
-#include <stdlib.h>
-#include <type_traits>
 
-#define BM 128
-#define BN 128
+#define BM 64
+#define BN 64
 #define BK 32
 #define LDA_S (BM + 1)  // As[k][m]: +1 pad makes the transposing ds_write_b32 conflict-free
 #define LDB_S (BN + 4)  // Bs[k][n]: rows stay 16-byte aligned for ds_write_b128
 #define A_TILE (BK * LDA_S)
 #define B_TILE (BK * LDB_S)
-#define LDT_S (BM + 4)  // TN kernel: both operands are straight copies
-#define T_TILE (BK * LDT_S)
-
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -134,29 +127,28 @@ __device__ __forceinline__ void epilogue_store(const NudfGemmNN& p, int row, int
 }
 
 // ---------------------------------------------------------------------------------------
-// C[M,N] = epilogue(A[M,K] B[K,N]).  Block = 4 waves (2x2); each wave owns (WM*32)x(WN*32) outputs as
-// WMxWN MFMA tiles, so the block tile is (64*WM)x(64*WN).  NBUF = 1: single LDS buffer + register
-// prefetch, two barriers per k-step, small enough (33 KB at 128x128) for 3-4 co-resident blocks per CU
-// whose epilogues (HBM-bound) overlap the other blocks' MFMA phases; NBUF = 2: double-buffered LDS.
+// C[M,N] = epilogue(A[M,K] B[K,N]).  Block = 4 waves (2x2); each wave owns one 32x32 MFMA tile of the 64x64 block
+// tile.  One LDS buffer (17 KB) + register prefetch, two barriers per k-step; many small co-resident blocks, whose epilogues
+// (HBM-bound) overlap the other blocks' MFMA phases.
+// Measured on MI355X (profiles/r01_gemm_variants.txt): the 64x64 tile wins on every shape of this workload over
+// 128x128 (single / double-buffered) and 64x128 -- these layer GEMMs sit at the fp32 ridge (K = 128..256, several
+// [M,N] epilogue operands), so overlapping many small blocks matters more than LDS reuse.  Those variants are retired.
 // ---------------------------------------------------------------------------------------
-template <int EPI, int WM, int WN, int NBUF, int OCC>
-__global__ __launch_bounds__(256, OCC) void gemm_nn_kernel(NudfGemmNN p) {
-  constexpr int TBM = 64 * WM, TBN = 64 * WN;
-  constexpr int LDA = TBM + 1, LDB = TBN + 4;
-  constexpr int ATILE = BK * LDA, BTILE = BK * LDB;
-  constexpr int APASS = TBM / 32, BPASS = TBN / 32;  // float4 loads per thread per k-step
-  __shared__ __attribute__((aligned(16))) float smem[NBUF * (ATILE + BTILE)];
+template <int EPI>
+__global__ __launch_bounds__(256, 6) void gemm_nn_kernel(NudfGemmNN p) {
+  constexpr int APASS = BM / 32, BPASS = BN / 32;  // float4 loads per thread per k-step
+  __shared__ __attribute__((aligned(16))) float smem[A_TILE + B_TILE];
   float* As = smem;
-  float* Bs = smem + NBUF * ATILE;
+  float* Bs = smem + A_TILE;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int tiles_n = (p.N + TBN - 1) / TBN;
+  const int tiles_n = (p.N + BN - 1) / BN;
   const int lb = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int m0 = (lb / tiles_n) * TBM;
-  const int n0 = (lb % tiles_n) * TBN;
+  const int m0 = (lb / tiles_n) * BM;
+  const int n0 = (lb % tiles_n) * BN;
   const int nk = p.K / BK;
 
   int a_off[APASS], b_off[BPASS];
@@ -169,16 +161,16 @@ __global__ __launch_bounds__(256, OCC) void gemm_nn_kernel(NudfGemmNN p) {
     int gr = m0 + row;
     if (gr > p.M - 1) gr = p.M - 1;
     a_off[ps] = gr * p.lda + kq * 4;
-    a_lds[ps] = (kq * 4) * LDA + row;
+    a_lds[ps] = (kq * 4) * LDA_S + row;
   }
 #pragma unroll
   for (int ps = 0; ps < BPASS; ++ps) {
     const int idx = ps * 256 + tid;
-    const int kr = idx / (TBN / 4), c4 = idx % (TBN / 4);
+    const int kr = idx / (BN / 4), c4 = idx % (BN / 4);
     const int gc = n0 + c4 * 4;
     b_ok[ps] = gc < p.ldb;
     b_off[ps] = kr * p.ldb + (b_ok[ps] ? gc : 0);
-    b_lds[ps] = kr * LDB + c4 * 4;
+    b_lds[ps] = kr * LDB_S + c4 * 4;
   }
 
   f32x4 ra[APASS], rb[BPASS];
@@ -191,136 +183,65 @@ __global__ __launch_bounds__(256, OCC) void gemm_nn_kernel(NudfGemmNN p) {
     for (int ps = 0; ps < BPASS; ++ps)
       rb[ps] = b_ok[ps] ? *reinterpret_cast<const f32x4*>(Bk + b_off[ps]) : f32x4{0.f, 0.f, 0.f, 0.f};
   };
-  auto sstore = [&](int buf) {
-    float* as = As + buf * ATILE;
-    float* bs = Bs + buf * BTILE;
+  auto sstore = [&]() {
 #pragma unroll
     for (int ps = 0; ps < APASS; ++ps) {
-      float* d = as + a_lds[ps];
+      float* d = As + a_lds[ps];
       d[0] = ra[ps].x;
-      d[LDA] = ra[ps].y;
-      d[2 * LDA] = ra[ps].z;
-      d[3 * LDA] = ra[ps].w;
+      d[LDA_S] = ra[ps].y;
+      d[2 * LDA_S] = ra[ps].z;
+      d[3 * LDA_S] = ra[ps].w;
     }
 #pragma unroll
-    for (int ps = 0; ps < BPASS; ++ps) *reinterpret_cast<f32x4*>(bs + b_lds[ps]) = rb[ps];
+    for (int ps = 0; ps < BPASS; ++ps) *reinterpret_cast<f32x4*>(Bs + b_lds[ps]) = rb[ps];
   };
 
-  f32x16 acc[WM][WN];
+  f32x16 acc;
 #pragma unroll
-  for (int i = 0; i < WM; ++i)
-#pragma unroll
-    for (int j = 0; j < WN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
 
-  // wave-uniform activity of the column tiles (N may end inside the block tile)
-  const int ncol_act = min(WN, max(0, (p.N - (n0 + wn * 32 * WN) + 31) / 32));
+  // wave-uniform: live column tiles of this wave, 0 or 1 (N may end inside the block tile)
+  const int ncol_act = min(1, max(0, (p.N - (n0 + wn * 32) + 31) / 32));
 
-  auto compute = [&](int buf) {
-    const float* as = As + buf * ATILE + (lane >> 5) * LDA + wm * (32 * WM) + (lane & 31);
-    const float* bs = Bs + buf * BTILE + (lane >> 5) * LDB + wn * (32 * WN) + (lane & 31);
-    if (ncol_act == WN) {
+  auto compute = [&]() {
+    const float* as = As + (lane >> 5) * LDA_S + wm * 32 + (lane & 31);
+    const float* bs = Bs + (lane >> 5) * LDB_S + wn * 32 + (lane & 31);
+    // (a loop over 0 or 1 tiles, not an `if`: hipcc orders the kernel's address arithmetic differently for the `if`, and these
+    // 13 kernels stay instruction for instruction the ones that were measured)
+    for (int j = 0; j < ncol_act; ++j) {
 #pragma unroll
-      for (int kk = 0; kk < BK / 2; ++kk) {
-        float a[WM], b[WN];
-#pragma unroll
-        for (int i = 0; i < WM; ++i) a[i] = as[(2 * kk) * LDA + 32 * i];
-#pragma unroll
-        for (int j = 0; j < WN; ++j) b[j] = bs[(2 * kk) * LDB + 32 * j];
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-          for (int j = 0; j < WN; ++j) acc[i][j] = mfma32(a[i], b[j], acc[i][j]);
-      }
-    } else if (ncol_act > 0) {  // only the first column tile is live (WN == 2)
-#pragma unroll
-      for (int kk = 0; kk < BK / 2; ++kk) {
-        const float b0 = bs[(2 * kk) * LDB];
-#pragma unroll
-        for (int i = 0; i < WM; ++i) acc[i][0] = mfma32(as[(2 * kk) * LDA + 32 * i], b0, acc[i][0]);
-      }
+      for (int kk = 0; kk < BK / 2; ++kk) acc = mfma32(as[(2 * kk) * LDA_S], bs[(2 * kk) * LDB_S], acc);
     }
   };
 
-  if (NBUF == 2) {
-    gload(0);
-    sstore(0);
+  gload(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    sstore();
     __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) gload(kt + 1);
-      compute(cur);
-      if (kt + 1 < nk) sstore(cur ^ 1);
-      __syncthreads();
-    }
-  } else {
-    gload(0);
-    for (int kt = 0; kt < nk; ++kt) {
-      sstore(0);
-      __syncthreads();
-      if (kt + 1 < nk) gload(kt + 1);
-      compute(0);
-      __syncthreads();
-    }
+    if (kt + 1 < nk) gload(kt + 1);
+    compute();
+    __syncthreads();
   }
 
   if (ncol_act == 0) return;
+  const int col = n0 + wn * 32 + (lane & 31);
+  if (col >= p.N) return;
 #pragma unroll
-  for (int i = 0; i < WM; ++i) {
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-      if (j >= ncol_act) continue;
-      const int col = n0 + wn * (32 * WN) + j * 32 + (lane & 31);
-      if (col >= p.N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * (32 * WM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < p.M) epilogue_store<EPI>(p, row, col, acc[i][j][r]);
-      }
-    }
+  for (int r = 0; r < 16; ++r) {
+    const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    if (row < p.M) epilogue_store<EPI>(p, row, col, acc[r]);
   }
 }
 
 // ---------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------
-template <int EPI, int WM, int WN, int NBUF, int OCC>
-static int launch_cfg(const NudfGemmNN& p, hipStream_t st) {
-  const int tiles = ((p.M + 64 * WM - 1) / (64 * WM)) * ((p.N + 64 * WN - 1) / (64 * WN));
-  hipLaunchKernelGGL((gemm_nn_kernel<EPI, WM, WN, NBUF, OCC>), dim3(tiles), dim3(256), 0, st, p);
-  NUDF_CHECK_LAUNCH("nudf_gemm_nn");
-  return 0;
-}
-
-static int g_variant = -1;  // NUDF_GEMM_VARIANT: 0 auto, 1 = 128x128 double-buffered, 2 = 128x128 single,
-                            // 3 = 64x128 single, 4 = 64x64 single   (tuning / A-B measurements only)
-extern "C" int nudf_set_gemm_variant(int v) {
-  const int old = g_variant;
-  g_variant = v;
-  return old;
-}
-
 template <int EPI>
 static int launch_nn(const NudfGemmNN& p, hipStream_t st) {
-  if (g_variant < 0) {
-    const char* e = getenv("NUDF_GEMM_VARIANT");
-    g_variant = e ? atoi(e) : 0;
-  }
-  int v = g_variant;
-  if (v == 0) {
-    // measured on MI355X (scripts/gemm_bench.py, profiles/r01_gemm_variants.txt): the 64x64 tile at 8 waves/SIMD
-    // wins on every shape of this workload -- these layer GEMMs sit at the fp32 ridge (K = 128..256, several
-    // [M,N] epilogue operands), so overlapping many small blocks' epilogues with other blocks' MFMA phases
-    // matters more than LDS reuse; 64x128 is within 5 % on M = 32768
-    v = 4;
-  }
-  switch (v) {
-    case 1: return launch_cfg<EPI, 2, 2, 2, 2>(p, st);
-    case 2: return launch_cfg<EPI, 2, 2, 1, 4>(p, st);
-    case 3: return launch_cfg<EPI, 1, 2, 1, 4>(p, st);
-    default: return launch_cfg<EPI, 1, 1, 1, 6>(p, st);
-  }
+  const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+  hipLaunchKernelGGL((gemm_nn_kernel<EPI>), dim3(tiles), dim3(256), 0, st, p);
+  NUDF_CHECK_LAUNCH("nudf_gemm_nn");
+  return 0;
 }
 
 extern "C" int nudf_gemm_nn(const NudfGemmNN* args, void* stream) {

@@ -33,11 +33,12 @@
 #define T_TILE (BK * LDT)
 #define TN_MAX_TILES 64
 #define TN_WS_TILE (BM * BN + BM)   // floats per workspace slot: 4 waves x 4 sub-tiles x 64 lanes x 16 accumulators + bias
-// Bits 2 ("drop the epilogue") and 4 ("skip the bias sums") computed wrong results on purpose and are RETIRED: the host masks
-// them off (nudf_set_tn_flags, NUDF_TN_FLAGS), so no kernel ever sees them set.  The three split-image kernels (tn3, tn2,
-// tn3w) still carry the two tests: without them hipcc hoists epilogue address arithmetic into the staging code and
+// Bits 2 ("drop the epilogue") and 4 ("skip the bias sums") computed wrong results on purpose, and bit 1024 selected the wide
+// bf16x3 kernel, which measured 8-12 % slower (profiles/r05_tn_wide.txt) and is deleted.  All three are RETIRED: the host masks
+// them off (nudf_set_tn_flags, NUDF_TN_FLAGS), so no kernel ever sees them set.  The two split-image kernels (tn3, tn2) still
+// carry the tests of bits 2 and 4: without them hipcc hoists epilogue address arithmetic into the staging code and
 // reschedules it, and an unmeasured reshuffle of those kernels is not worth two dead scalar tests.
-#define TNF_RETIRED (2 | 4)
+#define TNF_RETIRED (2 | 4 | 1024)
 #define TNF_NO_EPILOGUE 2
 #define TNF_NO_BIAS 4
 #define TNF_ATOMICS 8
@@ -49,9 +50,6 @@
 #define TNF_NO_SPLIT_IMAGE 512      // bf16x3 mode through the generic kernel (split on the way out of the fp32 image; A/B of gemm_tn3_group_kernel)
 #define TNF_GENERIC_STAGE 2048      // bf16x3 split-image kernel: every k-step through the generic (clamped-address) staging: A/B of the
                                     // loop-invariant addressing of round 5; bit-identical
-#define TNF_WIDE 1024               // bf16x3 mode: the wide double-buffered kernel (gemm_tn3w_group_kernel) instead of the 128 x 128
-                                    // two-barrier one -- opt-in: bit-identical on equal row chunks, measured 8-12 % SLOWER
-                                    // (profiles/r05_tn_wide.txt)
 
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -73,16 +71,7 @@ struct TnPlan {
   TnTile tile[TN_MAX_TILES + 1];   // tile[n_tiles].blk_start = total workgroups
   int n_tiles, M, prec, flags;
   int grid_blocks;                 // workgroups launched (>= tile[n_tiles].blk_start: the XCD-aware order leaves holes, which exit)
-  short partner[TN_MAX_TILES];     // wide bf16x3 kernel (gemm_tn3w_group_kernel): >= 0 = this tile leads a pair with the tile one
-                                   // tile row below (same problem, same tile column, same chunks); -1 = a leader without partner;
-                                   // -2 = follower (its workgroups exit: the leader's workgroup computes both tiles)
   int assign;                      // reduce kernel: C = 0 + sum instead of C += sum
-  int wide;                        // the wide bf16x3 kernel runs this plan (partner[] is set)
-  short unit_tile[TN_MAX_TILES];   // wide kernel: workgroup unit u = the leader (or unpaired) tile unit_tile[u] ...
-  int n_units, unit_chunks;        // ... and its row chunks: blockIdx = u * unit_chunks + chunk.  n_units * unit_chunks <= 256
-                                   // workgroups, one per CU and 32 per XCD whatever the chunk count (the 128 x 128 kernels'
-                                   // XCD-aware order puts a chunk's tiles on ONE XCD: 13 chunks x 19 units would load five
-                                   // XCDs with 38 one-per-CU workgroups and three with 19 -- two rounds, measured 2x slower)
   float* ws;
   long long* dbg;                  // tuning: per workgroup {start, end} of wall_clock64 (100 MHz), layout, n
   const float* amax_a;             // f16x2 mode (prec 4): device scalars holding max |A| / max |B| over the group's operands
@@ -1545,263 +1534,6 @@ __global__ __launch_bounds__(256, 2) void gemm_tn2_group_kernel(TnPlan g) {
   }
 }
 
-// =======================================================================================================
-// bf16x3 mode, WIDE form (round 5; OPT-IN through NUDF_TN_FLAGS bit 1024 -- it measured slower): one
-// 8-wave workgroup per CU computes TWO vertically adjacent 128 x 128 tiles of a problem -- a 256 x 128 block: 25 % less
-// operand traffic per flop than two 128 x 128 workgroups (the B panel is staged once) -- from a DOUBLE-BUFFERED split image
-// (2 x 72 KB), so a k-step has ONE barrier: step kt's MFMAs read buffer kt & 1 while step kt + 1 is split into the other one.
-// The two waves of every SIMD run the two halves of a step in OPPOSITE order -- waves 0..3 multiply first and stage
-// afterwards, waves 4..7 stage first and multiply afterwards (both orders are legal between the same two barriers) -- so that
-// one wave's split / LDS stores run beside its partner's 48 MFMAs.
-// Same 32-row k-steps, same MFMA order per accumulator, same workspace slots (a wave's 64 x 64 quadrant is written where the
-// 128 x 128 kernel's wave writes it) and the same fixed-order reduce: on equal row chunks C and dbias are BIT-IDENTICAL to
-// gemm_tn3_group_kernel's (tests/test_gpu_bf16x3.py).  The plan keeps its 128 x 128 tiles; TnPlan.partner pairs them and
-// TnPlan.unit_tile enumerates the workgroups.
-// MEASURED (profiles/r05_tn_wide.txt): 511-541 us against 467-495 us for the UDF adjoint group at 65 536 points.  Per k-step
-// and wave (nudf_set_tn_debug, shader-clock ticks): MFMA segment 1.8-2.1 k (48 MFMAs = 1.5 k of pipe), split + LDS stores
-// 2.0-3.3 k, load issue 0.8-1.7 k, barrier wait 1.1-3.1 k = 8.1 k per step where the pipe needs 3.1 k -- the staging of a
-// step (24 four-byte loads with clamped 64-bit addresses, 12 pair splits of 11 VALU operations, 9 LDS stores per thread) costs
-// a wave more issue time than its 48 MFMAs, and two such waves per SIMD do not hide each other's; the 128 x 128 kernel's two
-// independent workgroups per CU interleave better than one barrier domain of eight waves.  What would move both kernels is
-// less staging work per MFMA (a 256 x 256 block per workgroup needs 128 accumulator registers per wave: no room beside the
-// staging sets), not a different overlap of the same work.
-// =======================================================================================================
-#define T3WA (4 * 256 * 4)   // dwords per plane of the A image [k-pair group 4][column 256][4]
-#define T3WB (4 * 128 * 4)   // ... of the B image
-#define T3W_BUF (3 * T3WA + 3 * T3WB)
-__global__ __launch_bounds__(512, 1) void gemm_tn3w_group_kernel(TnPlan g) {
-  __shared__ __attribute__((aligned(16))) unsigned smem_w[2 * T3W_BUF];   // 144 KB: one workgroup per CU
-  const int t = g.unit_tile[blockIdx.x / g.unit_chunks];
-  const int chunk = blockIdx.x % g.unit_chunks;
-  const int partner = g.partner[t];
-  const TnTile tl = g.tile[t];
-  const NudfGemmTNProblem& q = g.prob[tl.prob];
-  const bool two = partner >= 0;
-  const int slot0 = tl.blk_start + chunk;
-  const int slot1 = two ? g.tile[partner].blk_start + chunk : slot0;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;                       // 0..7: A quadrant wave >> 1 (64 columns), B half wave & 1
-  const int i0 = tl.ti * BM, j0 = tl.tj * BN;
-  const int mbeg = chunk * tl.rows_per_block;
-  const int mend = min(mbeg + tl.rows_per_block, g.M);
-  const int nk = (mend - mbeg + BK3 - 1) / BK3;
-  const int sca = tid & 255, sga = tid >> 8;       // A staging: column of the 256-wide panel, rows 16 sga .. + 15 of the step
-  const int scb = tid & 127, sgb = tid >> 7;       // B staging: column, rows 8 sgb .. + 7 (one k-pair group)
-  const bool bias_tile = (q.dbias != nullptr) && (tl.tj == 0) && !(g.flags & TNF_NO_BIAS);
-  const bool do_bias = bias_tile && (two || sca < BM);
-  float bias_acc = 0.0f;
-  const bool mm_live = two || wave < 4;            // an unpaired tile: waves 4..7 only stage
-
-  f32x16 acc[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[s2][r] = 0.0f;
-
-  const float* pa = q.A1 + min(i0 + sca, q.lda1 - 1);
-  const float* pb = q.B1 + min(j0 + scb, q.ldb1 - 1);
-  const size_t lda = (size_t)q.lda1, ldb = (size_t)q.ldb1;
-  auto load_a = [&](float (&st)[16], int kt) {
-    const int r0 = mbeg + kt * BK3 + 16 * sga;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) st[r] = pa[(size_t)min(r0 + r, g.M - 1) * lda];
-  };
-  auto load_b = [&](float (&st)[8], int kt) {
-    const int r0 = mbeg + kt * BK3 + 8 * sgb;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) st[r] = pb[(size_t)min(r0 + r, g.M - 1) * ldb];
-  };
-  auto store_a = [&](const float (&st)[16], int kt, unsigned* img) {
-    const int r0 = mbeg + kt * BK3 + 16 * sga;
-    u32x4 hq[2], mq[2], lq[2];
-    float ps[8];
-#pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-      const float x0 = (r0 + 2 * pp < mend) ? st[2 * pp] : 0.0f;
-      const float x1 = (r0 + 2 * pp + 1 < mend) ? st[2 * pp + 1] : 0.0f;
-      unsigned a, b, d;
-      tn_split3_pair(x0, x1, a, b, d);
-      hq[pp >> 2][pp & 3] = a; mq[pp >> 2][pp & 3] = b; lq[pp >> 2][pp & 3] = d;
-      ps[pp] = x0 + x1;
-    }
-    // (the same tree per 16 rows and the same running sum as gemm_tn3_group_kernel: identical bias gradients)
-    if (do_bias) bias_acc += ((ps[0] + ps[1]) + (ps[2] + ps[3])) + ((ps[4] + ps[5]) + (ps[6] + ps[7]));
-    unsigned* dst = img + ((2 * sga) * 256 + sca) * 4;
-    *reinterpret_cast<u32x4*>(dst) = hq[0];
-    *reinterpret_cast<u32x4*>(dst + 1024) = hq[1];
-    *reinterpret_cast<u32x4*>(dst + T3WA) = mq[0];
-    *reinterpret_cast<u32x4*>(dst + T3WA + 1024) = mq[1];
-    *reinterpret_cast<u32x4*>(dst + 2 * T3WA) = lq[0];
-    *reinterpret_cast<u32x4*>(dst + 2 * T3WA + 1024) = lq[1];
-  };
-  auto store_b = [&](const float (&st)[8], int kt, unsigned* img) {
-    const int r0 = mbeg + kt * BK3 + 8 * sgb;
-    u32x4 hq, mq, lq;
-#pragma unroll
-    for (int pp = 0; pp < 4; ++pp) {
-      const float x0 = (r0 + 2 * pp < mend) ? st[2 * pp] : 0.0f;
-      const float x1 = (r0 + 2 * pp + 1 < mend) ? st[2 * pp + 1] : 0.0f;
-      unsigned a, b, d;
-      tn_split3_pair(x0, x1, a, b, d);
-      hq[pp] = a; mq[pp] = b; lq[pp] = d;
-    }
-    unsigned* dst = img + 3 * T3WA + (sgb * 128 + scb) * 4;
-    *reinterpret_cast<u32x4*>(dst) = hq;
-    *reinterpret_cast<u32x4*>(dst + T3WB) = mq;
-    *reinterpret_cast<u32x4*>(dst + 2 * T3WB) = lq;
-  };
-  // one k-step of MFMAs: the 12 operand fragments of the SECOND group of 16 rows are requested before the first group's 24
-  // MFMAs (two register sets), so only the first group's LDS latency is exposed per step
-  auto mma = [&](const unsigned* img) {
-    const unsigned* as = img + ((lane >> 5) * 256 + (wave >> 1) * 64 + (lane & 31)) * 4;
-    const unsigned* bs = img + 3 * T3WA + ((lane >> 5) * 128 + (wave & 1) * 64 + (lane & 31)) * 4;
-    u32x4 fa[2][2][3], fb[2][2][3];
-    auto ldf = [&](int kk) {
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          fa[kk][s2][pl] = *reinterpret_cast<const u32x4*>(as + pl * T3WA + (2 * kk) * 1024 + 128 * s2);
-          fb[kk][s2][pl] = *reinterpret_cast<const u32x4*>(bs + pl * T3WB + (2 * kk) * 512 + 128 * s2);
-        }
-    };
-    ldf(0);
-#pragma unroll
-    for (int kk = 0; kk < BK3 / 16; ++kk) {
-      if (kk + 1 < BK3 / 16) ldf(kk + 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int tt = 0; tt < 6; ++tt) {
-        const int qa = (tt == 0 || tt == 3 || tt == 5) ? 0 : (tt == 1 ? 2 : 1);     // h l m h m h
-        const int qb = (tt == 0) ? 2 : ((tt == 2 || tt == 3) ? 1 : 0);              // l h m m h h
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-            acc[i * 2 + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[kk][i][qa]),
-                                                                     __builtin_bit_cast(bf16x8, fb[kk][j][qb]), acc[i * 2 + j], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  unsigned* buf0 = smem_w;
-  unsigned* buf1 = smem_w + T3W_BUF;
-  float sa[16], sb[8], sa2[16], sb2[8];
-  if (nk > 0) {
-    load_a(sa, 0);
-    load_b(sb, 0);
-    if (nk > 1) {
-      load_a(sa2, 1);
-      load_b(sb2, 1);
-    }
-    store_a(sa, 0, buf0);
-    store_b(sb, 0, buf0);
-  }
-  const bool mma_first = wave < 4;
-  // tuning (nudf_set_tn_debug): shader-clock ticks this wave spent in its three segments and waiting at the barrier
-  long long tk_mma = 0, tk_store = 0, tk_load = 0, tk_bar = 0;
-  const bool prof = g.dbg != nullptr;
-  const long long tk_begin = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
-#define TNW_STAMP(acc_) if (prof) { const long long n_ = (long long)__builtin_amdgcn_s_memtime(); acc_ += n_ - tk_last; tk_last = n_; }
-  if (!mma_first && nk > 2) {     // the staging-first waves run one request further ahead (see kstep)
-    load_a(sa, 2);
-    load_b(sb, 2);
-  }
-  __syncthreads();
-  auto kstep = [&](int kt, float (&la)[16], float (&lb)[8], float (&ua)[16], float (&ub)[8], const unsigned* cur, unsigned* nxt) {
-    // la / lb: free staging set, receives step kt + 2; ua / ub: holds step kt + 1, split into `nxt` during this step.
-    // Matrix-first waves: the rows of step kt + 2 are requested at the top of step kt and split at the END of step kt + 1.
-    long long tk_last = prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
-    if (mma_first) {
-      if (kt + 2 < nk) {
-        load_a(la, kt + 2);
-        load_b(lb, kt + 2);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      TNW_STAMP(tk_load)
-      if (mm_live) mma(cur);
-      __builtin_amdgcn_sched_barrier(0);
-      TNW_STAMP(tk_mma)
-      if (kt + 1 < nk) {
-        store_a(ua, kt + 1, nxt);
-        store_b(ub, kt + 1, nxt);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      TNW_STAMP(tk_store)
-    } else {
-      // staging-first waves: ua / ub (step kt + 1) is split right away and its registers take the rows of step kt + 3 --
-      // la / lb keep step kt + 2, requested one step ago -- so every request has two whole steps to land here as well
-      if (kt + 1 < nk) {
-        store_a(ua, kt + 1, nxt);
-        store_b(ub, kt + 1, nxt);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      TNW_STAMP(tk_store)
-      if (kt + 3 < nk) {
-        load_a(ua, kt + 3);
-        load_b(ub, kt + 3);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      TNW_STAMP(tk_load)
-      if (mm_live) mma(cur);
-      __builtin_amdgcn_sched_barrier(0);
-      TNW_STAMP(tk_mma)
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
-    TNW_STAMP(tk_bar)
-  };
-  for (int kt = 0; kt < nk; kt += 2) {
-    kstep(kt, sa, sb, sa2, sb2, buf0, buf1);
-    if (kt + 1 < nk) kstep(kt + 1, sa2, sb2, sa, sb, buf1, buf0);
-  }
-
-#undef TNW_STAMP
-  if (prof && lane == 0 && (wave == 0 || wave == 4)) {   // 8 int64 per workgroup: waves 0 (matrix-first) and 4 (staging-first)
-    long long* d = g.dbg + 8 * (size_t)blockIdx.x + (wave ? 4 : 0);
-    d[0] = ((long long)__builtin_amdgcn_s_memtime() - tk_begin) | ((long long)nk << 40);
-    d[1] = tk_mma; d[2] = tk_store | (tk_load << 32); d[3] = tk_bar;
-  }
-  if (g.flags & TNF_NO_EPILOGUE) return;
-  const int tsel = wave >> 2;                                   // which tile of the pair this wave's quadrant belongs to
-  const int vw = 2 * ((wave >> 1) & 1) + (wave & 1);            // its wave id in the 128 x 128 kernel's quadrant layout
-  float* slot_t[2] = {g.ws ? g.ws + (size_t)slot0 * TN_WS_TILE : nullptr, g.ws ? g.ws + (size_t)slot1 * TN_WS_TILE : nullptr};
-  if (bias_tile) {   // the loop's last barrier has passed: the image is free
-    float* red = reinterpret_cast<float*>(smem_w);
-    red[sga * 256 + sca] = bias_acc;
-    __syncthreads();
-    if (tid < 256 && (two || tid < BM)) {
-      const float sum = red[tid] + red[256 + tid];
-      float* sl = slot_t[tid >> 7];
-      if (sl) sl[BM * BN + (tid & 127)] = sum;
-      else if (i0 + tid < q.NA) atomicAdd(q.dbias + i0 + tid, sum);
-    }
-  }
-  if (!mm_live) return;
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) {
-    float* slot = slot_t[tsel];
-    if (slot) {
-      float* w = slot + ((vw * 4 + s2) * 64 + lane) * 16;
-#pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const f32x4 v = {acc[s2][4 * qd], acc[s2][4 * qd + 1], acc[s2][4 * qd + 2], acc[s2][4 * qd + 3]};
-        *reinterpret_cast<f32x4*>(w + 4 * qd) = v;
-      }
-    } else {
-      const int col = j0 + 32 * tn_jsub(2, vw, s2) + (lane & 31);
-      if (col >= q.NB) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = i0 + 128 * tsel + 32 * tn_isub(2, vw, s2) + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < q.NA) atomicAdd(q.C + (size_t)row * q.ldc + col, acc[s2][r]);
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // host side: the plan (tiles, layouts, cost-weighted row chunks) and the C ABI
 // ---------------------------------------------------------------------------------------
@@ -1913,37 +1645,6 @@ static int tn_plan(const NudfGemmTNGroup& g, TnPlan& pl) {
   pl.M = g.M;
   pl.prec = g.prec;
   pl.flags = flags;
-  // bf16x3 groups of fp32 row-major operands: pair every tile with the tile one tile row below it (same problem, same tile
-  // column) for the wide kernel -- one 8-wave workgroup per CU computes both.  Worth it when most tiles find a partner (the
-  // UDF network's 256-wide layers; the colour net's 128-wide ones do not).
-  pl.wide = 0;
-  int n_units = nt;
-  for (int t = 0; t < nt; ++t) pl.partner[t] = -1;
-  {
-    bool ok = g.prec == 3 && (flags & TNF_WIDE) && !(flags & TNF_NO_SPLIT_IMAGE);
-    for (int i = 0; i < g.n_problems && ok; ++i)
-      if (g.prob[i].flags & (NUDF_TN_A16 | NUDF_TN_B16 | NUDF_TN_A_BLK | NUDF_TN_B_BLK | NUDF_TN_A_P4 | NUDF_TN_B_P4)) ok = false;
-    if (ok) {
-      int pairs = 0;
-      for (int t = 0; t < nt; ++t) {
-        if (pl.partner[t] != -1 || (pl.tile[t].ti & 1)) continue;
-        const NudfGemmTNProblem& q = g.prob[pl.tile[t].prob];
-        const int tj_n = (q.NB + BN - 1) / BN;
-        const int u = t + tj_n;                        // tiles of a problem are enumerated tile row by tile row
-        if (u < nt && pl.tile[u].prob == pl.tile[t].prob && pl.tile[u].ti == pl.tile[t].ti + 1 && pl.tile[u].tj == pl.tile[t].tj) {
-          pl.partner[t] = (short)u;
-          pl.partner[u] = -2;
-          ++pairs;
-        }
-      }
-      if (4 * pairs >= nt) {                           // at least half of the tiles are in pairs
-        pl.wide = 1;
-        n_units = nt - pairs;
-      } else {
-        for (int t = 0; t < nt; ++t) pl.partner[t] = -1;
-      }
-    }
-  }
   const int nkt = (g.M + BK - 1) / BK;                 // k-steps over all points
   int chunks_of[TN_MAX_TILES];
   int blocks = 0;
@@ -2011,54 +1712,34 @@ static int tn_plan(const NudfGemmTNGroup& g, TnPlan& pl) {
     static int target0 = -1;
     if (target0 < 0) { const char* e = getenv("NUDF_TNG_BLOCKS"); target0 = e ? atoi(e) : 512; }
     const int max_chunks = nkt / 8 > 0 ? nkt / 8 : 1;
-    if (pl.wide) {
-      // one resident wave of WIDE workgroups: a pair (or an unpaired tile) per CU, every tile the same number of chunks
-      static int target_w = -1;
-      if (target_w < 0) { const char* e = getenv("NUDF_TNW_BLOCKS"); target_w = e ? atoi(e) : 256; }
-      int n = target_w / n_units;
-      if (n < 1) n = 1;
-      if (n > max_chunks) n = max_chunks;
-      for (int t = 0; t < nt; ++t) chunks_of[t] = n;
-      for (int t = 0; t < nt; ++t) pl.tile[t].rows_per_block = ((nkt + chunks_of[t] - 1) / chunks_of[t]) * BK;
-      layout();
-    } else {
-      // (the XCD-aware order keeps whole chunks of a tile group on one XCD, so the XCDs' shares are not exactly equal: when one
-      // XCD would receive more live workgroups than it has slots -- a second round on its CUs -- the total is lowered)
-      for (int target = target0;; target -= 8) {
-        auto count = [&](double T, bool store) {
-          long total = 0;
-          for (int t = 0; t < nt; ++t) {
-            // 16-bit operands: the k-step is bound by the loads / LDS traffic of the (always full-size) operand tiles, not by
-            // the live MFMAs -- every tile costs the same
-            const double c = ((flags & TNF_UNIFORM_CHUNKS) || g.prec != 0) ? 4.0 : cost[t];
-            long n = (long)((c * (double)nkt + T - 1e-9) / T);
-            if (n < 1) n = 1;
-            if (n > max_chunks) n = max_chunks;
-            if (store) chunks_of[t] = (int)n;
-            total += n;
-          }
-          return total;
-        };
-        double lo = 0.0, hi = 4.0 * nkt;                   // hi: one chunk per tile (always fits: nt <= 64 <= target)
-        if (count(hi, false) <= target) {
-          for (int it = 0; it < 60; ++it) {
-            const double mid = 0.5 * (lo + hi);
-            if (count(mid, false) <= target) hi = mid; else lo = mid;
-          }
+    // (the XCD-aware order keeps whole chunks of a tile group on one XCD, so the XCDs' shares are not exactly equal: when one
+    // XCD would receive more live workgroups than it has slots -- a second round on its CUs -- the total is lowered)
+    for (int target = target0;; target -= 8) {
+      auto count = [&](double T, bool store) {
+        long total = 0;
+        for (int t = 0; t < nt; ++t) {
+          // 16-bit operands: the k-step is bound by the loads / LDS traffic of the (always full-size) operand tiles, not by
+          // the live MFMAs -- every tile costs the same
+          const double c = ((flags & TNF_UNIFORM_CHUNKS) || g.prec != 0) ? 4.0 : cost[t];
+          long n = (long)((c * (double)nkt + T - 1e-9) / T);
+          if (n < 1) n = 1;
+          if (n > max_chunks) n = max_chunks;
+          if (store) chunks_of[t] = (int)n;
+          total += n;
         }
-        count(hi, true);
-        for (int t = 0; t < nt; ++t) pl.tile[t].rows_per_block = ((nkt + chunks_of[t] - 1) / chunks_of[t]) * BK;
-        const int most = layout();
-        if (most <= target0 / 8 || target - 8 < nt || target - 8 < target0 / 2) break;
+        return total;
+      };
+      double lo = 0.0, hi = 4.0 * nkt;                   // hi: one chunk per tile (always fits: nt <= 64 <= target)
+      if (count(hi, false) <= target) {
+        for (int it = 0; it < 60; ++it) {
+          const double mid = 0.5 * (lo + hi);
+          if (count(mid, false) <= target) hi = mid; else lo = mid;
+        }
       }
-    }
-  }
-  pl.n_units = 0;
-  pl.unit_chunks = nt > 0 ? pl.tile[1].blk_start - pl.tile[0].blk_start : 1;
-  if (pl.wide) {
-    for (int t = 0; t < nt; ++t) {
-      if (pl.tile[t + 1].blk_start - pl.tile[t].blk_start != pl.unit_chunks) pl.wide = 0;   // (cannot happen: uniform chunks)
-      if (pl.partner[t] != -2) pl.unit_tile[pl.n_units++] = (short)t;
+      count(hi, true);
+      for (int t = 0; t < nt; ++t) pl.tile[t].rows_per_block = ((nkt + chunks_of[t] - 1) / chunks_of[t]) * BK;
+      const int most = layout();
+      if (most <= target0 / 8 || target - 8 < nt || target - 8 < target0 / 2) break;
     }
   }
   return blocks;
@@ -2090,7 +1771,7 @@ extern "C" int nudf_gemm_tn_grouped_plan(const NudfGemmTNGroup* args, int32_t* o
   return pl.grid_blocks;
 }
 
-// The five kernels behind the plan: the name and the launch of a row are made from the same token
+// The four kernels behind the plan: the name and the launch of a row are made from the same token
 struct TnKernel {
   const char* name;
   int threads;
@@ -2101,10 +1782,10 @@ static void tn_launch(const TnPlan& pl, int grid, hipStream_t st) {
   hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(THREADS), 0, st, pl);
 }
 #define TN_KERNEL(kernel, threads) {#kernel, threads, tn_launch<threads, kernel>}
-enum { TN_GENERIC, TN_16, TN_3, TN_3W, TN_2 };
+enum { TN_GENERIC, TN_16, TN_3, TN_2 };
 static const TnKernel g_tn_kernels[] = {
     TN_KERNEL(gemm_tn_group_kernel, 256), TN_KERNEL(gemm_tn16_group_kernel, 256), TN_KERNEL(gemm_tn3_group_kernel, 256),
-    TN_KERNEL(gemm_tn3w_group_kernel, 512), TN_KERNEL(gemm_tn2_group_kernel, 256),
+    TN_KERNEL(gemm_tn2_group_kernel, 256),
 };
 
 // Plan, check and select: completes `pl` with the launch's options and picks the kernel (kernel < 0: an empty group), its grid
@@ -2143,7 +1824,7 @@ static int tn_select(const NudfGemmTNGroup& g, TnPlan& pl, int& kernel, int& gri
   } else if (pl.prec == 3 && !(pl.flags & TNF_NO_SPLIT_IMAGE) && !any_fmt) {
     // bf16x3 mode: the split-image kernel when every operand is fp32 row-major (what the bf16x3 chains store); anything else
     // goes through the generic kernel, which splits on the way OUT of its fp32 image (NUDF_TN_FLAGS & 512 forces that: A/B)
-    kernel = pl.wide ? TN_3W : TN_3;
+    kernel = TN_3;
   } else if (any_p4 || (pl.prec != 0 && pl.prec != 3 && !(pl.flags & TNF_NO_PACK16) && !any_blk && n16 >= g.n_problems)) {
     // 16-bit MFMA mode: the packed-image kernel, unless an operand is in the blocked fp32 layout (generic kernel only) or
     // most operands are stored as fp32 (its staging of an fp32 operand is heavier: 262 -> 278 us with all-fp32 operands,
@@ -2152,7 +1833,7 @@ static int tn_select(const NudfGemmTNGroup& g, TnPlan& pl, int& kernel, int& gri
   } else {
     kernel = TN_GENERIC;
   }
-  grid = kernel == TN_3W ? pl.n_units * pl.unit_chunks : pl.grid_blocks;
+  grid = pl.grid_blocks;
   reduce_grid = pl.ws ? pl.n_tiles * 17 : 0;
   return 0;
 }

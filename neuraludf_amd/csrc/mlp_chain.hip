@@ -1559,15 +1559,15 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? CH_T16_WGS : 2) void mlp_
 // ---------------------------------------------------------------------------------------------------
 // host side: check the descriptor, select one row of the kernel table, launch that row
 // ---------------------------------------------------------------------------------------------------
-// mlp_chain_kernel's rows of the table (ChainKernelId of mlp_chain_shared.h); the other ten are in mlp_chain_rows.hip
-static const ChainKernel g_shared_kernels[CK_PAIR] = {
+// mlp_chain_kernel's rows of the table (ChainKernelId of mlp_chain_shared.h); the other seven are in mlp_chain_rows.hip
+static const ChainKernel g_shared_kernels[CK_TQ] = {
     CH_KERNEL(32, CH_THREADS, mlp_chain_kernel<32, 2>), CH_KERNEL(32, CH_THREADS, mlp_chain_kernel<32, 1>),
     CH_KERNEL(32, CH_THREADS, mlp_chain_kernel<32, 0>),
     CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 2>), CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 4>),
     CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 3>), CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 1>),
     CH_KERNEL(64, CH_THREADS, mlp_chain_kernel<64, 0>),
 };
-static const ChainKernel& chain_kernel(int id) { return id < CK_PAIR ? g_shared_kernels[id] : nudf_chain_tq_kernel(id); }
+static const ChainKernel& chain_kernel(int id) { return id < CK_TQ ? g_shared_kernels[id] : nudf_chain_tq_kernel(id); }
 
 // The process-wide settings of the selection, read once:
 //  NUDF_CHAIN_ROWS=1 lets large launches choose the wave-private kernel on their own (measured in round 2: equal to the
@@ -1580,21 +1580,15 @@ static const ChainKernel& chain_kernel(int id) { return id < CK_PAIR ? g_shared_
 //    lines); with the BLOCKED layout of nudf.h addressed instead (timing only) -8 / -10 / -7 / -4 %.  Over a whole train step
 //    the forward / gradient gain is inside the noise (3.95 vs 3.98 ms of chain time), so the default stays mlp_chain_kernel:
 //    =1 uses the transposed form for launches with at most one stored operand, =2 for every launch.
-//  NUDF_CHAIN_PAIR: 0 (default) = independent 64-point workgroups; 1 = launches of at least 32 768 points that already go to
-//    the transposed-product kernel (blocked state: the UDF sweeps) run as paired tiles (mlp_chain_pair_kernel); 2 = every fp32
-//    launch of at least 32 768 points that meets that kernel's contract does (colour / NeRF chains, coarse forward).  MEASURED
-//    (round 3, profiles/r03_chain_pair.txt): not faster -- a K loop alone on the pipe next to the partner's epilogue reaches
-//    only 77 % of the pipe rate (two in-phase K loops together 95 %), and the epilogue beside a K loop takes 1.8x as long; the
-//    kernel stays as the measured counter-example to "enforce anti-phase".
 //  NUDF_CHAIN_T16=0 / nudf_set_chain_t16: keep the fp32-tile kernel in the 16-bit mode (A/B; the two are bit-identical).
 //  NUDF_CHAIN_WIN2=3: the wave-private kernel's operand window (tiles in flight per stored-state operand) is 4 with one
 //    operand and 2 with two (3 makes the register allocator spill ~100 values per step; =3 selects that build for measurements).
-struct ChainSettings { int rows_auto, quad, pair, t16, win2; };
+struct ChainSettings { int rows_auto, quad, t16, win2; };
 static ChainSettings& chain_settings() {
   static ChainSettings s = [] {
     auto env = [](const char* name) { const char* e = getenv(name); return e ? e : ""; };
-    return ChainSettings{env("NUDF_CHAIN_ROWS")[0] == '1', atoi(env("NUDF_CHAIN_QUAD")), atoi(env("NUDF_CHAIN_PAIR")),
-                         env("NUDF_CHAIN_T16")[0] != '0', env("NUDF_CHAIN_WIN2")[0] == '3' ? 3 : 2};
+    return ChainSettings{env("NUDF_CHAIN_ROWS")[0] == '1', atoi(env("NUDF_CHAIN_QUAD")), env("NUDF_CHAIN_T16")[0] != '0',
+                         env("NUDF_CHAIN_WIN2")[0] == '3' ? 3 : 2};
   }();
   return s;
 }
@@ -1614,11 +1608,14 @@ struct ChainFacts {
 };
 
 static bool chain_tile_transposed(int tile_rows) {
-  return tile_rows == NUDF_CH_TILE_TQ || tile_rows == NUDF_CH_TILE_ROWS || tile_rows == NUDF_CH_TILE_PAIR;
+  return tile_rows == NUDF_CH_TILE_TQ || tile_rows == NUDF_CH_TILE_ROWS;
 }
 
 // Check: 0, or the error (text set).  Dereferences nothing the descriptor points to.
 static int chain_check(const NudfChain& p, ChainFacts& f) {
+  if (p.tile_rows == 130)   // (was NUDF_CH_TILE_PAIR: refused by name, so that an old caller does not silently get another kernel)
+    return nudf_refuse("nudf_mlp_chain: tile_rows 130 asked for the paired-tile kernel, which was retired (it measured no "
+                        "faster, profiles/r03_chain_experiments.txt); tile_rows 66 is the same tile without the pairing");
   bool bad = p.n_steps > NUDF_CH_MAX_STEPS || (p.k0 & 3) || p.k0 > 288 || p.x_div < 1;
   // SEED (two sweeps in one launch) contracts nothing and exists in mlp_chain_kernel<TM, 2> only: checked on its own
   f.fused = false;
@@ -1692,7 +1689,7 @@ static int chain_check(const NudfChain& p, ChainFacts& f) {
   for (int i = 0; i < p.n_steps; ++i) f.blocked = f.blocked || (p.step[i].layout & 31) != 0;
   f.cls = nudf_chain_rows_class(p, f.blocked);
   // only the transposed-product shared tile addresses the blocked layout
-  if (f.blocked && (f.cls < 0 || (p.tile_rows != NUDF_CH_TILE_TQ && p.tile_rows != NUDF_CH_TILE_PAIR && p.tile_rows != 0)))
+  if (f.blocked && (f.cls < 0 || (p.tile_rows != NUDF_CH_TILE_TQ && p.tile_rows != 0)))
     return nudf_refuse("nudf_mlp_chain: blocked-layout buffers need the transposed-product kernel (tile_rows 0 / 66, fp32 "
                         "steps, 16-byte aligned rows)");
   return 0;
@@ -1701,8 +1698,6 @@ static int chain_check(const NudfChain& p, ChainFacts& f) {
 // Select: the table row of a checked descriptor -- a pure function of the descriptor, what the check learned and the settings.
 static int chain_select(const NudfChain& p, const ChainFacts& f, const ChainSettings& set) {
   const int tile = p.tile_rows;
-  // the transposed-product shared tile, as paired tiles on request (tile_rows) or for large launches with NUDF_CHAIN_PAIR
-  auto tq = [&](bool pair) { return ((pair || (set.pair > 0 && p.P >= 32768)) ? CK_PAIR : CK_TQ) + f.cls; };
   // Large launches: wave-private 32-point tiles (mlp_chain_rows.hip), one free-running wave per SIMD.  A "round" of
   // that kernel is 1024 waves = 32 768 points, so it is chosen when the last round is at least ~80 % full; the
   // up-sampling rounds (5-8 k points) and awkward sizes keep the workgroup-shared tiles below.
@@ -1713,15 +1708,10 @@ static int chain_select(const NudfChain& p, const ChainFacts& f, const ChainSett
   }
   // (contract of the wave-private kernel not met -- 16-bit operands, unaligned row buffers: workgroup-shared tiles)
   if (rows_ok && f.cls >= 0) return f.cls < 2 ? CK_ROWS + f.cls : set.win2 == 3 ? CK_ROWS_2_WIN3 : CK_ROWS_2_WIN2;
-  if (f.blocked) return tq(tile == NUDF_CH_TILE_PAIR);
-  if (f.cls >= 0) {
-    if (tile == NUDF_CH_TILE_PAIR) return tq(true);     // paired tiles requested explicitly (tests, A/B): any size
-    if (!f.roww && !f.fused && (tile == NUDF_CH_TILE_TQ || (tile == 0 && p.P > 256 * 64 && set.quad > 0)) &&
-        (tile == NUDF_CH_TILE_TQ || f.cls <= 1 || set.quad >= 2))
-      return tq(false);
-    // NUDF_CHAIN_PAIR=2: paired tiles for every fp32 launch of at least 32 768 points that meets that kernel's contract
-    if (!f.roww && tile == 0 && p.P >= 32768 && !f.any16 && !f.any3 && set.pair >= 2) return tq(false);
-  }
+  if (f.blocked) return CK_TQ + f.cls;     // only the transposed-product shared tile addresses the blocked layout
+  if (f.cls >= 0 && !f.roww && !f.fused && (tile == NUDF_CH_TILE_TQ || (tile == 0 && p.P > 256 * 64 && set.quad > 0)) &&
+      (tile == NUDF_CH_TILE_TQ || f.cls <= 1 || set.quad >= 2))
+    return CK_TQ + f.cls;
   // small launches: 32-point tiles fill the 256 CUs sooner (up-sampling rounds are 5-8 k points)
   const bool small = tile == 32 || (tile != 64 && p.P <= 256 * 64);
   // 16-bit mode, 64-point tiles: the 16-bit-TILE kernel (MODE 3) when every step contracts in the same 16-bit type (the

@@ -179,7 +179,7 @@ __device__ __forceinline__ void ch_udf_head(int type, float v, float scale, floa
 // ---- host side: the kernel table nudf_mlp_chain selects from (mlp_chain.hip) ----------------------------------------------
 // One row per kernel instantiation.  CH_KERNEL makes the name and the launch from the same tokens, so the name a launch is
 // reported under (nudf_mlp_chain_plan) is the kernel it runs.  A kernel is launched from the file that instantiates it:
-// mlp_chain.hip holds the rows below CK_PAIR, mlp_chain_rows.hip the others.
+// mlp_chain.hip holds the rows below CK_TQ, mlp_chain_rows.hip the others.
 struct ChainKernel {
   const char* name;     // the instantiation as spelled in the source
   int points, threads;  // per workgroup: grid = ceil(P / points)
@@ -194,12 +194,11 @@ static void ch_launch(const NudfChain& p, int grid, hipStream_t st) {
 enum ChainKernelId {
   CK_32_M2, CK_32_M1, CK_32_M0,                         // mlp_chain_kernel<32, MODE>
   CK_64_M2, CK_64_M4, CK_64_M3, CK_64_M1, CK_64_M0,     // mlp_chain_kernel<64, MODE>
-  CK_PAIR,                                              // + operand class 0..2 (nudf_chain_rows_class): mlp_chain_pair_kernel
-  CK_TQ = CK_PAIR + 3,                                  // + operand class: mlp_chain_tq_kernel
+  CK_TQ,                                                // + operand class 0..2 (nudf_chain_rows_class): mlp_chain_tq_kernel
   CK_ROWS = CK_TQ + 3,                                  // + operand class 0..1: mlp_chain_rows_kernel<class, 4>
   CK_ROWS_2_WIN3 = CK_ROWS + 2, CK_ROWS_2_WIN2,         // mlp_chain_rows_kernel<2, 3> (NUDF_CHAIN_WIN2=3) and <2, 2>
   CK_COUNT
 };
-const ChainKernel& nudf_chain_tq_kernel(int id);   // mlp_chain_rows.hip: rows CK_PAIR .. CK_COUNT - 1
+const ChainKernel& nudf_chain_tq_kernel(int id);   // mlp_chain_rows.hip: rows CK_TQ .. CK_COUNT - 1
 // launch-time contract of the transposed-product kernels (mlp_chain_rows.hip): the operand class, -1 when it is not met
 int nudf_chain_rows_class(const NudfChain& p, bool allow_blocked = false);

@@ -289,15 +289,13 @@ __device__ __forceinline__ float wave_bcast(float v, int src) {
 }
 // sum over the 64 lanes, returned to every lane
 __device__ __forceinline__ float wave_sum(float v) { return wave_bcast(wave_incl_scan_add(v), 63); }
-// inclusive suffix sum: out[l] = sum_{j>=l} v[j]: reverse the lane order (one ds_bpermute, crossbar only), run the
-// DPP prefix scan, reverse back -- 8 instructions.  (DPP has no backward row broadcast, and total - prefix would
+// inclusive suffix sums: out[l] = sum_{j>=l} v[j]: reverse the lane order (one ds_bpermute, crossbar only), run the
+// DPP prefix scan, reverse back.  (DPP has no backward row broadcast, and total - prefix would
 // cancel catastrophically for the small suffixes behind a surface; the earlier version walked 6 shuffle steps of
 // bpermute + select + add.)
 __device__ __forceinline__ float wave_reverse(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((63 - lane_id()) << 2, __builtin_bit_cast(int, v)));
 }
-__device__ __forceinline__ float wave_incl_rscan_add(float v) { return wave_reverse(wave_incl_scan_add(wave_reverse(v))); }
-
 template <int N>
 __device__ __forceinline__ void wave_incl_rscan_add_n(float (&v)[N]) {
   // N independent suffix scans: reverse, interleaved prefix scans, reverse back

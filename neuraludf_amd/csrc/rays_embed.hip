@@ -376,23 +376,6 @@ extern "C" int nudf_sigmoid_head_bwd(const float* y, const float* dy, const floa
   return 0;
 }
 
-// out[p,c] = a[p,c] + b[p,c]  (adjoint joins, e.g. the hidden tap of the colour net)
-__global__ void add_cols_kernel(const float* __restrict__ a, int lda, const float* __restrict__ b, int ldb,
-                                float* __restrict__ out, int ldo, int P, int C) {
-  long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long long)P * C) return;
-  int p = (int)(idx / C), c = (int)(idx - (long long)p * C);
-  out[(size_t)p * ldo + c] = a[(size_t)p * lda + c] + b[(size_t)p * ldb + c];
-}
-extern "C" int nudf_add_cols(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int P, int C,
-                             void* stream) {
-  if (P == 0) return 0;
-  hipLaunchKernelGGL(add_cols_kernel, dim3(nblocks((long long)P * C, 256)), dim3(256), 0, (hipStream_t)stream, a, lda, b,
-                     ldb, out, ldo, P, C);
-  NUDF_CHECK_LAUNCH("nudf_add_cols");
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------
 // weight_norm packing: W = g * v / ||v||_row  (torch.nn.utils.weight_norm, applied at
 // fields.py:175-176, 433-446), written zero-padded into the two layouts the GEMMs read:

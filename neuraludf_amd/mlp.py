@@ -746,7 +746,7 @@ def _state_blocked(P):
     (1 KB of contiguous memory per wave instruction in the epilogues, 16 KB contiguous operand tiles in the weight-gradient GEMM)."""
     # (bf16x3: measured with the split K loop ported into the transposed-product kernel -- chains 2.752 vs 2.758 ms, and the
     # weight-gradient GEMM loses its split-image kernel on blocked operands, 1.14 -> 2.09 ms: row-major state there)
-    return PRECISION == "fp32" and USE_CHAIN and CHAIN_TILE in (0, 66, 130) and P > 256 * 64
+    return PRECISION == "fp32" and USE_CHAIN and CHAIN_TILE in (0, 66) and P > 256 * 64
 
 
 def _state_dtype():

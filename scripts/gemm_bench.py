@@ -16,10 +16,6 @@ def bench(fn, flops, reps=20):
     us = s.elapsed_time(e) / reps * 1e3
     return us, flops / us / 1e6
 
-from neuraludf_amd import _lib
-VARIANT = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-_lib.lib().nudf_set_gemm_variant(VARIANT)
-print("variant", VARIANT)
 for (M, N, K) in [(65536, 256, 256), (8192, 256, 256), (32768, 256, 256), (65536, 128, 128), (65536, 256, 64)]:
     A = torch.randn(M, K, device=dev); B = torch.randn(K, N, device=dev) * 0.05
     C1 = torch.empty(M, N, device=dev); C2 = torch.empty(M, N, device=dev)
@@ -39,4 +35,5 @@ for (M, NA, NB) in [(65536, 256, 256), (8192, 256, 256)]:
     res[f"tn2_{M}x{NA}x{NB}"] = (round(us, 1), round(tf, 1))
 for k, v in res.items():
     print(f"{k:40s} {v[0]:9.1f} us  {v[1]:7.1f} TF")
-json.dump(res, open(f"gpurun_out/gemm_bench_v{VARIANT}.json", "w"))
+if len(sys.argv) > 1:      # optional: a file for the results
+    json.dump(res, open(sys.argv[1], "w"))

@@ -132,11 +132,12 @@ def test_weight_gradient_gemm_plan_host_logic():
 
 
 def test_retired_tn_flag_bits_are_masked_off():
-    """bits 2 (drop the epilogue) and 4 (skip the bias sums) of nudf_set_tn_flags computed wrong results on purpose and are
-    retired: the setter drops them, so an old command line cannot produce garbage.  Host-only call."""
+    """bits 2 (drop the epilogue) and 4 (skip the bias sums) of nudf_set_tn_flags computed wrong results on purpose, bit 1024
+    selected the wide bf16x3 kernel that was deleted; all three are retired: the setter drops them, so an old command line
+    can neither produce garbage nor ask for a kernel that is gone.  Host-only call."""
     from neuraludf_amd import _lib
     lib = _lib.lib()
-    prev = lib.nudf_set_tn_flags(2 | 4 | 16)
+    prev = lib.nudf_set_tn_flags(2 | 4 | 16 | 1024)
     try:
         assert lib.nudf_set_tn_flags(0) == 16
     finally:

@@ -7,7 +7,7 @@ import os
 
 import pytest
 
-SETTINGS = ("NUDF_CHAIN_ROWS", "NUDF_CHAIN_QUAD", "NUDF_CHAIN_PAIR", "NUDF_CHAIN_T16", "NUDF_CHAIN_WIN2")
+SETTINGS = ("NUDF_CHAIN_ROWS", "NUDF_CHAIN_QUAD", "NUDF_CHAIN_T16", "NUDF_CHAIN_WIN2")
 SETTINGS_SET = any(v in os.environ for v in SETTINGS)       # the chain selection depends on them: read once per process
 A = 1 << 20
 
@@ -91,9 +91,6 @@ CHAIN_CASES = [
     ("tq-class1", lambda: _sweep(1000, 66, 0, ("MULSP", 0, X1)), "mlp_chain_tq_kernel<1, 3, true>", 16, 256),
     ("tq-class2", lambda: _sweep(1000, 66, 0, ("BWD", 0, X12)), "mlp_chain_tq_kernel<2>", 16, 256),
     ("tq-split-falls-back", lambda: _sweep(1000, 66, 4), "mlp_chain_kernel<32, 2>", 32, 256),
-    ("pair-class0", lambda: _sweep(1000, 130, 0), "mlp_chain_pair_kernel<0>", 8, 512),
-    ("pair-class1", lambda: _sweep(1000, 130, 0, ("MULSP", 0, X1)), "mlp_chain_pair_kernel<1>", 8, 512),
-    ("pair-class2", lambda: _sweep(1000, 130, 0, ("BWD", 0, X12)), "mlp_chain_pair_kernel<2>", 8, 512),
     ("blocked-class0", lambda: _sweep(1000, 0, 0, ("SOFTPLUS", 0, BLK_C1)), "mlp_chain_tq_kernel<0, 3>", 16, 256),
     ("blocked-class1", lambda: _sweep(1000, 0, 0, ("MULSP", 0, dict(X1, **BLK_C1))), "mlp_chain_tq_kernel<1, 3, true>", 16, 256),
     ("half-65536", lambda: _sweep(65536, 0, 1), "mlp_chain_kernel<64, 3>", 1024, 256),
@@ -133,7 +130,8 @@ def test_chain_t16_switch_is_part_of_the_selection():
     (lambda: _sweep(1000, 64, 0, ("SOFTPLUS", 0, BLK_C1)), "blocked-layout"),
     (lambda: _colour_head(65536, 66, 4), "row_w"),
     (lambda: _seed_chain(66), "split-mode"),
-], ids=["blocked-on-tile64", "roww-on-tq", "seed-on-tq"])
+    (lambda: _sweep(1000, 130, 0), "tile_rows"),           # the retired paired-tile kernel: refused, not given another kernel
+], ids=["blocked-on-tile64", "roww-on-tq", "seed-on-tq", "retired-tile130"])
 def test_chain_refusals_are_reported_without_a_launch(make, word):
     rc, name, out, err = _report("nudf_mlp_chain_plan", make())
     assert rc != 0 and word in err
@@ -177,7 +175,7 @@ GROUP_CASES = [
     ("fp32", 0, lambda: _group(UDF, 0), "gemm_tn_group_kernel", 256),
     ("bf16x3", 0, lambda: _group(UDF, 3), "gemm_tn3_group_kernel", 256),
     ("bf16x3-no-split-image", 512, lambda: _group(UDF, 3), "gemm_tn_group_kernel", 256),
-    ("bf16x3-wide", 1024, lambda: _group([(256, 256)], 3), "gemm_tn3w_group_kernel", 512),
+    ("bf16x3-retired-wide-flag", 1024, lambda: _group([(256, 256)], 3), "gemm_tn3_group_kernel", 256),
     ("bf16x3-one-blocked", 0, lambda: _one_blocked(_group(UDF, 3)), "gemm_tn_group_kernel", 256),
     ("f16x2", 0, lambda: _group(UDF, 4), "gemm_tn2_group_kernel", 256),
     ("bf16-packed", 0, lambda: _group(UDF, 2, flags=3, ld=256), "gemm_tn16_group_kernel", 256),
@@ -196,16 +194,28 @@ def test_weight_gradient_kernel_selection(tn_flags, make, kernel, block):
         rc, name, out, err = _report("nudf_gemm_tn_grouped_kernel", g)
         assert rc == 0, err
         assert name == kernel and out[1] == block and out[2:] == [0, 0]         # no workspace: no reduce launch
-        if kernel != "gemm_tn3w_group_kernel":                                   # (the wide kernel: one workgroup per tile pair)
-            assert out[0] == lib.nudf_gemm_tn_grouped_plan(C.byref(g), (C.c_int32 * 4)(), 1)
-        else:
-            assert 0 < out[0] < lib.nudf_gemm_tn_grouped_plan(C.byref(g), (C.c_int32 * 4)(), 1)
+        assert out[0] == lib.nudf_gemm_tn_grouped_plan(C.byref(g), (C.c_int32 * 4)(), 1)
         rc, name, out2, err = _report("nudf_gemm_tn_grouped_kernel", _with_workspace(make()))
         assert rc == 0, err
         assert name == kernel and out2[:2] == out[:2]
         assert out2[2] == (36 if g.n_problems == len(UDF) else 4) * 17            # tn_reduce_kernel: 17 workgroups per tile
     finally:
         lib.nudf_set_tn_flags(prev)
+
+
+def test_retired_wide_flag_changes_neither_kernel_nor_grid():
+    """NUDF_TN_FLAGS bit 1024 once selected the wide bf16x3 kernel (deleted: profiles/r05_tn_wide.txt); it is masked off"""
+    from neuraludf_amd import _lib
+    lib = _lib.lib()
+    reports = []
+    for flags in (0, 1024):
+        prev = lib.nudf_set_tn_flags(flags)
+        try:
+            reports.append(_report("nudf_gemm_tn_grouped_kernel", _group([(256, 256)], 3))[:3])
+        finally:
+            lib.nudf_set_tn_flags(prev)
+    assert reports[0][0] == 0 and reports[0][1] == "gemm_tn3_group_kernel" and reports[0][2][1] == 256
+    assert reports[1] == reports[0]
 
 
 def test_weight_gradient_refusals_are_reported_without_a_launch():
