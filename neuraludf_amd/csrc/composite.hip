@@ -745,6 +745,8 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(NudfComposite p, Nud
 }
 
 #define NUDF_MAX_CHUNKS 8
+// chunks of the instantiation that serves nc chunks of samples: <1> ... <6> are compiled, nc = 7 and 8 share <8>
+static inline int composite_chunks(int nc) { return nc <= 6 ? nc : NUDF_MAX_CHUNKS; }
 
 extern "C" int nudf_composite_fwd(const NudfComposite* args, void* stream) {
   const NudfComposite& p = *args;
@@ -771,7 +773,9 @@ extern "C" int nudf_composite_fwd(const NudfComposite* args, void* stream) {
   // carries no stores, branches or address arithmetic for them
   const bool diag = p.o_alpha_occ || p.o_raw_occ || p.o_true_cos || p.o_grad_mag || p.o_mid_z || p.o_dists ||
                     p.o_inside || p.o_flip || p.o_vis_prob || p.o_alpha || p.o_alpha_plus || p.o_alpha_minus;
-  const bool full = (p.S == 64 * nc) && p.n_out == 0 && p.s_nominal >= p.S;
+  // FULL promises a live sample in every lane of every INSTANTIATED chunk: nc = 7 runs <8> with a dead chunk, so
+  // S = 448 is not FULL (it used to be: the dead chunk's lanes then stored 64 weights past the ray's row)
+  const bool full = (p.S == 64 * composite_chunks(nc)) && p.n_out == 0 && p.s_nominal >= p.S;
 #define NUDF_CF_LAUNCH(NCV)                                                                                   \
   if (diag) hipLaunchKernelGGL((composite_fwd_kernel<NCV, true, false>), grid, block, 0, st, p, status);      \
   else if (full) hipLaunchKernelGGL((composite_fwd_kernel<NCV, false, true>), grid, block, 0, st, p, status); \
@@ -813,7 +817,7 @@ extern "C" int nudf_composite_bwd(const NudfComposite* args, const NudfComposite
   }
   dim3 grid((p.N + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
-  const bool full = (p.S == 64 * nc) && p.n_out == 0 && p.s_nominal >= p.S;
+  const bool full = (p.S == 64 * composite_chunks(nc)) && p.n_out == 0 && p.s_nominal >= p.S;   // (see nudf_composite_fwd)
 #define NUDF_CB_LAUNCH(NCV)                                                                         \
   if (full) hipLaunchKernelGGL((composite_bwd_kernel<NCV, true>), grid, block, 0, st, p, *grads);   \
   else hipLaunchKernelGGL((composite_bwd_kernel<NCV, false>), grid, block, 0, st, p, *grads)

@@ -6,6 +6,7 @@ import math
 import pytest
 import torch
 
+import composite_ref
 from common import CONF, build_modules, perturb_, state_dicts, oracle_nets, grel, grel2
 from oracle import udf_oracle as O
 
@@ -588,38 +589,10 @@ def test_composite_stagewise(dev, case):
     if n_out:
         leaves += [bg_sigma.clone().requires_grad_(True), bg_col.clone().requires_grad_(True)]
 
-    def oracle_composite(u, gr, c, b, s_, be, ga, bs=None, bc=None):
-        dists = torch.cat([z[:, 1:] - z[:, :-1], torch.full((N, 1), sdist)], -1)
-        mid = z + dists * 0.5
-        dirs = r["rays_d"][:, None, :].expand(N, S, 3)
-        pts = r["rays_o"][:, None, :] + dirs * mid[..., None]
-        gm = torch.linalg.norm(gr, ord=2, dim=-1, keepdim=True)
-        gn = gr / (gm + 1e-5)
-        tc = (dirs * (gn if use_norm else gr)).sum(-1)
-        flip = -torch.sign((dirs * gn).sum(-1))
-        flip[flip == 0] = 1
-        raw = O.udf2logistic(u, be, 1.0, 1.0)
-        aocc = 1.0 - torch.exp(-torch.relu(raw) * ga * dists)
-        vm = torch.cat([(tc < 0.01).float()[:, 1:], torch.ones(N, 1)], -1)
-        vis = O.excl_cumprod((1.0 - aocc + fs * vm).clip(0, 1) + 1e-7).clip(0, 1)
-        ap = O.sdf2alpha(u, -tc.abs(), dists, s_, anneal, kind=kind)
-        am = O.sdf2alpha(-u, -tc.abs(), dists, s_, anneal, kind=kind)
-        alpha = ap * vis + am * (1 - vis)
-        cc, bb = c, b
-        if bs is not None:
-            dz = torch.cat([bg_z[:, 1:] - bg_z[:, :-1], torch.full((N, 1), sdist)], -1)
-            alpha = torch.cat([alpha, 1.0 - torch.exp(-torch.relu(bs) * dz)], -1)
-            cc = torch.cat([c, bc], 1)
-            bb = torch.cat([b, bc], 1)
-        w = alpha * O.excl_cumprod(1.0 - alpha + 1e-7)
-        pn = torch.linalg.norm(pts, ord=2, dim=-1)
-        ge = (gm[..., 0] - 1.0) ** 2
-        relax, near = (pn < 1.2).float(), (u < 0.05).float().detach()
-        sums = torch.stack([(relax * ge).sum(), relax.sum(), (near * ge).sum(), near.sum(),
-                            torch.exp(-25000.0 * u).sum()])
-        return dict(color=(cc * w[..., None]).sum(1), color_base=(bb * w[..., None]).sum(1), weights=w,
-                    depth=(mid * w[:, :S]).sum(1, keepdim=True), normals=(flip[..., None] * gr * w[:, :S, None]).sum(1),
-                    sums=sums, vis=vis, alpha=alpha[:, :S], wsum=w[:, :S].sum(-1, keepdim=True))
+    geom = dict(rays_o=r["rays_o"], rays_d=r["rays_d"], z=z, sdist=sdist, bg_z=bg_z)
+
+    def oracle_composite(*lv):
+        return composite_ref.oracle_composite(geom, *lv, kind=kind, anneal=anneal, fs=fs, use_norm=use_norm)
 
     ref = oracle_composite(*leaves)
     wts = dict(color=torch.randn(N, 3, generator=g), color_base=torch.randn(N, 3, generator=g),
