@@ -156,6 +156,7 @@ extern "C" int nudf_pixel_blend_fwd(const NudfPixelBlend* a, void* stream) {
   NUDF_CHECK_LAUNCH("nudf_pixel_blend_fwd");
   return 0;
 }
+// (the forward's argument checks are not repeated: autograd only runs this after nudf_pixel_blend_fwd accepted them)
 extern "C" int nudf_pixel_blend_bwd(const NudfPixelBlend* a, const float* d_pix, float* d_logits, void* stream) {
   if (a->P <= 0) return 0;
   hipLaunchKernelGGL(pixel_blend_kernel<true>, dim3((a->P + 127) / 128), dim3(128), 0, (hipStream_t)stream, *a, d_pix,
@@ -460,7 +461,7 @@ extern "C" int nudf_patch_blend_fwd(const NudfPatchBlend* a, void* stream) {
   if (a->N <= 0) return 0;
   const int npx = (2 * a->hps + 1) * (2 * a->hps + 1);
   if (a->V > MAXV || a->V > a->nl || npx > 128) {
-    nudf_set_error("nudf_patch_blend: V <= 16 and h_patch_size <= 5 required", hipErrorInvalidValue);
+    nudf_set_error("nudf_patch_blend: V <= 10, V <= the logits' width and h_patch_size <= 5 required", hipErrorInvalidValue);
     return (int)hipErrorInvalidValue;
   }
   const bool w8 = a->N < 1024;
@@ -476,6 +477,7 @@ extern "C" int nudf_patch_blend_fwd(const NudfPatchBlend* a, void* stream) {
   NUDF_CHECK_LAUNCH("nudf_patch_blend_fwd");
   return 0;
 }
+// (no argument checks here: autograd only reaches a backward through the forward that made them, on the same struct)
 extern "C" int nudf_patch_blend_bwd(const NudfPatchBlend* a, const float* d_patch, float* d_logits, float* d_w,
                                     void* stream) {
   if (a->N <= 0) return 0;
