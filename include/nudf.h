@@ -17,7 +17,31 @@
 extern "C" {
 #endif
 
+/* The ABI version.  Every change to an argument struct, an enum value, a #define or an entry point's signature raises it; a
+ * caller that mirrors this header by hand (neuraludf_amd/_lib.py) refuses a library whose nudf_version() differs.
+ *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
+ *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
+ *        NudfIsoSurfaceSparse, NudfMeshOrient, NudfMeshRaster and the two dispatch reports nudf_mlp_chain_plan /
+ *        nudf_gemm_tn_grouped_kernel
+ *   108: nudf_meshtopo_* + NudfMeshTopo (mesh clean-up)
+ *   107: nudf_pc_* + NudfPointCloud (Chamfer evaluation)
+ *   106: nudf_meshudf_* + NudfMeshUDF
+ *   105: NudfChain.tile_scale / tile_amax_in / tile_amax_out
+ *   104: NudfChain.absmax_out, NudfGemmTNGroup.amax_a / amax_b + prec 4 (struct sizes)
+ *   103: NudfChainStep.X3 / ldx3, prec 4 chains, NudfPackFrag.dtype 4 */
+#define NUDF_ABI_VERSION 109
 int nudf_version(void);
+/* every argument struct of this header, once, in the order of their definitions */
+#define NUDF_ABI_STRUCTS(X) \
+  X(NudfGemmNN) X(NudfGemmTN) X(NudfGemmTNProblem) X(NudfGemmTNGroup) X(NudfComposite) X(NudfCompositeGrad) \
+  X(NudfUpsample) X(NudfPixelBlend) X(NudfPixelComposite) X(NudfPatchBlend) X(NudfPatchWarp) X(NudfBlendLoss) \
+  X(NudfAdamTensor) X(NudfAdamGroup) X(NudfAdam) X(NudfChainStep) X(NudfChain) X(NudfPackFrag) X(NudfPackLayer) \
+  X(NudfPackMulti) X(NudfUnpackLayer) X(NudfUnpackMulti) X(NudfRayBatch) X(NudfMeshUDF) X(NudfMeshUDFSparse) \
+  X(NudfIsoSurface) X(NudfIsoSurfaceSparse) X(NudfPointCloud) X(NudfMeshTopo) X(NudfMeshOrient) X(NudfMeshRaster)
+/* entry i of that list as the library was compiled (host code only): returns sizeof and stores the struct's name in *name
+ * (name may be NULL); -1 for an i outside the list.  A caller that passes these structs by reference checks every size
+ * after the version (the Python loader refuses a library in which one differs). */
+int nudf_abi_struct(int i, const char** name);
 const char* nudf_last_error(void);
 
 /* ------------------------------------------------------------------------------------
@@ -682,9 +706,6 @@ int nudf_mlp_chain(const NudfChain* args, void* stream);
  * nudf_last_error, empty name, zero grid).  An empty launch (P <= 0 or no steps) gives 0, an empty name and a zero grid.
  * The choice depends on the process-wide settings NUDF_CHAIN_ROWS / _QUAD / _T16 / _WIN2. */
 int nudf_mlp_chain_plan(const NudfChain* args, char* name, int capacity, int32_t* out);
-/* NUDF_CH_MAX_STEPS of the header the library was compiled against: the array bound sets sizeof(NudfChain), so a caller that
- * passes the struct by reference checks it as it checks nudf_version() (the Python loader refuses a library that differs). */
-int nudf_chain_max_steps(void);
 /* 16-bit mode (prec 1 / 2), 64-point tiles: chains whose steps ALL contract in the same 16-bit type run on the 16-bit-tile
  * kernel -- the LDS activation tile holds that type (the MFMA operand itself: one ds_read_b128 per 32-row tile and k step, no
  * conversion in the K loop, 37 KB per workgroup = three workgroups per CU), the epilogue rounds the new activations once on
@@ -922,7 +943,6 @@ typedef struct NudfMeshUDFSparse {
   float max_thr;              /* 1.74 h                                                                               */
   int32_t pad_;
 } NudfMeshUDFSparse;
-int nudf_meshudf_sparse_struct_size(void);                                      /* sizeof(NudfMeshUDFSparse): the loader refuses a library that differs */
 int nudf_meshudf_sparse_classify(const NudfMeshUDFSparse* args, void* stream);  /* one workgroup per brick, its U in LDS */
 int nudf_meshudf_sparse_edges(const NudfMeshUDFSparse* args, void* stream);     /* one thread per cell with triangles */
 int nudf_meshudf_sparse_emit(const NudfMeshUDFSparse* args, void* stream);      /* one thread per cell with triangles */
@@ -961,7 +981,6 @@ typedef struct NudfIsoSurface {
   int32_t N;
   float level;
 } NudfIsoSurface;
-int nudf_isosurface_struct_size(void);                                   /* sizeof(NudfIsoSurface): the loader refuses a library that differs */
 int nudf_isosurface_classify(const NudfIsoSurface* args, void* stream);  /* one thread per cell   */
 int nudf_isosurface_emit(const NudfIsoSurface* args, void* stream);      /* one thread per cell with triangles */
 int nudf_isosurface_vertices(const NudfIsoSurface* args, void* stream);  /* one thread per flagged edge */
@@ -1003,7 +1022,6 @@ typedef struct NudfIsoSurfaceSparse {
   int32_t nb;                 /* ceil((N - 1) / B)                                                                   */
   float level;
 } NudfIsoSurfaceSparse;
-int nudf_isosurface_sparse_struct_size(void);                                         /* sizeof(NudfIsoSurfaceSparse) */
 int nudf_isosurface_sparse_classify(const NudfIsoSurfaceSparse* args, void* stream);  /* one workgroup per brick, its F in LDS */
 int nudf_isosurface_sparse_edges(const NudfIsoSurfaceSparse* args, void* stream);     /* one thread per cell with triangles */
 int nudf_isosurface_sparse_emit(const NudfIsoSurfaceSparse* args, void* stream);      /* one thread per cell with triangles */
@@ -1186,7 +1204,6 @@ typedef struct NudfMeshOrient {
   int64_t n_medges;
   int64_t n_comps;
 } NudfMeshOrient;
-int nudf_meshorient_struct_size(void);                                     /* sizeof(NudfMeshOrient)          */
 int nudf_meshorient_hook(const NudfMeshOrient* args, void* stream);        /* one thread per manifold edge    */
 int nudf_meshorient_jump(const NudfMeshOrient* args, void* stream);        /* one thread per face             */
 int nudf_meshorient_check(const NudfMeshOrient* args, void* stream);       /* one thread per manifold edge    */
@@ -1258,7 +1275,6 @@ typedef struct NudfMeshRaster {
   int32_t W;
   int32_t image_f32;         /* colour: 1 = float32 images, 0 = uint8                                                */
 } NudfMeshRaster;
-int nudf_meshraster_struct_size(void);                                     /* sizeof(NudfMeshRaster)          */
 int nudf_meshraster_project(const NudfMeshRaster* args, void* stream);     /* one thread per (view, vertex)   */
 int nudf_meshraster_bounds(const NudfMeshRaster* args, void* stream);      /* one thread per (view, face)     */
 int nudf_meshraster_draw_small(const NudfMeshRaster* args, void* stream);  /* one thread per entry            */

@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must be loaded before libnudf, see module docstring
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NUDF_LIB") or os.path.join(_HERE, "libnudf.so")      # NUDF_LIB: A/B builds of the library
-ABI_VERSION = 108         # nudf_version() of the include/nudf.h these ctypes structures mirror
+ABI_VERSION = 109         # NUDF_ABI_VERSION of the include/nudf.h these ctypes structures mirror
 
 c_fp = C.c_void_p
 i32 = C.c_int32
@@ -264,130 +264,123 @@ LW_COUNT = 16
 EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMOID=7, UDFHEAD=8,
            SKIPSPLIT=9, RELU_DUAL=10, ADDMASK=11, MULSP=12)
 
-# every symbol include/nudf.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "nudf_version", "nudf_chain_max_steps", "nudf_last_error", "nudf_set_status_flag", "nudf_status_flag", "nudf_gemm_nn", "nudf_gemm_tn", "nudf_gemm_tn_grouped", "nudf_gemm_tn_grouped_workspace", "nudf_gemm_tn_grouped_plan", "nudf_gemm_tn_grouped_kernel", "nudf_set_tn_flags", "nudf_patch_metric", "nudf_set_tn_debug", "nudf_composite_fwd",
-    "nudf_composite_bwd", "nudf_partial_sums", "nudf_composite_colour_finish", "nudf_upsample", "nudf_merge", "nudf_merge_points", "nudf_coarse_z", "nudf_coarse_start", "nudf_outside_z",
-    "nudf_ray_points", "nudf_posenc", "nudf_posenc_vjp", "nudf_copy_cols",
-    "nudf_udf_grad_seed", "nudf_udf_head_bwd", "nudf_signed_colsum", "nudf_sigmoid_head_bwd",
-    "nudf_weightnorm_pack", "nudf_weightnorm_unpack_grad",
-    "nudf_pixel_blend_fwd", "nudf_pixel_blend_bwd", "nudf_pixel_composite_fwd", "nudf_pixel_composite_bwd",
-    "nudf_patch_blend_fwd", "nudf_patch_blend_bwd", "nudf_ssim_patch", "nudf_pixel_warp", "nudf_patch_warp",
-    "nudf_adam_step", "nudf_adam_chunk", "nudf_mlp_chain", "nudf_mlp_chain_plan", "nudf_set_chain_t16", "nudf_pack_frag",
-    "nudf_weightnorm_pack_multi", "nudf_weightnorm_unpack_grad_multi",
-    "nudf_scalars_fwd", "nudf_scalars_bwd", "nudf_l1_sum_fwd", "nudf_l1_sum_bwd",
-    "nudf_sums_errors_fwd", "nudf_sums_errors_bwd", "nudf_color_loss_fwd", "nudf_color_loss_bwd",
-    "nudf_gen_ray_batch", "nudf_color_loss_sums", "nudf_color_loss_finish",
-    "nudf_step_loss_fwd", "nudf_step_loss_bwd", "nudf_col0_seed4",
-    "nudf_blend_loss_prepare", "nudf_blend_loss_fwd", "nudf_blend_loss_bwd",
-    "nudf_meshudf_classify", "nudf_meshudf_emit", "nudf_meshudf_vertices",
-    "nudf_meshudf_sparse_struct_size", "nudf_meshudf_sparse_classify", "nudf_meshudf_sparse_edges",
-    "nudf_meshudf_sparse_emit", "nudf_meshudf_sparse_vertices",
-    "nudf_isosurface_struct_size", "nudf_isosurface_classify", "nudf_isosurface_emit", "nudf_isosurface_vertices",
-    "nudf_isosurface_sparse_struct_size", "nudf_isosurface_sparse_classify", "nudf_isosurface_sparse_edges",
-    "nudf_isosurface_sparse_emit", "nudf_isosurface_sparse_vertices",
-    "nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells", "nudf_pc_thin_round", "nudf_pc_nearest",
-    "nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit", "nudf_meshtopo_smooth",
-    "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump", "nudf_meshtopo_views",
-    "nudf_meshorient_struct_size", "nudf_meshorient_hook", "nudf_meshorient_jump", "nudf_meshorient_check",
-    "nudf_meshorient_outward", "nudf_meshorient_normals",
-    "nudf_meshraster_struct_size", "nudf_meshraster_project", "nudf_meshraster_bounds", "nudf_meshraster_draw_small",
-    "nudf_meshraster_draw_large", "nudf_meshraster_resolve", "nudf_meshraster_visible", "nudf_meshraster_colour",
-]
+# the ctypes mirror of every argument struct, under the header's name: NudfX is the class X above, without exception
+MIRRORS = {"Nudf" + c.__name__: c for c in C.Structure.__subclasses__() if c.__module__ == __name__}
 
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
-_ARGTYPES = {
-    "nudf_gemm_nn": [C.POINTER(GemmNN), _P],
-    "nudf_gemm_tn": [C.POINTER(GemmTN), _P],
-    "nudf_gemm_tn_grouped": [C.POINTER(GemmTNGroup), _P],
-    "nudf_gemm_tn_grouped_workspace": [C.POINTER(GemmTNGroup)],
-    "nudf_gemm_tn_grouped_plan": [C.POINTER(GemmTNGroup), C.POINTER(C.c_int32), i32],
-    "nudf_gemm_tn_grouped_kernel": [C.POINTER(GemmTNGroup), C.c_char_p, i32, C.POINTER(C.c_int32)],
-    "nudf_set_tn_flags": [i32],
-    "nudf_set_tn_debug": [_P],
-    "nudf_composite_fwd": [C.POINTER(Composite), _P],
-    "nudf_composite_bwd": [C.POINTER(Composite), C.POINTER(CompositeGrad), _P],
-    "nudf_partial_sums": [_P, _I, _I, _P, _P],
-    "nudf_composite_colour_finish": [_P, _P, _I, _I, _P, _P, _P, _P, _P],
-    "nudf_upsample": [C.POINTER(Upsample), _P],
-    "nudf_merge": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P],
-    "nudf_coarse_z": [_P, _P, _I, _P, _I, _I, _P, _P, _P],
-    "nudf_coarse_start": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "nudf_merge_points": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "nudf_outside_z": [_P, _I, _P, _I, _I, _I, _P, _P],
-    "nudf_ray_points": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
-    "nudf_posenc": [_P, _I, _I, _P, _I, _I, _F, _I, _P, _I, _F, _P, _I, _F, _P],
-    "nudf_posenc_vjp": [_P, _I, _I, _I, _F, _I, _P, _I, _F, _P, _I, _F, _P, _P],
-    "nudf_copy_cols": [_P, _I, _I, _P, _I, _I, _I, _F, _P],
-    "nudf_udf_grad_seed": [_P, _P, _P, _I, _F, _I, _I, _F, _P, _I, _P],
-    "nudf_udf_head_bwd": [_P, _P, _P, _I, _I, _I, _F, _P, _I, _P],
-    "nudf_signed_colsum": [_P, _P, _I, _I, _I, _F, _P, _P],
-    "nudf_sigmoid_head_bwd": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, _P],
-    "nudf_weightnorm_pack": [_P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P],
-    "nudf_weightnorm_unpack_grad": [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "nudf_pixel_blend_fwd": [C.POINTER(PixelBlend), _P],
-    "nudf_pixel_blend_bwd": [C.POINTER(PixelBlend), _P, _P, _P],
-    "nudf_pixel_composite_fwd": [C.POINTER(PixelComposite), _P],
-    "nudf_pixel_composite_bwd": [C.POINTER(PixelComposite), _P, _P, _P, _P, _P, _P],
-    "nudf_patch_blend_fwd": [C.POINTER(PatchBlend), _P],
-    "nudf_patch_blend_bwd": [C.POINTER(PatchBlend), _P, _P, _P, _P],
-    "nudf_pixel_warp": [C.POINTER(PixelBlend), _P, _P, _P],
-    "nudf_patch_warp": [C.POINTER(PatchWarp), _P],
-    "nudf_ssim_patch": [_P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "nudf_patch_metric": [_I] + [_P, _P, _P, _I, _I, _P, _P, _P, _P],
-    "nudf_adam_step": [C.POINTER(Adam), _P],
-    "nudf_mlp_chain": [C.POINTER(Chain), _P],
-    "nudf_mlp_chain_plan": [C.POINTER(Chain), C.c_char_p, i32, C.POINTER(C.c_int32)],
-    "nudf_pack_frag": [_P, _I, _I, _I, _P, _P],
-    "nudf_weightnorm_pack_multi": [C.POINTER(PackMulti), _P],
-    "nudf_weightnorm_unpack_grad_multi": [C.POINTER(UnpackMulti), _P],
-    "nudf_scalars_fwd": [_P, _P, _P, _F, _P, _P, _P],
-    "nudf_scalars_bwd": [_P, _P, _P, _F, _P, _P, _P],
-    "nudf_l1_sum_fwd": [_P, _P, _I, _P, _P],
-    "nudf_l1_sum_bwd": [_P, _P, _I, _P, _P, _P],
-    "nudf_sums_errors_fwd": [_P, _F, _P, _P],
-    "nudf_sums_errors_bwd": [_P, _F, _P, _P, _P],
-    "nudf_color_loss_fwd": [_P, _P, _P, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P],
-    "nudf_color_loss_bwd": [_P, _P, _P, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P],
-    "nudf_gen_ray_batch": [C.POINTER(RayBatch), _P],
-    "nudf_color_loss_sums": [_P, _P, _P, _I, _P, _I, _P, _P],
-    "nudf_color_loss_finish": [_P, _I, _F, _F, _F, _P, _P, _P, _P],
-    "nudf_step_loss_fwd": [_P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _I, _P],
-    "nudf_step_loss_bwd": [_P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P],
-    "nudf_col0_seed4": [_P, _P, _F, _I, _I, _P, _P, _P],
-    "nudf_blend_loss_prepare": [C.POINTER(BlendLoss), _P],
-    "nudf_blend_loss_fwd": [C.POINTER(BlendLoss), _P],
-    "nudf_blend_loss_bwd": [C.POINTER(BlendLoss), _P],
-    "nudf_meshudf_classify": [C.POINTER(MeshUDF), _P],
-    "nudf_meshudf_emit": [C.POINTER(MeshUDF), _P],
-    "nudf_meshudf_vertices": [C.POINTER(MeshUDF), _P],
-    **{n: [C.POINTER(MeshUDFSparse), _P] for n in ("nudf_meshudf_sparse_classify", "nudf_meshudf_sparse_edges",
-                                                   "nudf_meshudf_sparse_emit", "nudf_meshudf_sparse_vertices")},
-    **{n: [C.POINTER(IsoSurface), _P] for n in ("nudf_isosurface_classify", "nudf_isosurface_emit",
-                                                "nudf_isosurface_vertices")},
-    **{n: [C.POINTER(IsoSurfaceSparse), _P] for n in ("nudf_isosurface_sparse_classify", "nudf_isosurface_sparse_edges",
-                                                      "nudf_isosurface_sparse_emit", "nudf_isosurface_sparse_vertices")},
-    **{n: [C.POINTER(PointCloud), _P] for n in ("nudf_pc_tri_count", "nudf_pc_tri_emit", "nudf_pc_keys", "nudf_pc_cells",
-                                                "nudf_pc_thin_round", "nudf_pc_nearest")},
-    **{n: [C.POINTER(MeshTopo), _P] for n in ("nudf_meshtopo_edges", "nudf_meshtopo_fill_count", "nudf_meshtopo_fill_emit",
-                                              "nudf_meshtopo_smooth", "nudf_meshtopo_cc_hook", "nudf_meshtopo_cc_jump",
-                                              "nudf_meshtopo_views")},
-    **{n: [C.POINTER(MeshOrient), _P] for n in ("nudf_meshorient_hook", "nudf_meshorient_jump", "nudf_meshorient_check",
-                                                "nudf_meshorient_outward", "nudf_meshorient_normals")},
-    **{n: [C.POINTER(MeshRaster), _P] for n in ("nudf_meshraster_project", "nudf_meshraster_bounds",
-                                                "nudf_meshraster_draw_small", "nudf_meshraster_draw_large",
-                                                "nudf_meshraster_resolve", "nudf_meshraster_visible",
-                                                "nudf_meshraster_colour")},
+# every symbol include/nudf.h declares: name -> (restype, argtypes)   (checked by tests/test_abi.py)
+SIGNATURES = {
+    "nudf_version": (_I, []),
+    "nudf_abi_struct": (_I, [_I, C.POINTER(C.c_char_p)]),
+    "nudf_last_error": (C.c_char_p, []),
+    "nudf_set_status_flag": (_I, [_P]),
+    "nudf_status_flag": (_P, []),
+    "nudf_gemm_nn": (_I, [C.POINTER(GemmNN), _P]),
+    "nudf_gemm_tn": (_I, [C.POINTER(GemmTN), _P]),
+    "nudf_gemm_tn_grouped": (_I, [C.POINTER(GemmTNGroup), _P]),
+    "nudf_gemm_tn_grouped_workspace": (C.c_int64, [C.POINTER(GemmTNGroup)]),
+    "nudf_gemm_tn_grouped_plan": (_I, [C.POINTER(GemmTNGroup), C.POINTER(C.c_int32), i32]),
+    "nudf_gemm_tn_grouped_kernel": (_I, [C.POINTER(GemmTNGroup), C.c_char_p, i32, C.POINTER(C.c_int32)]),
+    "nudf_set_tn_flags": (_I, [i32]),
+    "nudf_set_tn_debug": (_I, [_P]),
+    "nudf_composite_fwd": (_I, [C.POINTER(Composite), _P]),
+    "nudf_composite_bwd": (_I, [C.POINTER(Composite), C.POINTER(CompositeGrad), _P]),
+    "nudf_partial_sums": (_I, [_P, _I, _I, _P, _P]),
+    "nudf_composite_colour_finish": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "nudf_upsample": (_I, [C.POINTER(Upsample), _P]),
+    "nudf_merge": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "nudf_coarse_z": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "nudf_coarse_start": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "nudf_merge_points": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "nudf_outside_z": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
+    "nudf_ray_points": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "nudf_posenc": (_I, [_P, _I, _I, _P, _I, _I, _F, _I, _P, _I, _F, _P, _I, _F, _P]),
+    "nudf_posenc_vjp": (_I, [_P, _I, _I, _I, _F, _I, _P, _I, _F, _P, _I, _F, _P, _P]),
+    "nudf_copy_cols": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P]),
+    "nudf_udf_grad_seed": (_I, [_P, _P, _P, _I, _F, _I, _I, _F, _P, _I, _P]),
+    "nudf_udf_head_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _P, _I, _P]),
+    "nudf_signed_colsum": (_I, [_P, _P, _I, _I, _I, _F, _P, _P]),
+    "nudf_sigmoid_head_bwd": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
+    "nudf_weightnorm_pack": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "nudf_weightnorm_unpack_grad": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "nudf_pixel_blend_fwd": (_I, [C.POINTER(PixelBlend), _P]),
+    "nudf_pixel_blend_bwd": (_I, [C.POINTER(PixelBlend), _P, _P, _P]),
+    "nudf_pixel_composite_fwd": (_I, [C.POINTER(PixelComposite), _P]),
+    "nudf_pixel_composite_bwd": (_I, [C.POINTER(PixelComposite), _P, _P, _P, _P, _P, _P]),
+    "nudf_patch_blend_fwd": (_I, [C.POINTER(PatchBlend), _P]),
+    "nudf_patch_blend_bwd": (_I, [C.POINTER(PatchBlend), _P, _P, _P, _P]),
+    "nudf_pixel_warp": (_I, [C.POINTER(PixelBlend), _P, _P, _P]),
+    "nudf_patch_warp": (_I, [C.POINTER(PatchWarp), _P]),
+    "nudf_ssim_patch": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "nudf_patch_metric": (_I, [_I] + [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "nudf_adam_step": (_I, [C.POINTER(Adam), _P]),
+    "nudf_adam_chunk": (_I, []),
+    "nudf_mlp_chain": (_I, [C.POINTER(Chain), _P]),
+    "nudf_mlp_chain_plan": (_I, [C.POINTER(Chain), C.c_char_p, i32, C.POINTER(C.c_int32)]),
+    "nudf_set_chain_t16": (_I, [_I]),
+    "nudf_pack_frag": (_I, [_P, _I, _I, _I, _P, _P]),
+    "nudf_weightnorm_pack_multi": (_I, [C.POINTER(PackMulti), _P]),
+    "nudf_weightnorm_unpack_grad_multi": (_I, [C.POINTER(UnpackMulti), _P]),
+    "nudf_scalars_fwd": (_I, [_P, _P, _P, _F, _P, _P, _P]),
+    "nudf_scalars_bwd": (_I, [_P, _P, _P, _F, _P, _P, _P]),
+    "nudf_l1_sum_fwd": (_I, [_P, _P, _I, _P, _P]),
+    "nudf_l1_sum_bwd": (_I, [_P, _P, _I, _P, _P, _P]),
+    "nudf_sums_errors_fwd": (_I, [_P, _F, _P, _P]),
+    "nudf_sums_errors_bwd": (_I, [_P, _F, _P, _P, _P]),
+    "nudf_color_loss_fwd": (_I, [_P, _P, _P, _I, _P, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "nudf_color_loss_bwd": (_I, [_P, _P, _P, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "nudf_gen_ray_batch": (_I, [C.POINTER(RayBatch), _P]),
+    "nudf_color_loss_sums": (_I, [_P, _P, _P, _I, _P, _I, _P, _P]),
+    "nudf_color_loss_finish": (_I, [_P, _I, _F, _F, _F, _P, _P, _P, _P]),
+    "nudf_step_loss_fwd": (_I, [_P, _P, _P, _I, _P, _I, _P, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _I, _P]),
+    "nudf_step_loss_bwd": (_I, [_P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "nudf_col0_seed4": (_I, [_P, _P, _F, _I, _I, _P, _P, _P]),
+    # one struct and the stream: every entry point of these families
+    **{"nudf_" + n: (_I, [C.POINTER(st), _P]) for st, names in (
+        (BlendLoss, ("blend_loss_prepare", "blend_loss_fwd", "blend_loss_bwd")),
+        (MeshUDF, ("meshudf_classify", "meshudf_emit", "meshudf_vertices")),
+        (MeshUDFSparse, ("meshudf_sparse_classify", "meshudf_sparse_edges", "meshudf_sparse_emit",
+                         "meshudf_sparse_vertices")),
+        (IsoSurface, ("isosurface_classify", "isosurface_emit", "isosurface_vertices")),
+        (IsoSurfaceSparse, ("isosurface_sparse_classify", "isosurface_sparse_edges", "isosurface_sparse_emit",
+                            "isosurface_sparse_vertices")),
+        (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest")),
+        (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
+                    "meshtopo_cc_jump", "meshtopo_views")),
+        (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals")),
+        (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",
+                      "meshraster_resolve", "meshraster_visible", "meshraster_colour")),
+    ) for n in names},
 }
+SYMBOLS = list(SIGNATURES)
 
 _lib = None
 
 
-def _bind(l):
-    for name, at in _ARGTYPES.items():
-        fn = getattr(l, name)
-        fn.argtypes = at
-        fn.restype = C.c_int
+def _abi_mismatch(version, table):
+    """why a library that reports this nudf_version() and this {struct name: sizeof} table cannot be driven through the
+    mirrors above, or None when it can.  Pure: no library, no GPU."""
+    if version != ABI_VERSION:
+        return f"is ABI version {version}, this package binds {ABI_VERSION}"
+    for name, size in table.items():
+        if name not in MIRRORS:
+            return f"has an argument struct {name} that this package does not bind"
+        if size != C.sizeof(MIRRORS[name]):
+            return f"has a {name} of {size} bytes, this package binds {C.sizeof(MIRRORS[name])}"
+    missing = [name for name in MIRRORS if name not in table]
+    if missing:
+        return f"does not report {', '.join(missing)}, which this package binds"
+    return None
+
+
+def _abi_report(l):
+    """(nudf_version(), {struct name: sizeof}) of a loaded library.  The version is read first: a library of another version
+    is refused by that number, whether or not it has the table."""
+    version, table, name, i = int(l.nudf_version()), {}, C.c_char_p(), 0
+    if version == ABI_VERSION:
+        while (size := l.nudf_abi_struct(i, C.byref(name))) >= 0:
+            table[name.value.decode()], i = size, i + 1
+    return version, table
 
 
 def lib():
@@ -399,50 +392,20 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -m neuraludf_amd.build` "
                 "(the NeuralUDF hot path has no CPU/PyTorch fallback)")
         try:
-            _lib = C.CDLL(LIB_PATH)
+            l = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise NudfError(f"cannot load {LIB_PATH}: {e}") from e
-        _lib.nudf_last_error.restype = C.c_char_p
-        _lib.nudf_version.restype = C.c_int
-        _lib.nudf_adam_chunk.restype = C.c_int
-        if _lib.nudf_version() != ABI_VERSION:      # the ctypes structures below mirror include/nudf.h of exactly this version
-            v, _lib = _lib.nudf_version(), None
-            raise NudfError(f"{LIB_PATH} is ABI version {v}, this package binds {ABI_VERSION}: rebuild with "
-                            "`python -m neuraludf_amd.build --force`")
-        # (the step capacity of NudfChain sets its size: a library built before it grew lacks the symbol or reports another bound)
-        steps = getattr(_lib, "nudf_chain_max_steps", None)
-        if steps is None or int(steps()) != CH_MAX_STEPS:
-            v, _lib = (None if steps is None else int(steps())), None
-            raise NudfError(f"{LIB_PATH} holds {v} chain steps per launch, this package binds {CH_MAX_STEPS}: rebuild with "
-                            "`python -m neuraludf_amd.build --force`")
-        # (NudfMeshUDFSparse came without a version step, which an existing test pins: its size is checked instead)
-        size = getattr(_lib, "nudf_meshudf_sparse_struct_size", None)
-        if size is None or int(size()) != C.sizeof(MeshUDFSparse):
-            v, _lib = (None if size is None else int(size())), None
-            raise NudfError(f"{LIB_PATH} has a NudfMeshUDFSparse of {v} bytes, this package binds {C.sizeof(MeshUDFSparse)}: "
-                            "rebuild with `python -m neuraludf_amd.build --force`")
-        for name, mirror in (("nudf_isosurface_struct_size", IsoSurface),
-                             ("nudf_isosurface_sparse_struct_size", IsoSurfaceSparse),       # (the same, for the level-set mesher
-                             ("nudf_meshorient_struct_size", MeshOrient),                    # the face orientation
-                             ("nudf_meshraster_struct_size", MeshRaster)):                   # and the rasteriser)
-            size = getattr(_lib, name, None)
-            if size is None or int(size()) != C.sizeof(mirror):
-                v, _lib = (None if size is None else int(size())), None
-                raise NudfError(f"{LIB_PATH}: {name}() is {v}, this package binds {C.sizeof(mirror)} bytes: rebuild with "
-                                "`python -m neuraludf_amd.build --force`")
-        # (the two dispatch reports came without a version step as well: a library from before them is refused by name)
-        for name in ("nudf_mlp_chain_plan", "nudf_gemm_tn_grouped_kernel"):
-            if getattr(_lib, name, None) is None:
-                _lib = None
-                raise NudfError(f"{LIB_PATH} does not export {name}: rebuild with `python -m neuraludf_amd.build --force`")
-        _bind(_lib)
-        _lib.nudf_gemm_tn_grouped_workspace.restype = C.c_int64
-        _lib.nudf_set_chain_t16.argtypes = [C.c_int]
-        _lib.nudf_set_chain_t16.restype = C.c_int
-        _lib.nudf_set_status_flag.argtypes = [C.c_void_p]
-        _lib.nudf_set_status_flag.restype = C.c_int
-        _lib.nudf_status_flag.argtypes = []
-        _lib.nudf_status_flag.restype = C.c_void_p
+        try:
+            why = _abi_mismatch(*_abi_report(l))
+            if why is None:
+                for name, (restype, argtypes) in SIGNATURES.items():
+                    fn = getattr(l, name)
+                    fn.restype, fn.argtypes = restype, argtypes
+        except AttributeError as e:
+            why = f"does not export every symbol of include/nudf.h ({e})"
+        if why is not None:
+            raise NudfError(f"{LIB_PATH} {why}: rebuild with `python -m neuraludf_amd.build --force`")
+        _lib = l
     return _lib
 
 

@@ -8,9 +8,6 @@
 __device__ __forceinline__ const float* mc_field(const NudfIsoSurface& a) { return a.F; }
 __device__ __forceinline__ const float* mc_field(const NudfIsoSurfaceSparse& a) { return a.F; }
 
-extern "C" int nudf_isosurface_struct_size(void) { return (int)sizeof(NudfIsoSurface); }
-extern "C" int nudf_isosurface_sparse_struct_size(void) { return (int)sizeof(NudfIsoSurfaceSparse); }
-
 MC_DENSE_ENTRY(nudf_isosurface_classify, NudfIsoSurface, mc_dense_cells(a), mc_dense_classify_kernel<McLevelRule, NudfIsoSurface>)
 MC_DENSE_ENTRY(nudf_isosurface_emit, NudfIsoSurface, a.n_cells, mc_dense_emit_kernel<NudfIsoSurface>)
 MC_DENSE_ENTRY(nudf_isosurface_vertices, NudfIsoSurface, a.n_edges, mc_dense_vertices_kernel<McLevelRule, NudfIsoSurface>)

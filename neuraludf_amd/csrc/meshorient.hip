@@ -183,8 +183,6 @@ static bool sizes_ok(const NudfMeshOrient& a) {
   NUDF_CHECK_LAUNCH(name);                                                                                \
   return 0
 
-extern "C" int nudf_meshorient_struct_size(void) { return (int)sizeof(NudfMeshOrient); }
-
 extern "C" int nudf_meshorient_hook(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
   if (!sizes_ok(a)) return refuse("nudf_meshorient_hook: bad sizes (n_verts must be < 2^31, n_medges <= 3 n_faces / 2)");

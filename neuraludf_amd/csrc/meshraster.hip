@@ -198,8 +198,6 @@ static bool sizes_ok(const NudfMeshRaster& a) {
 #define MR_NEED_IMAGE(name) \
   if (a.H < 1 || a.W < 1) return refuse(name ": H and W must be >= 1")
 
-extern "C" int nudf_meshraster_struct_size(void) { return (int)sizeof(NudfMeshRaster); }
-
 extern "C" int nudf_meshraster_project(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
   if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_project"));

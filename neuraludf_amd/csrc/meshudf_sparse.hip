@@ -5,8 +5,6 @@
 
 __device__ __forceinline__ const float* mc_field(const NudfMeshUDFSparse& a) { return a.U; }
 
-extern "C" int nudf_meshudf_sparse_struct_size(void) { return (int)sizeof(NudfMeshUDFSparse); }
-
 MC_SPARSE_CLASSIFY_ENTRY(nudf_meshudf_sparse_classify, NudfMeshUDFSparse, McUdfRule)
 MC_SPARSE_ENTRY(nudf_meshudf_sparse_edges, NudfMeshUDFSparse, a.n_cells, mc_sparse_edges_kernel<NudfMeshUDFSparse>)
 MC_SPARSE_ENTRY(nudf_meshudf_sparse_emit, NudfMeshUDFSparse, a.n_cells, mc_sparse_emit_kernel<NudfMeshUDFSparse>)

@@ -1598,8 +1598,6 @@ extern "C" int nudf_set_chain_t16(int on) {
   return old;
 }
 
-extern "C" int nudf_chain_max_steps(void) { return NUDF_CH_MAX_STEPS; }
-
 // what the check learns about a descriptor on its way and the selection needs
 struct ChainFacts {
   bool fused, any16, any3;   // a SEED step (two sweeps in one launch); a 16-bit step or 16-bit stored state; a split-mode step

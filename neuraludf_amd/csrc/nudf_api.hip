@@ -1,4 +1,4 @@
-// error plumbing + version for libnudf
+// error plumbing, version and struct table of libnudf
 #include "nudf_common.h"
 #include "../../include/nudf.h"
 #include <stdio.h>
@@ -10,7 +10,17 @@ extern "C" void nudf_set_error(const char* where, hipError_t e) {
   snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
 }
 extern "C" const char* nudf_last_error(void) { return g_err; }
-extern "C" int nudf_version(void) { return 108; }   // 108: nudf_meshtopo_* + NudfMeshTopo (mesh clean-up); 107: nudf_pc_* + NudfPointCloud (Chamfer evaluation); 106: nudf_meshudf_* + NudfMeshUDF; 105: NudfChain.tile_scale / tile_amax_in / tile_amax_out; 104: NudfChain.absmax_out, NudfGemmTNGroup.amax_a / amax_b + prec 4 (struct sizes); 103: NudfChainStep.X3 / ldx3, prec 4 chains, NudfPackFrag.dtype 4
+extern "C" int nudf_version(void) { return NUDF_ABI_VERSION; }   // (the change log is at the define)
+
+// every argument struct as THIS build lays it out: what a by-reference caller compares its own mirrors with
+extern "C" int nudf_abi_struct(int i, const char** name) {
+#define NUDF_ABI_ROW(S) {#S, (int)sizeof(S)},
+  static const struct { const char* name; int size; } table[] = {NUDF_ABI_STRUCTS(NUDF_ABI_ROW)};
+#undef NUDF_ABI_ROW
+  if (i < 0 || i >= (int)(sizeof(table) / sizeof(table[0]))) return -1;
+  if (name) *name = table[i].name;
+  return table[i].size;
+}
 
 // The non-finite status word (include/nudf.h): ONE int32 in device memory the caller owns.  The launchers of the three
 // kernels that can see a non-finite value first hand the pointer to their kernels as a plain kernel argument (baked into a

@@ -1,5 +1,7 @@
-"""CPU checks of the C-ABI boundary: the library builds for gfx950, loads, exports every symbol
-declared in include/nudf.h, and the product path refuses to run without a GPU (no fallback)."""
+"""CPU checks of the C-ABI boundary, each once for the whole header: the library builds for gfx950, loads and exports every
+symbol include/nudf.h declares; one version in header, package and library; every argument struct's ctypes mirror against a
+C compile of the header and against the table the library reports; the loader's refusals; the hand-copied constants; and the
+product path refuses to run without a GPU (no fallback)."""
 import os
 import re
 
@@ -9,78 +11,176 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+HEADER = open(os.path.join(ROOT, "include", "nudf.h")).read()
+
+
+def header_structs():
+    """{NudfX: [field, ...]} of every `typedef struct NudfX {...} NudfX;` of the header, in its order.  A declaration may
+    hold several declarators (`int32_t M, N, K;`) and arrays (`origin[3]`, `prob[NUDF_TN_MAX_PROBLEMS]`)."""
+    out = {}
+    for cname, body in re.findall(r"typedef struct (Nudf\w+) \{(.*?)\} \1;", HEADER, re.S):
+        body = re.sub(r"\[[^\]]*\]", "", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+        out[cname] = [re.findall(r"[A-Za-z_]\w*", part)[-1] for decl in body.split(";") if decl.strip()
+                      for part in decl.split(",")]
+    return out
+
+
+def header_constants():
+    """({NUDF_X: n} of every `NUDF_X = n` enum entry and every `#define NUDF_X n` of the header, the enum entries' names)"""
+    code = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    enums = {k: int(v) for k, v in re.findall(r"\b(NUDF_\w+) = (\d+)", code)}
+    defines = {k: int(v) for k, v in re.findall(r"^#define (NUDF_\w+) (\d+)\b", code, re.M)}
+    assert enums and defines and not set(enums) & set(defines)
+    return {**enums, **defines}, set(enums)
+
+
+def mirror_of(cname):
+    from neuraludf_amd import _lib
+    return getattr(_lib, cname[len("Nudf"):])               # the mirror of NudfX is _lib.X, without exception
+
+
+def mirror_fields(st):
+    return ["in" if f[0] == "in_" else f[0] for f in st._fields_]       # `in` is a Python keyword: the mirrors say in_
+
+
 def test_library_builds_and_exports_header_symbols():
     from neuraludf_amd import build, _lib
     path = build.build()
     assert os.path.exists(path)
     lib = _lib.lib()
-    assert lib.nudf_version() >= 105
-    hdr = open(os.path.join(ROOT, "include", "nudf.h")).read()
-    declared = sorted(set(re.findall(r"\b(nudf_[a-z0-9_]+)\s*\(", hdr)))
+    declared = sorted(set(re.findall(r"\b(nudf_[a-z0-9_]+)\s*\(", HEADER)))
     assert declared, "no declarations found"
     for s in declared:
         assert hasattr(lib, s), f"{s} declared in include/nudf.h but not exported"
+    assert sorted(_lib.SIGNATURES) == declared
     assert sorted(_lib.SYMBOLS) == declared
 
 
-def test_ctypes_structs_match_header_field_counts():
-    from neuraludf_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "nudf.h")).read()
-    for cname, st in [("NudfGemmNN", _lib.GemmNN), ("NudfGemmTN", _lib.GemmTN), ("NudfComposite", _lib.Composite),
-                      ("NudfCompositeGrad", _lib.CompositeGrad), ("NudfUpsample", _lib.Upsample),
-                      ("NudfPixelBlend", _lib.PixelBlend), ("NudfPixelComposite", _lib.PixelComposite),
-                      ("NudfPatchBlend", _lib.PatchBlend), ("NudfPatchWarp", _lib.PatchWarp), ("NudfAdamTensor", _lib.AdamTensor),
-                      ("NudfAdamGroup", _lib.AdamGroup), ("NudfChainStep", _lib.ChainStep), ("NudfRayBatch", _lib.RayBatch),
-                      ("NudfGemmTNProblem", _lib.GemmTNProblem), ("NudfBlendLoss", _lib.BlendLoss)]:
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            for part in decl.split(","):
-                names.append(re.findall(r"[A-Za-z_0-9]+", part)[-1])
-        assert names == [f[0] for f in st._fields_], cname
+def test_one_version_in_header_package_and_library():
+    from neuraludf_amd import build, _lib
+    build.build()
+    version = header_constants()[0]["NUDF_ABI_VERSION"]
+    assert version == _lib.ABI_VERSION == _lib.lib().nudf_version()
 
 
-def test_ctypes_struct_layouts_match_a_c_compile_of_the_header(tmp_path):
-    """sizeof and every field offset of the by-value argument structs, as gcc lays out include/nudf.h, against the ctypes
-    mirrors of neuraludf_amd/_lib.py (the field-name test above cannot see padding or type widths)."""
+def test_struct_list_is_the_same_everywhere():
+    """the typedefs of the header, its NUDF_ABI_STRUCTS list and the ctypes.Structure subclasses of _lib: a struct forgotten
+    in any of the three fails here"""
     import ctypes as C
+    from neuraludf_amd import _lib
+    listed = re.search(r"#define NUDF_ABI_STRUCTS\(X\)((?:.*\\\n)*.*)", HEADER).group(1)
+    listed = re.findall(r"X\((\w+)\)", listed)
+    assert listed == list(header_structs()) and len(listed) == len(set(listed)) == 31
+    classes = {"Nudf" + k for k, v in vars(_lib).items() if isinstance(v, type) and issubclass(v, C.Structure)}
+    assert classes == set(listed) == set(_lib.MIRRORS)
+    assert all(_lib.MIRRORS[c] is mirror_of(c) for c in listed)
+
+
+def test_library_struct_table_equals_the_mirrors():
+    """what nudf_abi_struct reports, as the loader reads it, against ctypes.sizeof of every mirror -- the step capacity of
+    NudfChain included, which sets its size"""
+    import ctypes as C
+    from neuraludf_amd import build, _lib
+    build.build()
+    lib = _lib.lib()
+    version, table = _lib._abi_report(lib)
+    assert version == _lib.ABI_VERSION
+    assert table == {c: C.sizeof(mirror_of(c)) for c in header_structs()} and len(table) == 31
+    assert list(table) == list(header_structs())
+    assert C.sizeof(_lib.Chain) == C.sizeof(_lib.ChainStep) * _lib.CH_MAX_STEPS + _lib.Chain.step.offset
+    name = C.c_char_p()
+    assert lib.nudf_abi_struct(31, C.byref(name)) == -1 and lib.nudf_abi_struct(-1, C.byref(name)) == -1
+    assert lib.nudf_abi_struct(0, None) == C.sizeof(_lib.GemmNN)
+
+
+def test_loader_refusals():
+    """_abi_mismatch is pure: made-up reports give a refusal that names the offending item, the real values pass"""
+    import ctypes as C
+    from neuraludf_amd import _lib
+    v = _lib.ABI_VERSION
+    good = {c: C.sizeof(m) for c, m in _lib.MIRRORS.items()}
+    assert _lib._abi_mismatch(v, good) is None
+    for other in (v - 1, v + 1, 0):
+        why = _lib._abi_mismatch(other, good)
+        assert f"version {other}" in why and str(v) in why
+    assert f"version {v - 1}" in _lib._abi_mismatch(v - 1, {})          # an older library has no table: refused by version
+    why = _lib._abi_mismatch(v, {**good, "NudfComposite": good["NudfComposite"] + 8})
+    assert "NudfComposite" in why and str(good["NudfComposite"] + 8) in why and str(good["NudfComposite"]) in why
+    why = _lib._abi_mismatch(v, {**good, "NudfNewThing": 64})
+    assert "NudfNewThing" in why
+    why = _lib._abi_mismatch(v, {c: s for c, s in good.items() if c != "NudfPointCloud"})
+    assert "NudfPointCloud" in why
+    assert "NudfGemmNN" in _lib._abi_mismatch(v, {})
+
+
+def test_python_constants_equal_the_header():
+    """every hand-copied constant of _lib against the enum entries and #defines of include/nudf.h"""
+    import ctypes as C
+    from neuraludf_amd import _lib
+    hdr, enums = header_constants()
+
+    def family(prefix, skip=()):
+        return {k[len(prefix):]: hdr[k] for k in enums if k.startswith(prefix) and not k[len(prefix):].startswith(skip)}
+
+    assert _lib.EPI == family("NUDF_EPI_")
+    assert _lib.CH == family("NUDF_CH_", skip="INIT_") and "SEED" in _lib.CH
+    assert _lib.CH_INIT == family("NUDF_CH_INIT_")
+    assert {k.upper(): v for k, v in _lib.LW.items()} == family("NUDF_LW_", skip="COUNT")
+    assert max(_lib.LW.values()) < _lib.LW_COUNT == hdr["NUDF_LW_COUNT"]
+    status = family("NUDF_STATUS_")
+    assert status == {k[len("STATUS_"):]: v for k, v in vars(_lib).items() if k.startswith("STATUS_")} and len(status) == 3
+    for name in ("CH_MAX_STEPS", "CH_STATE16", "CH_P4_X1", "CH_P4_C1", "TN_MAX_PROBLEMS", "ADAM_MAX_TENSORS",
+                 "ADAM_MAX_GROUPS", "PACK_MAX_LAYERS", "PACK_MAX_FRAGS"):
+        assert getattr(_lib, name) == hdr["NUDF_" + name], name
+    assert _lib.CH_MAX_STEPS >= 19               # forward + input gradient of a 9-layer UDF network in one launch
+    assert C.sizeof(_lib.Chain) <= 4096          # travels by value in the kernel-argument segment
+
+
+def test_ctypes_structs_match_header_field_counts():
+    structs = header_structs()
+    assert len(structs) == 31
+    for cname, names in structs.items():
+        assert names == mirror_fields(mirror_of(cname)), cname
+
+
+@pytest.fixture(scope="module")
+def c_layout(tmp_path_factory):
+    """{(NudfX, field): (offset, size), (NudfX, "sizeof"): (0, sizeof)} of every struct as gcc lays out include/nudf.h:
+    one compile for the module"""
     import shutil
     import subprocess
-    from neuraludf_amd import _lib
     gcc = shutil.which("gcc")
     if gcc is None:
         pytest.skip("no gcc on this box")
-    pairs = [("NudfBlendLoss", _lib.BlendLoss), ("NudfGemmNN", _lib.GemmNN), ("NudfGemmTN", _lib.GemmTN), ("NudfGemmTNProblem", _lib.GemmTNProblem),
-             ("NudfGemmTNGroup", _lib.GemmTNGroup), ("NudfComposite", _lib.Composite), ("NudfCompositeGrad", _lib.CompositeGrad),
-             ("NudfUpsample", _lib.Upsample), ("NudfPixelBlend", _lib.PixelBlend), ("NudfPixelComposite", _lib.PixelComposite),
-             ("NudfPatchBlend", _lib.PatchBlend), ("NudfPatchWarp", _lib.PatchWarp), ("NudfAdamTensor", _lib.AdamTensor),
-             ("NudfAdamGroup", _lib.AdamGroup), ("NudfChainStep", _lib.ChainStep), ("NudfChain", _lib.Chain),
-             ("NudfRayBatch", _lib.RayBatch), ("NudfAdam", _lib.Adam), ("NudfPackFrag", _lib.PackFrag),
-             ("NudfPackLayer", _lib.PackLayer), ("NudfPackMulti", _lib.PackMulti), ("NudfUnpackLayer", _lib.UnpackLayer),
-             ("NudfUnpackMulti", _lib.UnpackMulti)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nudf.h"', 'int main(void) {']
-    for cname, st in pairs:
-        lines.append('  printf("%s sizeof %%zu\\n", sizeof(%s));' % (cname, cname))
-        for f in st._fields_:
-            cfield = "in" if f[0] == "in_" else f[0]        # `in` is a Python keyword: the mirrors call that field in_
-            lines.append('  printf("%s %s %%zu\\n", offsetof(%s, %s));' % (cname, f[0], cname, cfield))
+    for cname, names in header_structs().items():
+        lines.append('  printf("%s sizeof 0 %%zu\\n", sizeof(%s));' % (cname, cname))
+        lines += ['  printf("%s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (cname, n, cname, n, cname, n)
+                  for n in names]
     lines += ['  return 0;', '}']
-    src = tmp_path / "layout.c"
+    tmp = tmp_path_factory.mktemp("layout")
+    src, exe = tmp / "layout.c", tmp / "layout"
     src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
     subprocess.run([gcc, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
     got = {}
     for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
-        a, b, c = ln.split()
-        got[(a, b)] = int(c)
-    for cname, st in pairs:
-        assert got[(cname, "sizeof")] == C.sizeof(st), cname
-        for f in st._fields_:
-            assert got[(cname, f[0])] == getattr(st, f[0]).offset, (cname, f[0])
+        a, b, off, size = ln.split()
+        got[(a, b)] = (int(off), int(size))
+    return got
+
+
+@pytest.mark.parametrize("cname", list(header_structs()))
+def test_struct_layout_matches_the_header(c_layout, cname):
+    """sizeof, and the offset and the size of every field, of one argument struct as gcc lays out include/nudf.h, against
+    its ctypes mirror in neuraludf_amd/_lib.py (the field-name test above cannot see padding or type widths; the sizes
+    catch a mirror typed int32 where the header says int64_t and padding hides it from the offsets)."""
+    import ctypes as C
+    st, names = mirror_of(cname), header_structs()[cname]
+    assert c_layout[(cname, "sizeof")] == (0, C.sizeof(st))
+    assert names == mirror_fields(st)
+    for n, f in zip(names, st._fields_):
+        field = getattr(st, f[0])
+        assert c_layout[(cname, n)] == (field.offset, field.size), n
 
 
 def test_weight_gradient_gemm_plan_host_logic():

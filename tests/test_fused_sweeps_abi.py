@@ -1,30 +1,11 @@
-"""CPU: the chain descriptor after the step kind that fuses two sweeps into one launch (NUDF_CH_SEED) -- the step limit and the
-enum values of include/nudf.h against the ctypes mirror, the descriptor inside the 4 KB kernel-argument segment, and the
-host-side validation of nudf_mlp_chain refusing the new kind out of place.  The refusal cases pass made-up addresses, which is
-safe only where a descriptor that slipped through could not be launched: they run on machines without a GPU."""
+"""CPU: the host-side validation of nudf_mlp_chain refusing the step kind that fuses two sweeps into one launch
+(NUDF_CH_SEED) out of place.  The refusal cases pass made-up addresses, which is safe only where a descriptor that slipped
+through could not be launched: they run on machines without a GPU.  (The step limit and the enum values of include/nudf.h
+against the ctypes mirror, and the descriptor inside the 4 KB kernel-argument segment: tests/test_abi.py.)"""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_step_limit_and_kinds_match_the_header():
-    from neuraludf_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "nudf.h")).read()
-    assert int(re.search(r"#define NUDF_CH_MAX_STEPS (\d+)", hdr).group(1)) == _lib.CH_MAX_STEPS >= 19
-    for name, val in re.findall(r"NUDF_CH_([A-Z0-9]+) = (\d+)", hdr):
-        if name.startswith("INIT_"):
-            assert _lib.CH_INIT[name[5:]] == int(val), name
-        else:
-            assert _lib.CH[name] == int(val), name
-    assert "SEED" in _lib.CH
-    assert C.sizeof(_lib.Chain) <= 4096          # travels by value in the kernel-argument segment
-    # the library reports the bound it was compiled with (the loader refuses one that differs: the bound sets sizeof(NudfChain))
-    assert _lib.lib().nudf_chain_max_steps() == _lib.CH_MAX_STEPS
 
 
 def _chain(P=128):

@@ -1,8 +1,7 @@
 """CPU checks of the MeshUDF mesher's pieces that need no GPU: the generated marching-cubes table
-(neuraludf_amd/mc_tables.py, committed as csrc/mc_tables.inc), the numpy restatement of the mesher on an analytic grid,
-the PLY writer and the ABI mirror of NudfMeshUDF."""
+(neuraludf_amd/mc_tables.py, committed as csrc/mc_tables.inc), the numpy restatement of the mesher on an analytic grid
+and the PLY writer.  (The ABI mirror of NudfMeshUDF: tests/test_abi.py.)"""
 import collections
-import os
 
 import numpy as np
 import pytest
@@ -12,7 +11,6 @@ from neuraludf_amd import meshing
 
 import meshudf_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = T.tables()
 
 
@@ -93,25 +91,3 @@ def test_write_ply_round_trip(tmp_path):
     np.testing.assert_array_equal(rec["v"], f)
     with pytest.raises(ValueError):
         meshing.write_ply(str(path), v, f + 7)
-
-
-def test_meshudf_struct_layout_matches_the_header(tmp_path):
-    import ctypes as C
-    import shutil
-    import subprocess
-    from neuraludf_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc on this box")
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nudf.h"', 'int main(void) {',
-             '  printf("sizeof %zu\\n", sizeof(NudfMeshUDF));']
-    lines += ['  printf("%s %%zu\\n", offsetof(NudfMeshUDF, %s));' % (f[0], f[0]) for f in _lib.MeshUDF._fields_]
-    lines += ['  return 0;', '}']
-    src = tmp_path / "layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run([gcc, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(got["sizeof"]) == C.sizeof(_lib.MeshUDF)
-    for f in _lib.MeshUDF._fields_:
-        assert int(got[f[0]]) == getattr(_lib.MeshUDF, f[0]).offset, f[0]
