@@ -19,6 +19,7 @@ extern "C" {
 
 /* The ABI version.  Every change to an argument struct, an enum value, a #define or an entry point's signature raises it; a
  * caller that mirrors this header by hand (neuraludf_amd/_lib.py) refuses a library whose nudf_version() differs.
+ *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
  *        NudfIsoSurfaceSparse, NudfMeshOrient, NudfMeshRaster and the two dispatch reports nudf_mlp_chain_plan /
@@ -29,7 +30,7 @@ extern "C" {
  *   105: NudfChain.tile_scale / tile_amax_in / tile_amax_out
  *   104: NudfChain.absmax_out, NudfGemmTNGroup.amax_a / amax_b + prec 4 (struct sizes)
  *   103: NudfChainStep.X3 / ldx3, prec 4 chains, NudfPackFrag.dtype 4 */
-#define NUDF_ABI_VERSION 109
+#define NUDF_ABI_VERSION 110
 int nudf_version(void);
 /* every argument struct of this header, once, in the order of their definitions */
 #define NUDF_ABI_STRUCTS(X) \
@@ -1149,6 +1150,32 @@ typedef struct NudfMeshTopo {
   int32_t W;
   int32_t border;            /* views: 0 for the mask test, 50 for the visual-hull test                              */
   int32_t pad_;
+  /* mesh simplification (nudf_meshsimplify_*, below); `pos`, `faces`, `edges`, `he_edge`, n_faces, n_verts and n_edges
+   * above are read too */
+  int64_t* sp_key;               /* [n_verts] (keys)                                                                 */
+  const int64_t* sp_cluster_key; /* [n_clusters] the unique keys, ascending (place)                                  */
+  const int64_t* sp_vcluster;    /* [n_verts] cluster of each vertex = rank of its key (faces)                       */
+  const int64_t* sp_member_off;  /* [n_clusters + 1] CSR offsets of the member vertices (place)                      */
+  const int64_t* sp_member;      /* [n_verts] the vertices grouped by cluster, ascending inside each (place)         */
+  const int64_t* sp_corner_off;  /* [n_clusters + 1] CSR offsets of the corners (place, sp_placement 0)              */
+  const int64_t* sp_corner;      /* [3 n_faces] the corners 3 f + k grouped by cluster, ascending inside each (place) */
+  const double* sp_attr;         /* [n_verts, sp_attr_width] vertex attributes, or NULL with width 0 (place)         */
+  double* sp_rep;                /* [n_clusters, 3] the representatives (place)                                      */
+  uint8_t* sp_accepted;          /* [n_clusters] 1: the quadric solution was taken, 0: the mean (place)              */
+  double* sp_quadric;            /* [n_clusters, 10] A00 A01 A02 A11 A12 A22 b0 b1 b2 c, or NULL: not stored (place) */
+  double* sp_attr_out;           /* [n_clusters, sp_attr_width] attribute means (place)                              */
+  int64_t* sp_faces;             /* [n_faces, 3] the faces over cluster ids (faces)                                  */
+  int64_t* sp_triple;            /* [n_faces, 3] the same ids in ascending order (faces)                             */
+  uint8_t* sp_degenerate;        /* [n_faces] 1: two corners share a cluster (faces)                                 */
+  int64_t n_clusters;
+  int64_t sp_grid[3];            /* cells per axis, each in [1, 2^20]                                                */
+  double sp_origin[3];           /* the corner of cell (0, 0, 0)                                                     */
+  double sp_cell;                /* edge length of a cell, > 0                                                       */
+  double sp_lambda;              /* place: the regularisation, > 0                                                   */
+  double sp_boundary_weight;     /* place: weight of the boundary planes relative to their faces'; 0: none, and      */
+                                 /* edges / he_edge are not read                                                     */
+  int32_t sp_attr_width;
+  int32_t sp_placement;          /* place: 0 quadric, 1 mean (no corner walk, sp_accepted all 0)                     */
 } NudfMeshTopo;
 int nudf_meshtopo_edges(const NudfMeshTopo* args, void* stream);       /* one thread per unique edge      */
 int nudf_meshtopo_fill_count(const NudfMeshTopo* args, void* stream);  /* one thread per boundary vertex  */
@@ -1159,11 +1186,43 @@ int nudf_meshtopo_cc_jump(const NudfMeshTopo* args, void* stream);     /* one th
 int nudf_meshtopo_views(const NudfMeshTopo* args, void* stream);       /* one thread per vertex           */
 
 /* ------------------------------------------------------------------------------------
+ * Mesh simplification (neuraludf_amd/meshclean.py simplify_mesh, simplify_to_faces): vertex clustering on a uniform grid
+ * with each cluster's representative placed by quadric error minimisation.  The reference has no such step: its users
+ * take the mesher's output, whose triangles are as small as the grid spacing, to trimesh or open3d on the CPU.  The entry
+ * points take NudfMeshTopo and read the sp_ fields at its end.  The caller sorts the keys and the corners' clusters
+ * (stable) and scans between the launches; float64 without contracted multiply-adds, every sum in list order inside one
+ * thread, no atomics: every result is identical from run to run.
+ *   keys    one thread per vertex: c = floor((pos[v] - sp_origin) / sp_cell) per axis and
+ *           sp_key[v] = (cx Gy + cy) Gz + cz in int64 with G = sp_grid; -1 when a coordinate is not finite or c lies
+ *           outside [0, G) (the caller raises).  Clusters are the unique keys in ascending order;
+ *   place   one thread per cluster.  Coordinates are local to the cell's centre, sp_origin + (c + 1/2) sp_cell.  The mean
+ *           is the sum of (pos[v] - centre) over the members in list order divided by their number.  With sp_placement 0
+ *           the quadric (A, b, c) is summed over the cluster's corners in list order: corner (f, k) adds the plane of its
+ *           face -- n = (p1 - p0) x (p2 - p0), u = n / |n|, w = |n| / 2, d = -u . (p0 - centre), the plane adding
+ *           (w u u^T, (w d) u, (w d) d) -- then, with sp_boundary_weight != 0, the boundary plane of half-edge 3 f + k and
+ *           then that of half-edge 3 f + (k + 2) % 3 (the one that ends at the corner), each only when
+ *           edges[he_edge[h]].count is 1: for half-edge j with e = p_{j+1} - p_j and m = e x u, the plane through p_j with
+ *           normal m / |m| and weight sp_boundary_weight * w.  A face whose |n| is 0 or not finite adds nothing, as does a
+ *           boundary plane whose |m| is.  With t = A00 + A11 + A22 > 0, (A + lambda t I) x = -b + lambda t mean is solved
+ *           by a Cholesky factorisation without pivoting (the matrix is positive definite with condition at most
+ *           (1 + lambda) / lambda), and x is taken exactly when the key of centre + x, computed as in `keys`, is the
+ *           cluster's; otherwise, and with sp_placement 1, the mean.  sp_rep[c] = centre + x or centre + mean,
+ *           sp_accepted[c] says which, sp_quadric[c] (when not NULL) holds the ten sums, and sp_attr_out[c] the mean of
+ *           each attribute column over the members in list order;
+ *   faces   one thread per face: sp_faces[f] = the clusters of its corners, sp_degenerate[f] = two of them are equal,
+ *           sp_triple[f] = the three in ascending order.  Of the faces with equal triples the caller keeps the one with the
+ *           smallest index.
+ * ---------------------------------------------------------------------------------- */
+int nudf_meshsimplify_keys(const NudfMeshTopo* args, void* stream);    /* one thread per vertex           */
+int nudf_meshsimplify_place(const NudfMeshTopo* args, void* stream);   /* one thread per cluster          */
+int nudf_meshsimplify_faces(const NudfMeshTopo* args, void* stream);   /* one thread per face             */
+
+/* ------------------------------------------------------------------------------------
  * Consistent face orientation and vertex normals (neuraludf_amd/meshclean.py orient_faces, vertex_normals): the step the
  * reference leaves out after its mesher because trimesh does it with a serial graph traversal ("DO NOT try to
  * consistently align winding directions: too slow and poor results", extract_mesh.py:218-219), and
- * trimesh.geometry.weighted_vertex_normals, which it calls at extract_mesh.py:272-275.  A struct of its own: the layout of
- * NudfMeshTopo is pinned.  Half-edges and keys are NudfMeshTopo's.  A manifold edge is an undirected edge with exactly two
+ * trimesh.geometry.weighted_vertex_normals, which it calls at extract_mesh.py:272-275.  A struct of its own.
+ * Half-edges and keys are NudfMeshTopo's.  A manifold edge is an undirected edge with exactly two
  * half-edges, of two different faces neither of which repeats a vertex; the caller lists them (me_a, me_b) from the sorted
  * keys.  Every face f holds one packed word, parent * 2 + parity, set to 2 f by the caller: parity = 1 says that f and its
  * parent need opposite flips.  One struct; each entry point reads the fields its comment names.
@@ -1213,7 +1272,7 @@ int nudf_meshorient_normals(const NudfMeshOrient* args, void* stream);     /* on
 /* ------------------------------------------------------------------------------------
  * Triangle rasteriser with a depth buffer (neuraludf_amd/meshrender.py rasterize, vertex_visibility, color_vertices): depth,
  * face and barycentric maps of a mesh from the dataset cameras, depth-tested vertex visibility and vertex colours blended
- * from the source images.  A struct of its own: the layouts of NudfMeshTopo and NudfMeshOrient are pinned.  float64 without
+ * from the source images.  A struct of its own.  float64 without
  * contracted multiply-adds, integer atomics only: every result is identical from run to run.  A view is rows 0..2 of a world
  * matrix P, as `proj` of NudfMeshTopo; pixel (x, y) is the sample point with exactly those integer coordinates.  One struct;
  * each entry point reads the fields its comment names.  The caller passes `n_views` views at a time (a chunk of them, with

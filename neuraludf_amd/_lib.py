@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must be loaded before libnudf, see module docstring
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NUDF_LIB") or os.path.join(_HERE, "libnudf.so")      # NUDF_LIB: A/B builds of the library
-ABI_VERSION = 109         # NUDF_ABI_VERSION of the include/nudf.h these ctypes structures mirror
+ABI_VERSION = 110         # NUDF_ABI_VERSION of the include/nudf.h these ctypes structures mirror
 
 c_fp = C.c_void_p
 i32 = C.c_int32
@@ -239,7 +239,13 @@ class MeshTopo(C.Structure):
                 ("new_faces", c_fp), ("pos", c_fp), ("pos_out", c_fp), ("labels", c_fp), ("changed", c_fp), ("proj", c_fp),
                 ("masks", c_fp), ("vis_count", c_fp), ("n_faces", C.c_int64), ("n_verts", C.c_int64), ("n_edges", C.c_int64),
                 ("n_bverts", C.c_int64), ("n_new", C.c_int64), ("lam", C.c_double), ("max_loop", i32), ("n_views", i32),
-                ("H", i32), ("W", i32), ("border", i32), ("pad_", i32)]
+                ("H", i32), ("W", i32), ("border", i32), ("pad_", i32),
+                ("sp_key", c_fp), ("sp_cluster_key", c_fp), ("sp_vcluster", c_fp), ("sp_member_off", c_fp),
+                ("sp_member", c_fp), ("sp_corner_off", c_fp), ("sp_corner", c_fp), ("sp_attr", c_fp), ("sp_rep", c_fp),
+                ("sp_accepted", c_fp), ("sp_quadric", c_fp), ("sp_attr_out", c_fp), ("sp_faces", c_fp),
+                ("sp_triple", c_fp), ("sp_degenerate", c_fp), ("n_clusters", C.c_int64), ("sp_grid", C.c_int64 * 3),
+                ("sp_origin", C.c_double * 3), ("sp_cell", C.c_double), ("sp_lambda", C.c_double),
+                ("sp_boundary_weight", C.c_double), ("sp_attr_width", i32), ("sp_placement", i32)]
 
 
 class MeshOrient(C.Structure):
@@ -346,7 +352,8 @@ SIGNATURES = {
                             "isosurface_sparse_vertices")),
         (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest")),
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
-                    "meshtopo_cc_jump", "meshtopo_views")),
+                    "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
+                    "meshsimplify_faces")),
         (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals")),
         (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",
                       "meshraster_resolve", "meshraster_visible", "meshraster_colour")),

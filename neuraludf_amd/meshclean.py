@@ -8,6 +8,8 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
     orientation  orient_faces        consistent winding per component (csrc/meshorient.hip); the reference leaves it out
                                      (extract_mesh.py:218-219: trimesh's serial traversal is "too slow")
     normals      vertex_normals      extract_mesh.py:272-275 (trimesh weighted_vertex_normals, angle-weighted)
+    simplify     simplify_mesh, simplify_to_faces     vertex clustering with quadric placement (csrc/meshsimplify.hip);
+                                     the reference's users take this step to trimesh or open3d on the CPU
     views        clean_by_views, clean_dtu_mesh         clean_dtu_mesh.py:36-154 (mask and visual-hull cleaning)
     masks        ellipse_footprint, dilate_masks, load_dtu_views
 
@@ -43,6 +45,8 @@ from ._lib import call, ptr
 MAX_VERTS = 1 << 31          # half-edge keys are min * V + max in int64
 HULL_BORDER = 50             # clean_dtu_mesh.py:88
 HULL_MAX_OUTSIDE = 5         # clean_dtu_mesh.py:105
+SIMPLIFY_MAX_GRID = 1 << 20  # cells per axis: a cluster key (cx Gy + cy) Gz + cz stays below 2^60
+SIMPLIFY_BISECT_ROUNDS = 24
 
 
 class EdgeTable(NamedTuple):
@@ -403,6 +407,288 @@ def filter_components(verts, faces, min_faces=500, keep_largest=False):
     else:
         mask = size[labels] >= int(min_faces)
     return compact_mesh(verts, faces, face_mask=mask)
+
+
+class Simplified(NamedTuple):
+    """verts [V', 3] in the input's dtype; faces [F', 3] int64 into them; vertex_cluster [V] int64: the output vertex of
+    each input vertex, -1 where its cluster was dropped; face_src [F'] int64: the input face of each output face,
+    ascending; accepted [V'] bool: the vertex is the quadric's minimiser (otherwise its cluster's mean); attributes
+    [V', k] in their input's dtype, or None"""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    vertex_cluster: torch.Tensor
+    face_src: torch.Tensor
+    accepted: torch.Tensor
+    attributes: torch.Tensor | None
+
+
+def _three_finite(x, name):
+    try:
+        o = [float(t) for t in x]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be three finite numbers (got {x!r})") from None
+    if len(o) != 3 or not all(math.isfinite(t) for t in o):
+        raise ValueError(f"{name} must be three finite numbers (got {x!r})")
+    return o
+
+
+def _simplify_grid(pos, cell, origin):
+    """`cell` and `origin` against the vertices -> (cell, origin [3], cells per axis [3]); one read-back of the bounds"""
+    try:
+        cell = float(cell)
+    except (TypeError, ValueError):
+        raise ValueError(f"cell must be a positive finite number (got {cell!r})") from None
+    if not (cell > 0 and math.isfinite(cell)):
+        raise ValueError(f"cell must be a positive finite number (got {cell!r})")
+    lo, hi = torch.stack(torch.aminmax(pos, dim=0)).tolist()
+    if not all(math.isfinite(x) for x in lo + hi):
+        raise ValueError("a vertex is not finite")
+    if origin is None:
+        origin = lo
+    else:
+        origin = _three_finite(origin.tolist() if isinstance(origin, torch.Tensor) else origin, "origin")
+        if any(o > m for o, m in zip(origin, lo)):
+            raise ValueError(f"origin {origin} lies above the vertices' minimum {lo}")
+    grid = []
+    for o, m in zip(origin, hi):
+        q = (m - o) / cell                                   # floor is monotone: the largest vertex has the largest cell
+        if not q < SIMPLIFY_MAX_GRID:
+            raise ValueError(f"cell {cell} gives more than 2^20 cells along an axis (extent {m - o})")
+        grid.append(int(math.floor(q)) + 1)
+    return cell, origin, grid
+
+
+def _simplify_desc(pos, faces, cell, origin, grid):
+    d = _topo(faces, pos.shape[0])
+    d.pos, d.sp_cell = ptr(pos), cell
+    for x in range(3):
+        d.sp_origin[x], d.sp_grid[x] = origin[x], grid[x]
+    return d
+
+
+def _stage(events, state, name):
+    """ends the open stage and starts `name` (None: ends the last one); nothing without an event dict"""
+    if events is None:
+        return
+    if "open" in state:
+        events[state["open"]][1].record()
+    if name is not None:
+        events[name] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        events[name][0].record()
+        state["open"] = name
+    else:
+        state.pop("open", None)
+
+
+def _vertex_clusters(d, n_verts, dev, events=None, state=None):
+    """rules 1 and 2 for the vertices -> (cluster_key [C] ascending, vcluster [V], member [V]: the vertices by cluster,
+    ascending inside each, member_off [C + 1]).  d keeps pointers into the four: the caller holds them."""
+    keys = torch.empty(n_verts, dtype=torch.int64, device=dev)
+    d.sp_key = ptr(keys)
+    _stage(events, state, "keys")
+    call("nudf_meshsimplify_keys", d)
+    _stage(events, state, "sorts")
+    skey, member = torch.sort(keys, stable=True)
+    if int(skey[0]) < 0:
+        raise ValueError("a vertex is not finite or lies outside the grid")
+    first = torch.ones(n_verts, dtype=torch.bool, device=dev)
+    first[1:] = skey[1:] != skey[:-1]
+    start = torch.nonzero(first).reshape(-1)
+    vcluster = torch.empty(n_verts, dtype=torch.int64, device=dev)
+    vcluster[member] = torch.cumsum(first, 0) - 1
+    member_off = torch.cat([start, torch.full((1,), n_verts, dtype=torch.int64, device=dev)])
+    return skey[start].contiguous(), vcluster, member.contiguous(), member_off
+
+
+def _surviving_faces(d, faces, vcluster, n_clusters, events=None, state=None):
+    """rule 5 up to the compaction -> (the surviving faces over cluster ids, their source indices ascending)"""
+    n, dev = faces.shape[0], faces.device
+    out = torch.empty((n, 3), dtype=torch.int64, device=dev)
+    triple = torch.empty((n, 3), dtype=torch.int64, device=dev)
+    degenerate = torch.empty(n, dtype=torch.uint8, device=dev)
+    d.sp_vcluster, d.sp_faces, d.sp_triple, d.sp_degenerate = ptr(vcluster), ptr(out), ptr(triple), ptr(degenerate)
+    d.n_clusters = n_clusters
+    _stage(events, state, "faces")
+    call("nudf_meshsimplify_faces", d)
+    _stage(events, state, "dedupe")
+    src = torch.nonzero(degenerate == 0).reshape(-1)
+    t = triple[src]
+    # by (a, b, c), equal triples by source index: two stable sorts, the less significant key first (a C + b < 2^62)
+    order = torch.sort(t[:, 2], stable=True).indices
+    order = order[torch.sort((t[:, 0] * n_clusters + t[:, 1])[order], stable=True).indices]
+    ts = t[order]
+    first = torch.ones(order.numel(), dtype=torch.bool, device=dev)
+    first[1:] = (ts[1:] != ts[:-1]).any(1)
+    keep = torch.sort(src[order[first]]).values
+    return out[keep], keep
+
+
+def _check_attributes(attributes, verts):
+    if attributes is None:
+        return None
+    if not isinstance(attributes, torch.Tensor) or not attributes.is_floating_point():
+        raise ValueError("attributes must be a floating-point torch tensor")
+    if attributes.dim() != 2 or attributes.shape[0] != verts.shape[0]:
+        raise ValueError(f"attributes must be [{verts.shape[0]}, k] (got {tuple(attributes.shape)})")
+    if attributes.device != verts.device:
+        raise ValueError(f"attributes must be on the vertices' GPU (got {attributes.device})")
+    return attributes
+
+
+def simplify_mesh(verts, faces, cell, origin=None, boundary_weight=1.0, regularisation=1e-3, placement="quadric",
+                  attributes=None, _info=None):
+    """vertex clustering on a uniform grid of edge `cell`, each cluster's vertex placed by quadric error minimisation
+    (csrc/meshsimplify.hip) -> Simplified(verts, faces, vertex_cluster, face_src, accepted, attributes).
+    1. Keys: c = floor((p - origin) / cell) per axis in float64, key = (cx Gy + cy) Gz + cz with G = max c + 1 <= 2^20 per
+       axis.  `origin` defaults to the vertices' minimum; a given one must not lie above it.  A flat part of the mesh that
+       lies exactly at the minimum sits on a cell wall, where the accept test of step 4 hangs on the last bit: an origin a
+       fraction of a cell lower avoids that.
+    2. Clusters are the unique keys in ascending order, with their vertices and their corners 3 f + k in ascending order.
+    3. Quadric of a cluster, local to its cell's centre origin + (c + 1/2) cell, summed over its corners in that order in
+       float64: corner (f, k) adds the plane of f with weight |n| / 2 (n = (p1 - p0) x (p2 - p0); a face of zero or
+       non-finite |n| adds nothing, a face with two corners in the cluster adds twice) and, for the half-edge that starts
+       at the corner and for the one that ends there, when it is a boundary half-edge (its edge has one face in the
+       EdgeTable), the plane through the edge that stands on the face, with boundary_weight times the face's weight.
+       Without them an open surface shrinks at its border; boundary_weight = 0 leaves them out.
+    4. Placement: with t = tr(A) > 0, x solves (A + lambda t I) x = -b + lambda t mean (lambda = regularisation, mean = that
+       of the cluster's vertices; a 3 x 3 Cholesky factorisation, the condition is at most (1 + lambda) / lambda) and is
+       taken exactly when centre + x has the cluster's key; otherwise, and always with placement="mean", the vertex is
+       the mean.  Every output vertex lies in its cluster's cell.
+    5. Faces: corners become cluster ids; a face that repeats an id goes; of the faces with the same three ids, whatever
+       the winding, the one with the smallest index stays; survivors keep their order and corner order; clusters that no
+       face uses are dropped.
+    6. `attributes` [V, k] (colours, normals): the mean over each cluster's vertices, float64 inside.
+    Unlike open3d's simplify_vertex_clustering (quadric mode): boundary quadrics, a regularised solve in place of a
+    pseudo-inverse, and a solution outside its cell is refused.  Stable sorts and scans in torch between three launches,
+    sums in list order without atomics: identical from run to run.  (`_info`: a dict that receives clusters, grid, origin,
+    cell, fallbacks and quadric [V', 10] = A00 A01 A02 A11 A12 A22 b0 b1 b2 c of each output vertex; when it holds a dict
+    under "events", that receives a pair of events per stage.)"""
+    if placement not in ("quadric", "mean"):
+        raise ValueError(f"placement must be 'quadric' or 'mean' (got {placement!r})")
+    try:
+        boundary_weight, regularisation = float(boundary_weight), float(regularisation)
+    except (TypeError, ValueError):
+        raise ValueError("boundary_weight and regularisation must be numbers") from None
+    if not (boundary_weight >= 0 and math.isfinite(boundary_weight)):
+        raise ValueError(f"boundary_weight must be >= 0 and finite (got {boundary_weight})")
+    if not (regularisation > 0 and math.isfinite(regularisation)):
+        raise ValueError(f"regularisation must be > 0 and finite (got {regularisation})")
+    verts, faces = _check_mesh(verts, faces)
+    attributes = _check_attributes(attributes, verts)
+    n_verts, n_faces, dev = verts.shape[0], faces.shape[0], verts.device
+    if n_verts == 0 or n_faces == 0:
+        try:
+            cell = float(cell)
+        except (TypeError, ValueError):
+            cell = math.nan
+        if not (cell > 0 and math.isfinite(cell)):
+            raise ValueError(f"cell must be a positive finite number (got {cell!r})")
+        if _info is not None:
+            _info.update(clusters=0, grid=[0, 0, 0], origin=None, cell=cell, fallbacks=0,
+                         quadric=torch.zeros((0, 10), dtype=torch.float64, device=dev))
+        return Simplified(verts[:0], faces[:0], torch.full((n_verts,), -1, dtype=torch.int64, device=dev),
+                          torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.bool, device=dev),
+                          None if attributes is None else attributes[:0])
+    events, state = None if _info is None else _info.get("events"), {}
+    pos = verts.double().contiguous()
+    cell, origin, grid = _simplify_grid(pos, cell, origin)
+    d = _simplify_desc(pos, faces, cell, origin, grid)
+    cluster_key, vcluster, member, member_off = _vertex_clusters(d, n_verts, dev, events, state)
+    n_clusters = cluster_key.numel()
+    d.n_clusters = n_clusters
+    quadric_rule = placement == "quadric"
+    table = corner = corner_off = None
+    if quadric_rule:
+        ckey = vcluster[faces.reshape(-1)]
+        corner = torch.sort(ckey, stable=True).indices                   # corners 3 f + k by cluster, ascending inside
+        corner_off = torch.zeros(n_clusters + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(ckey, minlength=n_clusters), 0, out=corner_off[1:])
+        del ckey
+        if boundary_weight != 0:
+            table = _mesh_edges(faces, n_verts)
+            d.edges, d.he_edge, d.n_edges = ptr(table.edges), ptr(table.he_edge), table.edges.shape[0]
+    _stage(events, state, "place")
+    rep = torch.empty((n_clusters, 3), dtype=torch.float64, device=dev)
+    accepted = torch.empty(n_clusters, dtype=torch.uint8, device=dev)
+    quadric = torch.zeros((n_clusters, 10), dtype=torch.float64, device=dev) if _info is not None else None
+    attr = attr_out = None
+    if attributes is not None and attributes.shape[1]:
+        attr = attributes.double().contiguous()
+        attr_out = torch.empty((n_clusters, attr.shape[1]), dtype=torch.float64, device=dev)
+        d.sp_attr, d.sp_attr_out, d.sp_attr_width = ptr(attr), ptr(attr_out), attr.shape[1]
+    d.sp_cluster_key, d.sp_member_off, d.sp_member = ptr(cluster_key), ptr(member_off), ptr(member)
+    d.sp_corner_off, d.sp_corner = ptr(corner_off), ptr(corner)
+    d.sp_rep, d.sp_accepted, d.sp_quadric = ptr(rep), ptr(accepted), ptr(quadric)
+    d.sp_lambda, d.sp_boundary_weight, d.sp_placement = regularisation, boundary_weight, 0 if quadric_rule else 1
+    call("nudf_meshsimplify_place", d)
+    new_faces, face_src = _surviving_faces(d, faces, vcluster, n_clusters, events, state)
+    _stage(events, state, "compact")
+    kept, out_faces = compact_mesh(torch.arange(n_clusters, dtype=torch.int64, device=dev), new_faces)
+    remap = torch.full((n_clusters,), -1, dtype=torch.int64, device=dev)
+    remap[kept] = torch.arange(kept.numel(), dtype=torch.int64, device=dev)
+    out_attr = None
+    if attributes is not None:
+        out_attr = attributes.new_zeros((kept.numel(), 0)) if attr_out is None else attr_out[kept].to(attributes.dtype)
+    out = Simplified(rep[kept].to(verts.dtype), out_faces, remap[vcluster], face_src, accepted[kept].bool(), out_attr)
+    _stage(events, state, None)
+    if _info is not None:
+        _info.update(clusters=n_clusters, grid=grid, origin=origin, cell=cell, quadric=quadric[kept],
+                     fallbacks=int((~out.accepted).sum()) if quadric_rule else 0)
+    return out
+
+
+def _count_faces(pos, faces, cell, origin):
+    """the number of faces simplify_mesh would leave with this cell: keys, unique, remap, dedupe; no quadrics"""
+    cell, origin, grid = _simplify_grid(pos, cell, origin)
+    d = _simplify_desc(pos, faces, cell, origin, grid)
+    cluster_key, vcluster, _, _ = _vertex_clusters(d, pos.shape[0], pos.device)
+    return _surviving_faces(d, faces, vcluster, cluster_key.numel())[1].numel()
+
+
+def simplify_to_faces(verts, faces, target_faces, **kw):
+    """simplify_mesh with the finest grid a bisection finds that leaves at most `target_faces` faces -> Simplified.  The
+    grid has n cells along the longest side of the bounding box (cell = side / n, a hair more so that the largest vertex
+    does not open a cell of its own) and starts at the box's minimum; n is bisected over [1, min(2^20 - 1, V)] in at most
+    24 rounds, each a count-only pass (keys, unique, remap, dedupe).  The result is guaranteed to have at most
+    target_faces faces; it is not guaranteed to be the largest such result, because the count is not strictly monotone in
+    n.  With target_faces >= F the input comes back unchanged (accepted all False).  Further arguments go to
+    simplify_mesh (`cell` and `origin` are the search's own)."""
+    if "cell" in kw or "origin" in kw:
+        raise ValueError("simplify_to_faces chooses cell and origin itself")
+    try:
+        target = int(target_faces)
+    except (TypeError, ValueError):
+        raise ValueError(f"target_faces must be an integer >= 0 (got {target_faces!r})") from None
+    if target < 0 or target != target_faces:
+        raise ValueError(f"target_faces must be an integer >= 0 (got {target_faces!r})")
+    verts, faces = _check_mesh(verts, faces)
+    attributes = _check_attributes(kw.get("attributes"), verts)
+    n_verts, n_faces, dev = verts.shape[0], faces.shape[0], verts.device
+    if n_faces == 0 or n_verts == 0:
+        return simplify_mesh(verts, faces, 1.0, **kw)
+    if n_faces <= target:
+        return Simplified(verts, faces, torch.arange(n_verts, dtype=torch.int64, device=dev),
+                          torch.arange(n_faces, dtype=torch.int64, device=dev),
+                          torch.zeros(n_verts, dtype=torch.bool, device=dev), attributes)
+    pos = verts.double().contiguous()
+    lo, hi = torch.stack(torch.aminmax(pos, dim=0)).tolist()
+    if not all(math.isfinite(x) for x in lo + hi):
+        raise ValueError("a vertex is not finite")
+    side = max(h - l for l, h in zip(lo, hi))
+    side = side if side > 0 else 1.0
+
+    def cell_of(n):
+        return side / n * (1.0 + 1e-9)
+    n_lo, n_hi = 1, min(SIMPLIFY_MAX_GRID - 1, max(1, n_verts))
+    for _ in range(SIMPLIFY_BISECT_ROUNDS):
+        if n_lo >= n_hi:
+            break
+        mid = (n_lo + n_hi + 1) // 2
+        if _count_faces(pos, faces, cell_of(mid), lo) <= target:
+            n_lo = mid
+        else:
+            n_hi = mid - 1
+    return simplify_mesh(verts, faces, cell_of(n_lo), origin=lo, **kw)
 
 
 def ellipse_footprint(ksize):
