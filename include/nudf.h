@@ -19,6 +19,8 @@ extern "C" {
 
 /* The ABI version.  Every change to an argument struct, an enum value, a #define or an entry point's signature raises it; a
  * caller that mirrors this header by hand (neuraludf_amd/_lib.py) refuses a library whose nudf_version() differs.
+ *   111: nudf_pc_tribin_count / nudf_pc_tribin_emit / nudf_pc_closest (point-to-mesh distance); NudfPointCloud grows by the
+ *        md_ fields, appended at its end
  *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
@@ -30,7 +32,7 @@ extern "C" {
  *   105: NudfChain.tile_scale / tile_amax_in / tile_amax_out
  *   104: NudfChain.absmax_out, NudfGemmTNGroup.amax_a / amax_b + prec 4 (struct sizes)
  *   103: NudfChainStep.X3 / ldx3, prec 4 chains, NudfPackFrag.dtype 4 */
-#define NUDF_ABI_VERSION 110
+#define NUDF_ABI_VERSION 111
 int nudf_version(void);
 /* every argument struct of this header, once, in the order of their definitions */
 #define NUDF_ABI_STRUCTS(X) \
@@ -1083,7 +1085,16 @@ typedef struct NudfPointCloud {
   double box_lo[3];
   double box_hi[3];
   double* dist;              /* [n_query] float64 sqrt(((dx dx) + (dy dy)) + (dz dz))                               */
-  int64_t* idx;              /* [n_query]                                                                            */
+  int64_t* idx;              /* [n_query] nearest: the rank of the nearest point; closest: the face                  */
+  /* point-to-mesh distance (ABI 111, appended): tribin_count / tribin_emit / closest                                 */
+  int64_t* md_ref_n;         /* [n_faces] cells touched by each face's box (written by tribin_count, read by emit)   */
+  const int64_t* md_ref_off; /* [n_faces] exclusive prefix sum of md_ref_n (tribin_emit)                             */
+  int64_t* md_ref_key;       /* [md_n_refs] packed cell of each (cell, face) reference (tribin_emit)                 */
+  int64_t* md_ref_face;      /* [md_n_refs] its face (tribin_emit)                                                   */
+  int64_t md_n_refs;
+  const int64_t* md_cell_face; /* [md_n_refs] the faces by cell: md_ref_face sorted by md_ref_key, stable (closest) */
+  double* md_point;          /* [n_query, 3] the closest point (closest)                                             */
+  double* md_bary;           /* [n_query, 3] its barycentric weights at the face's corner order (closest)            */
 } NudfPointCloud;
 int nudf_pc_tri_count(const NudfPointCloud* args, void* stream);   /* one thread per face  */
 int nudf_pc_tri_emit(const NudfPointCloud* args, void* stream);    /* one thread per face  */
@@ -1091,6 +1102,28 @@ int nudf_pc_keys(const NudfPointCloud* args, void* stream);        /* one thread
 int nudf_pc_cells(const NudfPointCloud* args, void* stream);       /* one thread per occupied cell */
 int nudf_pc_thin_round(const NudfPointCloud* args, void* stream);  /* one thread per point */
 int nudf_pc_nearest(const NudfPointCloud* args, void* stream);     /* one thread per query */
+
+/* ------------------------------------------------------------------------------------
+ * Exact point-to-mesh distance (neuraludf_amd/evaluation.py MeshIndex, closest_on_mesh, mesh_deviation): replaces
+ * trimesh.proximity.closest_point, which the reference's users leave the GPU for, and the approximation by a KD-tree on
+ * surface samples (sample_mesh + nearest).  The same struct, cell key, hash and ring search as above, over faces binned
+ * by their axis-aligned boxes; float64 without contraction, equal to tests/meshdist_ref.py bit for bit.
+ *   tribin_count  one thread per face: md_ref_n[f] = the cells of the grid (origin, cell, grid) that the box of face f
+ *                 touches, lower corner to upper corner inclusive; 0 for a face with an index outside [0, n_verts) or a
+ *                 non-finite coordinate; cap + 1 when more than cap (cap <= 2^40);
+ *   tribin_emit   one thread per face: (md_ref_key, md_ref_face)[md_ref_off[f] ...] = (packed cell, f), x outermost.  The
+ *                 caller sorts the pairs by key (stable), builds cell_key / cell_start / cell_count over the sorted keys
+ *                 and the hash with nudf_pc_cells, and passes the sorted faces as md_cell_face;
+ *   closest       one thread per query (cell-sorted for coherence): the closest point of the mesh over the interior and
+ *                 the three edges of every face, the smallest (squared distance, face) pair: dist / idx / md_point /
+ *                 md_bary [query_idx[t]]; +inf / -1 / NaN / NaN beyond bound.  box_lo / box_hi bound the vertices of the
+ *                 binned faces.
+ * Host-side refusals (no launch): NULL buffers, cell <= 0 or not finite, a grid axis outside [1, 2^21], n_faces, n_verts
+ * or n_query >= 2^31, cap outside [0, 2^40], bound <= 0 (closest).  Empty descriptors return 0.
+ * ---------------------------------------------------------------------------------- */
+int nudf_pc_tribin_count(const NudfPointCloud* args, void* stream);  /* one thread per face  */
+int nudf_pc_tribin_emit(const NudfPointCloud* args, void* stream);   /* one thread per face  */
+int nudf_pc_closest(const NudfPointCloud* args, void* stream);       /* one thread per query */
 
 /* ------------------------------------------------------------------------------------
  * Mesh topology for the mesh clean-up (neuraludf_amd/meshclean.py): replaces what the reference does with trimesh,

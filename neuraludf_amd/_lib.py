@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must be loaded before libnudf, see module docstring
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NUDF_LIB") or os.path.join(_HERE, "libnudf.so")      # NUDF_LIB: A/B builds of the library
-ABI_VERSION = 110         # NUDF_ABI_VERSION of the include/nudf.h these ctypes structures mirror
+ABI_VERSION = 111         # NUDF_ABI_VERSION of the include/nudf.h these ctypes structures mirror
 
 c_fp = C.c_void_p
 i32 = C.c_int32
@@ -230,7 +230,9 @@ class PointCloud(C.Structure):
                 ("rank", c_fp), ("state", c_fp), ("undecided", c_fp), ("r2", C.c_double),
                 ("query", c_fp), ("query_idx", c_fp), ("n_query", C.c_int64), ("bound", C.c_double),
                 ("box_bound2", C.c_double), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
-                ("dist", c_fp), ("idx", c_fp)]
+                ("dist", c_fp), ("idx", c_fp),
+                ("md_ref_n", c_fp), ("md_ref_off", c_fp), ("md_ref_key", c_fp), ("md_ref_face", c_fp),
+                ("md_n_refs", C.c_int64), ("md_cell_face", c_fp), ("md_point", c_fp), ("md_bary", c_fp)]
 
 
 class MeshTopo(C.Structure):
@@ -350,7 +352,8 @@ SIGNATURES = {
         (IsoSurface, ("isosurface_classify", "isosurface_emit", "isosurface_vertices")),
         (IsoSurfaceSparse, ("isosurface_sparse_classify", "isosurface_sparse_edges", "isosurface_sparse_emit",
                             "isosurface_sparse_vertices")),
-        (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest")),
+        (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest",
+                      "pc_tribin_count", "pc_tribin_emit", "pc_closest")),
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces")),

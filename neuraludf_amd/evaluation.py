@@ -11,6 +11,11 @@ their open3d file I/O, Python down-sampling loop and sklearn KD-trees replaced.
     distances   nearest             exact float64 nearest neighbours (kneighbors, n_neighbors=1) by rings of hashed cells
     metrics     chamfer_dtu, chamfer_deepfashion    means below max_dist, precision / recall / F-score, the log file
     files       read_ply / write_points_ply (neuraludf_amd.meshing), load_dtu_obs
+    surfaces    MeshIndex, closest_on_mesh, mesh_deviation    the exact distance from points to a triangle mesh and the
+                                    two-sided deviation between two meshes (csrc/meshdist.hip): the faces binned by their
+                                    boxes into the same hashed cells, the same ring search over them; what
+                                    trimesh.proximity.closest_point answers on the CPU.  Not part of the two protocols,
+                                    which define sampling and stay as they are
 
 Given the permutation, every step is the reference's float64 computation in its operation order, so the points, the
 masks and the distances equal a numpy restatement bit for bit (tests/pointcloud_ref.py); only the means are summed in
@@ -24,6 +29,7 @@ Non-finite points raise ValueError before thinning or a nearest-neighbour search
     python -m neuraludf_amd.evaluation {dtu,deepfashion} --data X.ply --gt Y.ply [--mode mesh|pcd]
         [--dataset_dir D --scan N] [--downsample_density ...] [--patch_size ...] [--max_dist ...]
         [--visualize_threshold ...] [--vis_out_dir ...] [--no_vis] [--log ...] [--seed 0]
+    python -m neuraludf_amd.evaluation deviation --a A.ply --b B.ply [--density D] [--bound B] [--log FILE]
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ import argparse
 import math
 import os
 import sys
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -42,6 +49,9 @@ MAX_POINTS = 1 << 28            # largest sampled cloud accepted (24 B per point
 AXIS_CELLS = 1 << 21            # cells per axis of the packed cell key
 THIN_CELL_SLACK = 1.0 + 2.0 ** -19   # thinning cell / radius: the 27-cell window survives the rounding of cell coordinates
 NEAREST_POINTS_PER_CELL = 16    # target points per occupied cell of the nearest-neighbour index (measured: DESIGN.md §4.9)
+MESH_CELL_FACTOR = 3.0          # MeshIndex: default cell / mean longest box side of the faces (measured: DESIGN.md §4.15)
+MAX_MESH_REFS = 1 << 27         # MeshIndex: most (cell, face) references accepted by default (16 B each, and the sort's copy)
+MAX_MESH_REFS_LIMIT = 1 << 40   # the kernels' cap (csrc/meshdist.hip MD_MAX_CAP)
 KEEP = 1
 
 PROTOCOLS = {
@@ -292,6 +302,225 @@ def nearest(query, ref, bound=math.inf, *, cell=None, _events=None):
     return dist, idx
 
 
+# ---- exact point-to-mesh distance ------------------------------------------------------------------------------------
+class Closest(NamedTuple):
+    """dist [M] float64; face [M] int64 (-1 beyond bound); point [M, 3] float64: the closest point of the mesh; bary
+    [M, 3] float64: its weights at the corners of `face`, in the face's corner order (NaN beyond bound, as point)"""
+    dist: torch.Tensor
+    face: torch.Tensor
+    point: torch.Tensor
+    bary: torch.Tensor
+
+
+def _check_face_array(faces):
+    f = torch.as_tensor(faces) if not isinstance(faces, torch.Tensor) else faces
+    if f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() or f.is_complex() or f.dtype == torch.bool:
+        raise ValueError(f"faces must be an integer [F, 3] array (got {tuple(f.shape)}, {f.dtype})")
+    return f
+
+
+def _stage(events, name):
+    """closes the open stage of the event dict and opens `name` (None: closes only); nothing without a dict"""
+    if events is None:
+        return
+    last = events.get("_open")
+    if last is not None:
+        events[last][1].record()
+    events["_open"] = name
+    if name is not None:
+        events[name] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        events[name][0].record()
+    else:
+        del events["_open"]
+
+
+class MeshIndex:
+    """the faces of a mesh binned into a uniform grid for closest_on_mesh: every face is listed in each cell its
+    axis-aligned box touches (csrc/meshdist.hip tribin_count / tribin_emit, a torch int64 scan between them), the
+    (cell, face) references sorted by cell (stable: ascending face inside a cell), the occupied-cell table and its hash
+    (nudf_pc_cells).  Build once, query many times.
+
+    vertices [V, 3] (NaN allowed: its faces are absent; +-inf is refused), faces [F, 3] integer indices.  `cell`: the
+    grid's edge; by default MESH_CELL_FACTOR times the mean longest box side of the faces -- a property of the mesh, not
+    of the queries.  Either way the cell doubles until the reference count fits `max_refs`.  ValueError: no face, no
+    usable face (every face has a NaN vertex), an index out of range, infinite vertices, more than max_refs faces.
+    (`_events`: a dict that receives a pair of events per stage: count, scan, emit, sort, cells.)"""
+
+    def __init__(self, vertices, faces, cell=None, max_refs=MAX_MESH_REFS, _events=None):
+        _shape3(vertices, "vertices")
+        f = _check_face_array(faces)
+        dev = _device(vertices, faces)
+        v = _points(vertices, "vertices", dev, finite=False)
+        if bool(torch.isinf(v).any()):
+            raise ValueError("vertices hold infinite coordinates")
+        f = f.to(device=dev, dtype=torch.int64).contiguous()
+        nv, nf = v.shape[0], f.shape[0]
+        if nf == 0:
+            raise ValueError("the mesh has no faces")
+        if int(f.min()) < 0 or int(f.max()) >= nv:
+            raise ValueError(f"face index out of range [0, {nv})")
+        max_refs = int(max_refs)
+        if not 0 < max_refs <= MAX_MESH_REFS_LIMIT:
+            raise ValueError(f"max_refs must lie in [1, 2^40] (got {max_refs})")
+        corners = v[f]                                                          # [F, 3, 3]
+        usable = torch.isfinite(corners).all(2).all(1)
+        n_usable = int(usable.sum())
+        if n_usable == 0:
+            raise ValueError("the mesh has no usable face: every face has a non-finite vertex")
+        if n_usable > max_refs:
+            raise ValueError(f"{n_usable} faces exceed max_refs={max_refs} even with one cell per axis")
+        corners = corners[usable]
+        lo, hi = corners.amin((0, 1)).tolist(), corners.amax((0, 1)).tolist()
+        ext = max(h - l for l, h in zip(lo, hi))
+        if cell is None:
+            cell = MESH_CELL_FACTOR * float((corners.amax(1) - corners.amin(1)).amax(1).mean())
+            if not cell > 0:
+                cell = ext if ext > 0 else 1.0
+        else:
+            cell = _positive(cell, "cell")
+        del corners
+        self.vertices, self.faces, self.lo, self.hi, self.n_usable = v, f, lo, hi, n_usable
+        ref_n = torch.empty(nf, dtype=torch.int64, device=dev)
+        d = _lib.PointCloud(verts=ptr(v), faces=ptr(f), n_verts=nv, n_faces=nf, cap=max_refs, md_ref_n=ptr(ref_n))
+        d.origin[:], d.box_lo[:], d.box_hi[:] = lo, lo, hi
+        while True:
+            self.cell, self.grid = _grid_size(lo, hi, cell)
+            d.cell = self.cell
+            d.grid[:] = self.grid
+            _stage(_events, "count")
+            call("nudf_pc_tribin_count", d)
+            _stage(_events, "scan")
+            ends = torch.cumsum(ref_n, 0)
+            n_refs = int(ends[-1])
+            if n_refs <= max_refs:
+                break
+            if self.cell > ext:                  # one cell holds the mesh: refs = faces <= max_refs, cannot happen
+                raise ValueError(f"{n_refs} references exceed max_refs={max_refs} even with one cell per axis")
+            cell = self.cell * 2.0
+        _stage(_events, "emit")
+        off = (ends - ref_n).contiguous()
+        ref_key = torch.empty(n_refs, dtype=torch.int64, device=dev)
+        ref_face = torch.empty(n_refs, dtype=torch.int64, device=dev)
+        d.md_ref_off, d.md_ref_key, d.md_ref_face, d.md_n_refs = ptr(off), ptr(ref_key), ptr(ref_face), n_refs
+        call("nudf_pc_tribin_emit", d)
+        _stage(_events, "sort")
+        skeys, order = torch.sort(ref_key, stable=True)
+        self.cell_face = ref_face[order].contiguous()
+        _stage(_events, "cells")
+        ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
+        self.cell_key, self.cell_count = ukeys.contiguous(), counts.contiguous()
+        self.cell_start = (torch.cumsum(counts, 0) - counts).contiguous()
+        nc = ukeys.numel()
+        cap = 1 << max(1, (2 * nc - 1).bit_length())
+        self.hash_key = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        self.hash_row = torch.empty(cap, dtype=torch.int64, device=dev)
+        d.cell_key, d.cell_start, d.cell_count, d.n_cells = ptr(self.cell_key), ptr(self.cell_start), ptr(self.cell_count), nc
+        d.hash_key, d.hash_row, d.hash_cap = ptr(self.hash_key), ptr(self.hash_row), cap
+        call("nudf_pc_cells", d)
+        _stage(_events, None)
+        d.md_cell_face = ptr(self.cell_face)
+        d.md_ref_n = d.md_ref_off = d.md_ref_key = d.md_ref_face = None        # the scratch of the build is released
+        self.d, self.n_refs, self.n_cells = d, n_refs, nc
+
+    def keys_of(self, pts):
+        keys = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
+        k = _lib.PointCloud(pts=ptr(pts), n=pts.shape[0], cell=self.cell, keys=ptr(keys))
+        k.origin[:] = self.lo
+        call("nudf_pc_keys", k)
+        return keys
+
+    def closest(self, query, bound=math.inf, _events=None):
+        """closest_on_mesh(query, index=self, bound=bound)  (`_events`: receives the stages query_sort and closest)"""
+        bound = _positive(bound, "bound", allow_inf=True)
+        _shape3(query, "query")
+        dev = self.vertices.device
+        q = _points(query, "query", dev)
+        m = q.shape[0]
+        out = Closest(torch.empty(m, dtype=torch.float64, device=dev), torch.empty(m, dtype=torch.int64, device=dev),
+                      torch.empty((m, 3), dtype=torch.float64, device=dev),
+                      torch.empty((m, 3), dtype=torch.float64, device=dev))
+        if m == 0:
+            return out
+        _stage(_events, "query_sort")
+        qorder = torch.sort(self.keys_of(q), stable=True).indices
+        qs = q[qorder].contiguous()
+        _stage(_events, "closest")
+        d = self.d
+        d.query, d.query_idx, d.n_query, d.bound = ptr(qs), ptr(qorder), m, bound
+        d.box_bound2 = (bound * (1.0 + 1e-9)) ** 2 if math.isfinite(bound) else math.inf
+        d.dist, d.idx, d.md_point, d.md_bary = ptr(out.dist), ptr(out.face), ptr(out.point), ptr(out.bary)
+        call("nudf_pc_closest", d)
+        _stage(_events, None)
+        d.query = d.query_idx = d.dist = d.idx = d.md_point = d.md_bary = None
+        return out
+
+
+def closest_on_mesh(query, vertices=None, faces=None, bound=math.inf, *, index=None, cell=None):
+    """the closest point of a triangle mesh for every point of `query` [M, 3], exactly (what
+    trimesh.proximity.closest_point answers on the CPU) -> Closest(dist, face, point, bary) on the GPU, in the caller's
+    order.  Per face the candidates are the interior (the foot of the perpendicular, when it falls strictly inside) and
+    the three edges, each evaluated from its lower vertex index to its higher, end points taken exactly: a query that is
+    a mesh vertex gets 0.0, two faces sharing an edge agree to the bit, the winding changes nothing.  Across faces the
+    smallest (squared distance, face index) wins, so the result depends neither on the cell size nor on the order of
+    traversal; it equals tests/meshdist_ref.py bit for bit.  Degenerate faces count as their edges; a face with a NaN
+    vertex is absent.  Rows beyond `bound` are +inf / -1 / NaN / NaN.  Non-finite queries raise ValueError; an empty
+    query gives empty outputs.  Pass either (vertices, faces[, cell]) or a MeshIndex built from them as `index`."""
+    if index is None:
+        if vertices is None or faces is None:
+            raise ValueError("closest_on_mesh needs (vertices, faces) or index=MeshIndex(...)")
+        _positive(bound, "bound", allow_inf=True)
+        _shape3(query, "query")
+        index = MeshIndex(vertices, faces, cell=cell)
+    elif vertices is not None or faces is not None or cell is not None:
+        raise ValueError("pass either (vertices, faces[, cell]) or index, not both")
+    elif not isinstance(index, MeshIndex):
+        raise ValueError("index must be a MeshIndex")
+    return index.closest(query, bound)
+
+
+def _as_index(m, name):
+    if isinstance(m, MeshIndex):
+        return m
+    if not isinstance(m, (tuple, list)) or len(m) != 2:
+        raise ValueError(f"{name} must be (vertices, faces) or a MeshIndex")
+    return MeshIndex(m[0], m[1])
+
+
+def _one_sided(src, dst, density, bound):
+    """from the finite vertices of src (with density: sample_mesh's cloud, which begins with them) to the surface of dst"""
+    pts = src.vertices if density is None else sample_mesh(src.vertices, src.faces, density)
+    pts = pts[torch.isfinite(pts).all(1)]
+    n = pts.shape[0]
+    if n == 0:
+        return dict(max=math.nan, mean=math.nan, rms=math.nan, n=0)
+    d = dst.closest(pts, bound).dist
+    return dict(max=float(d.max()), mean=float(d.mean()), rms=float(torch.sqrt((d * d).mean())), n=n)
+
+
+def mesh_deviation(a, b, *, density=None, bound=math.inf):
+    """the two-sided deviation between two meshes, each (vertices, faces) or a MeshIndex: for each direction the exact
+    distances from the vertices of one mesh -- with `density` from sample_mesh's cloud at that density, vertices included
+    -- to the surface of the other.  -> dict(a_to_b=dict(max, mean, rms, n), b_to_a=..., hausdorff=max of the two max).
+    `max` is the largest distance over the measured points: a lower bound of the true one-sided Hausdorff distance,
+    exact at the samples (the surface between them can lie farther away; a finer density tightens it).  NaN vertices
+    are left out; a distance beyond `bound` counts as +inf."""
+    bound = _positive(bound, "bound", allow_inf=True)
+    if density is not None:
+        density = _positive(density, "density")
+    ia, ib = _as_index(a, "a"), _as_index(b, "b")
+    ab, ba = _one_sided(ia, ib, density, bound), _one_sided(ib, ia, density, bound)
+    return dict(a_to_b=ab, b_to_a=ba, hausdorff=max(ab["max"], ba["max"]))
+
+
+def format_deviation(res, decimals=6):
+    """the deviation log, in format_log's style: one line per direction, the symmetric figure, rounded with np.round"""
+    def r(v):
+        return np.round(np.float64(v), decimals)
+    lines = [f"{k} max {r(res[k]['max'])} mean {r(res[k]['mean'])} rms {r(res[k]['rms'])} n {res[k]['n']} \n"
+             for k in ("a_to_b", "b_to_a")]
+    return "".join(lines) + f"hausdorff {r(res['hausdorff'])} \n"
+
+
 # ---- the protocols ---------------------------------------------------------------------------------------------------
 def _data_cloud(data, density, dev):
     if isinstance(data, (tuple, list)):
@@ -488,9 +717,39 @@ def parse_log(text):
     return out
 
 
+def _main_deviation(argv):
+    from .meshing import read_ply
+    ap = argparse.ArgumentParser(prog="python -m neuraludf_amd.evaluation deviation",
+                                 description="two-sided exact deviation between two meshes (mesh_deviation)")
+    ap.add_argument("--a", type=str, required=True, help="first mesh (PLY with faces)")
+    ap.add_argument("--b", type=str, required=True, help="second mesh (PLY with faces)")
+    ap.add_argument("--density", type=float, default=None, help="also measure from sample_mesh's points at this density")
+    ap.add_argument("--bound", type=float, default=math.inf)
+    ap.add_argument("--decimals", type=int, default=6)
+    ap.add_argument("--log", type=str, default=None)
+    a = ap.parse_args(argv)
+    meshes = []
+    for path in (a.a, a.b):
+        v, f = read_ply(path)
+        if f is None:
+            raise SystemExit(f"{path} holds no faces")
+        meshes.append((torch.as_tensor(np.asarray(v, dtype=np.float64)), torch.as_tensor(np.asarray(f))))
+    out = mesh_deviation(meshes[0], meshes[1], density=a.density, bound=a.bound)
+    for k in ("a_to_b", "b_to_a"):
+        print(f"{k}: max: {out[k]['max']}; mean: {out[k]['mean']}; rms: {out[k]['rms']}; n: {out[k]['n']}.")
+    print(f"hausdorff: {out['hausdorff']}")
+    log = a.log if a.log is not None else os.path.join(os.path.dirname(a.a), "deviation_result.txt")
+    with open(log, "w+") as fh:
+        fh.write(format_deviation(out, a.decimals))
+    return 0
+
+
 def main(argv=None):
     from pathlib import Path
     from .meshing import read_ply
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv and argv[0] == "deviation":            # the third protocol word has arguments of its own
+        return _main_deviation(argv[1:])
     ap = argparse.ArgumentParser(prog="python -m neuraludf_amd.evaluation", description=__doc__.split("\n\n")[0])
     ap.add_argument("protocol", choices=sorted(PROTOCOLS))
     ap.add_argument("--data", type=str, default="data_in.ply")

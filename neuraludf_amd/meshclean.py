@@ -10,6 +10,9 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
     normals      vertex_normals      extract_mesh.py:272-275 (trimesh weighted_vertex_normals, angle-weighted)
     simplify     simplify_mesh, simplify_to_faces     vertex clustering with quadric placement (csrc/meshsimplify.hip);
                                      the reference's users take this step to trimesh or open3d on the CPU
+    measure      simplify_to_error, transfer_attributes   simplification to a measured two-sided deviation, attributes
+                                     carried to the closest point of another mesh (evaluation.closest_on_mesh,
+                                     csrc/meshdist.hip; trimesh.proximity.closest_point on the CPU)
     views        clean_by_views, clean_dtu_mesh         clean_dtu_mesh.py:36-154 (mask and visual-hull cleaning)
     masks        ellipse_footprint, dilate_masks, load_dtu_views
 
@@ -536,7 +539,7 @@ def _check_attributes(attributes, verts):
 
 
 def simplify_mesh(verts, faces, cell, origin=None, boundary_weight=1.0, regularisation=1e-3, placement="quadric",
-                  attributes=None, _info=None):
+                  attributes=None, _info=None, measure=False):
     """vertex clustering on a uniform grid of edge `cell`, each cluster's vertex placed by quadric error minimisation
     (csrc/meshsimplify.hip) -> Simplified(verts, faces, vertex_cluster, face_src, accepted, attributes).
     1. Keys: c = floor((p - origin) / cell) per axis in float64, key = (cx Gy + cy) Gz + cz with G = max c + 1 <= 2^20 per
@@ -562,7 +565,10 @@ def simplify_mesh(verts, faces, cell, origin=None, boundary_weight=1.0, regulari
     pseudo-inverse, and a solution outside its cell is refused.  Stable sorts and scans in torch between three launches,
     sums in list order without atomics: identical from run to run.  (`_info`: a dict that receives clusters, grid, origin,
     cell, fallbacks and quadric [V', 10] = A00 A01 A02 A11 A12 A22 b0 b1 b2 c of each output vertex; when it holds a dict
-    under "events", that receives a pair of events per stage.)"""
+    under "events", that receives a pair of events per stage.)
+    With measure=True the result's two-sided deviation from the input is measured (evaluation.mesh_deviation, vertices
+    only) and returned beside it: -> (Simplified, deviation); `_info` receives it too, under "deviation".  Off by
+    default: the result and its cost are then exactly as without the argument."""
     if placement not in ("quadric", "mean"):
         raise ValueError(f"placement must be 'quadric' or 'mean' (got {placement!r})")
     try:
@@ -586,9 +592,12 @@ def simplify_mesh(verts, faces, cell, origin=None, boundary_weight=1.0, regulari
         if _info is not None:
             _info.update(clusters=0, grid=[0, 0, 0], origin=None, cell=cell, fallbacks=0,
                          quadric=torch.zeros((0, 10), dtype=torch.float64, device=dev))
-        return Simplified(verts[:0], faces[:0], torch.full((n_verts,), -1, dtype=torch.int64, device=dev),
-                          torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.bool, device=dev),
-                          None if attributes is None else attributes[:0])
+        out = Simplified(verts[:0], faces[:0], torch.full((n_verts,), -1, dtype=torch.int64, device=dev),
+                         torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.bool, device=dev),
+                         None if attributes is None else attributes[:0])
+        if measure:
+            raise ValueError("measure=True needs a mesh with faces")
+        return out
     events, state = None if _info is None else _info.get("events"), {}
     pos = verts.double().contiguous()
     cell, origin, grid = _simplify_grid(pos, cell, origin)
@@ -634,6 +643,11 @@ def simplify_mesh(verts, faces, cell, origin=None, boundary_weight=1.0, regulari
     if _info is not None:
         _info.update(clusters=n_clusters, grid=grid, origin=origin, cell=cell, quadric=quadric[kept],
                      fallbacks=int((~out.accepted).sum()) if quadric_rule else 0)
+    if measure:
+        deviation = _deviation(pos, faces, out)
+        if _info is not None:
+            _info["deviation"] = deviation
+        return out, deviation
     return out
 
 
@@ -689,6 +703,92 @@ def simplify_to_faces(verts, faces, target_faces, **kw):
         else:
             n_hi = mid - 1
     return simplify_mesh(verts, faces, cell_of(n_lo), origin=lo, **kw)
+
+
+def _deviation(src, src_faces, result):
+    """mesh_deviation(input, result), vertices only; `src`: (vertices, faces) or the input's MeshIndex.  A result without
+    faces is infinitely far"""
+    from . import evaluation                                 # lazily: evaluation imports meshing, which imports this file
+    if result.faces.shape[0] == 0:
+        inf = dict(max=math.inf, mean=math.inf, rms=math.inf, n=0)
+        return dict(a_to_b=inf, b_to_a=dict(inf), hausdorff=math.inf)
+    a = src if isinstance(src, evaluation.MeshIndex) else (src, src_faces)
+    return evaluation.mesh_deviation(a, (result.verts.double(), result.faces))
+
+
+def simplify_to_error(verts, faces, max_error, **kw):
+    """simplify_mesh on the coarsest grid a bisection finds whose measured deviation from the input is at most
+    `max_error` -> (Simplified, deviation).  The deviation is evaluation.mesh_deviation(input, result)["hausdorff"],
+    vertices only: the exact distance from every input vertex to the result's surface and from every result vertex to the
+    input's, the larger of the two maxima (a lower bound of the true Hausdorff distance, exact at the vertices).  The grid
+    has n cells along the longest side of the bounding box, as in simplify_to_faces; n is bisected over
+    [1, min(2^20 - 1, V)] in at most 24 passes, each a full simplification and measurement (the input's MeshIndex is
+    built once, the result's per pass).  The deviation is not monotone in n, so the result meets the bound but need not
+    be the coarsest grid that does.  When no grid tried meets it the input comes back unchanged: vertex_cluster and
+    face_src are arange, accepted is all True, the deviation is 0 in every figure.  Further arguments go to simplify_mesh
+    (`cell`, `origin` and `measure` are the search's own)."""
+    if "cell" in kw or "origin" in kw or "measure" in kw:
+        raise ValueError("simplify_to_error chooses cell and origin itself and always measures")
+    try:
+        max_error = float(max_error)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_error must be a number >= 0 (got {max_error!r})") from None
+    if not max_error >= 0:
+        raise ValueError(f"max_error must be a number >= 0 (got {max_error!r})")
+    from . import evaluation
+    verts, faces = _check_mesh(verts, faces)
+    attributes = _check_attributes(kw.get("attributes"), verts)
+    n_verts, n_faces, dev = verts.shape[0], faces.shape[0], verts.device
+    if n_faces == 0 or n_verts == 0:
+        raise ValueError("simplify_to_error needs a mesh with faces")
+    pos = verts.double().contiguous()
+    lo, hi = torch.stack(torch.aminmax(pos, dim=0)).tolist()
+    if not all(math.isfinite(x) for x in lo + hi):
+        raise ValueError("a vertex is not finite")
+    side = max(h - l for l, h in zip(lo, hi))
+    side = side if side > 0 else 1.0
+    index = evaluation.MeshIndex(pos, faces)
+    best = None
+    n_lo, n_hi = 1, min(SIMPLIFY_MAX_GRID - 1, max(1, n_verts))
+    for _ in range(SIMPLIFY_BISECT_ROUNDS):
+        if n_lo > n_hi:
+            break
+        mid = (n_lo + n_hi) // 2
+        s = simplify_mesh(verts, faces, side / mid * (1.0 + 1e-9), origin=lo, **kw)
+        deviation = _deviation(index, None, s)
+        if deviation["hausdorff"] <= max_error:
+            best, n_hi = (s, deviation), mid - 1                # met: look for a coarser grid
+        else:
+            n_lo = mid + 1
+    if best is not None:
+        return best
+    zero = dict(max=0.0, mean=0.0, rms=0.0, n=n_verts)
+    same = Simplified(verts, faces, torch.arange(n_verts, dtype=torch.int64, device=dev),
+                      torch.arange(n_faces, dtype=torch.int64, device=dev),
+                      torch.ones(n_verts, dtype=torch.bool, device=dev), attributes)
+    return same, dict(a_to_b=zero, b_to_a=dict(zero), hausdorff=0.0)
+
+
+def transfer_attributes(src_verts, src_faces, src_attributes, dst_points, bound=math.inf):
+    """attributes of a mesh at the places of it that lie closest to `dst_points` [M, 3]: for each point the closest
+    point of the source surface (evaluation.closest_on_mesh, exact) and there the barycentric blend
+    (w0 a0 + w1 a1) + w2 a2 of the three attribute rows of its face, in float64 -> [M, k] in the attributes' dtype.
+    src_attributes [V, k] floating point (colours, normals, any per-vertex quantity).  Rows farther than `bound` from the
+    source are NaN.  Carries what simplify_mesh only averages, and after any other edit of the mesh."""
+    from . import evaluation
+    if not isinstance(src_attributes, torch.Tensor) or not src_attributes.is_floating_point() or src_attributes.dim() != 2:
+        raise ValueError("src_attributes must be a floating-point [V, k] torch tensor")
+    index = evaluation.MeshIndex(src_verts, src_faces)
+    if src_attributes.shape[0] != index.vertices.shape[0]:
+        raise ValueError(f"src_attributes must be [{index.vertices.shape[0]}, k] (got {tuple(src_attributes.shape)})")
+    c = index.closest(dst_points, bound)
+    a = src_attributes.to(device=index.vertices.device, dtype=torch.float64)
+    hit = c.face >= 0
+    rows = a[index.faces[c.face.clamp(min=0)]]                                  # [M, 3, k]
+    w = c.bary.unsqueeze(2)
+    out = (w[:, 0] * rows[:, 0] + w[:, 1] * rows[:, 1]) + w[:, 2] * rows[:, 2]
+    out[~hit] = math.nan
+    return out.to(src_attributes.dtype)
 
 
 def ellipse_footprint(ksize):
