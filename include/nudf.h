@@ -20,7 +20,8 @@ extern "C" {
 /* The ABI version.  Every change to an argument struct, an enum value, a #define or an entry point's signature raises it; a
  * caller that mirrors this header by hand (neuraludf_amd/_lib.py) refuses a library whose nudf_version() differs.
  *   111: nudf_pc_tribin_count / nudf_pc_tribin_emit / nudf_pc_closest (point-to-mesh distance); NudfPointCloud grows by the
- *        md_ fields, appended at its end
+ *        md_ fields, appended at its end.  (nudf_pc_raycast and its md_ray_o ... md_count fields were appended later under
+ *        the same number: the size table below refuses a package and a library that disagree on the struct's size)
  *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
@@ -1094,7 +1095,16 @@ typedef struct NudfPointCloud {
   int64_t md_n_refs;
   const int64_t* md_cell_face; /* [md_n_refs] the faces by cell: md_ref_face sorted by md_ref_key, stable (closest) */
   double* md_point;          /* [n_query, 3] the closest point (closest)                                             */
-  double* md_bary;           /* [n_query, 3] its barycentric weights at the face's corner order (closest)            */
+  double* md_bary;           /* [n_query, 3] its barycentric weights at the face's corner order (closest, raycast)   */
+  /* rays against the mesh (appended, the version stays 111: see nudf_pc_raycast below): raycast                      */
+  const double* md_ray_o;    /* [n_query, 3] ray origins (sorted by the cell of entry for coherence)                 */
+  const double* md_ray_d;    /* [n_query, 3] ray directions, need not be unit: t is in units of the direction       */
+  double md_t_min;           /* the window t_min <= t <= t_max of every ray ...                                      */
+  double md_t_max;
+  const double* md_ray_window; /* ... or NULL, or [n_query, 2] a (t_min, t_max) per ray, which then replaces the two */
+  int32_t md_mode;           /* 0 first hit, 1 any hit, 2 count of the faces crossed                                 */
+  int32_t md_pad_;
+  int64_t* md_count;         /* [n_query] any: 0 / 1; count: the faces crossed in the window                         */
 } NudfPointCloud;
 int nudf_pc_tri_count(const NudfPointCloud* args, void* stream);   /* one thread per face  */
 int nudf_pc_tri_emit(const NudfPointCloud* args, void* stream);    /* one thread per face  */
@@ -1124,6 +1134,24 @@ int nudf_pc_nearest(const NudfPointCloud* args, void* stream);     /* one thread
 int nudf_pc_tribin_count(const NudfPointCloud* args, void* stream);  /* one thread per face  */
 int nudf_pc_tribin_emit(const NudfPointCloud* args, void* stream);   /* one thread per face  */
 int nudf_pc_closest(const NudfPointCloud* args, void* stream);       /* one thread per query */
+
+/* ------------------------------------------------------------------------------------
+ * Rays against the mesh (neuraludf_amd/evaluation.py MeshIndex.cast, cast_rays, contains_points, signed_distance): replaces
+ * trimesh.ray's intersects_first / intersects_any / intersects_location and Trimesh.contains.  The index is the one built
+ * for nudf_pc_closest; the struct grew at its end by the md_ray_o ... md_count fields WITHOUT a version step: the version
+ * stays 111, and a package and a library that disagree on the size of NudfPointCloud are refused all the same, by the size
+ * table of nudf_abi_struct that every loader checks after the version.
+ *   raycast       one thread per ray i: walks ray md_ray_o[i] + t md_ray_d[i] through the cells and applies the
+ *                 per-(ray, face) rule of DESIGN.md 4.16 (float64 without contraction, equal to tests/meshray_ref.py bit for
+ *                 bit; independent of the cell size and of the order of traversal).  md_mode 0: dist / idx / md_bary
+ *                 [query_idx[i]] = t, face and barycentric weights of the smallest (t, face) with the three edge functions
+ *                 all >= 0 or all <= 0, +inf / -1 / NaN on a miss; 1: md_count[query_idx[i]] = 1 when such a face exists
+ *                 (early exit), else 0; 2: md_count = the faces crossed, a zero edge function counting as positive in the
+ *                 edge's direction from its lower vertex index to its higher, each face once.
+ * Host-side refusals (no launch): NULL buffers, cell <= 0 or not finite, a grid axis outside [1, 2^21], a bad hash_cap,
+ * n_faces, n_verts or n_query >= 2^31, an unknown md_mode, md_t_min NaN, md_t_max < md_t_min.  Empty descriptors return 0.
+ * ---------------------------------------------------------------------------------- */
+int nudf_pc_raycast(const NudfPointCloud* args, void* stream);       /* one thread per ray   */
 
 /* ------------------------------------------------------------------------------------
  * Mesh topology for the mesh clean-up (neuraludf_amd/meshclean.py): replaces what the reference does with trimesh,

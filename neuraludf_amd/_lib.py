@@ -232,7 +232,9 @@ class PointCloud(C.Structure):
                 ("box_bound2", C.c_double), ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
                 ("dist", c_fp), ("idx", c_fp),
                 ("md_ref_n", c_fp), ("md_ref_off", c_fp), ("md_ref_key", c_fp), ("md_ref_face", c_fp),
-                ("md_n_refs", C.c_int64), ("md_cell_face", c_fp), ("md_point", c_fp), ("md_bary", c_fp)]
+                ("md_n_refs", C.c_int64), ("md_cell_face", c_fp), ("md_point", c_fp), ("md_bary", c_fp),
+                ("md_ray_o", c_fp), ("md_ray_d", c_fp), ("md_t_min", C.c_double), ("md_t_max", C.c_double),
+                ("md_ray_window", c_fp), ("md_mode", i32), ("md_pad_", i32), ("md_count", c_fp)]
 
 
 class MeshTopo(C.Structure):
@@ -353,7 +355,7 @@ SIGNATURES = {
         (IsoSurfaceSparse, ("isosurface_sparse_classify", "isosurface_sparse_edges", "isosurface_sparse_emit",
                             "isosurface_sparse_vertices")),
         (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest",
-                      "pc_tribin_count", "pc_tribin_emit", "pc_closest")),
+                      "pc_tribin_count", "pc_tribin_emit", "pc_closest", "pc_raycast")),
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces")),

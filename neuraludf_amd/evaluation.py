@@ -16,6 +16,10 @@ their open3d file I/O, Python down-sampling loop and sklearn KD-trees replaced.
                                     boxes into the same hashed cells, the same ring search over them; what
                                     trimesh.proximity.closest_point answers on the CPU.  Not part of the two protocols,
                                     which define sampling and stay as they are
+    rays        MeshIndex.cast, cast_rays, contains_points, signed_distance    rays against the same index
+                                    (csrc/meshray.hip): first hit, any hit, the number of faces crossed; inside / outside
+                                    by crossing parity and the signed distance; what trimesh.ray and Trimesh.contains
+                                    answer on the CPU
 
 Given the permutation, every step is the reference's float64 computation in its operation order, so the points, the
 masks and the distances equal a numpy restatement bit for bit (tests/pointcloud_ref.py); only the means are summed in
@@ -52,6 +56,12 @@ NEAREST_POINTS_PER_CELL = 16    # target points per occupied cell of the nearest
 MESH_CELL_FACTOR = 3.0          # MeshIndex: default cell / mean longest box side of the faces (measured: DESIGN.md §4.15)
 MAX_MESH_REFS = 1 << 27         # MeshIndex: most (cell, face) references accepted by default (16 B each, and the sort's copy)
 MAX_MESH_REFS_LIMIT = 1 << 40   # the kernels' cap (csrc/meshdist.hip MD_MAX_CAP)
+RAY_MODES = ("first", "any", "count")    # cast_rays: the values of md_mode (csrc/meshray.hip)
+# contains_points: three fixed directions in general position (no component zero, no two equal in magnitude, pairwise far
+# from parallel), so that a ray meets an edge or a vertex of an axis-aligned or regularly gridded mesh only by accident
+INSIDE_DIRECTIONS = ((0.5370861555295747, 0.2915274230636872, 0.7915368220043530),
+                     (-0.6812409104782753, 0.6469328946524311, 0.3425017306508174),
+                     (0.3129804157290411, -0.8331402637850166, -0.4560219781334682))
 KEEP = 1
 
 PROTOCOLS = {
@@ -303,6 +313,14 @@ def nearest(query, ref, bound=math.inf, *, cell=None, _events=None):
 
 
 # ---- exact point-to-mesh distance ------------------------------------------------------------------------------------
+class RayHits(NamedTuple):
+    """t [N] float64 in units of the direction (+inf on a miss); face [N] int64 (-1 on a miss); bary [N, 3] float64: the
+    weights of the hit at the corners of `face`, in the face's corner order (NaN on a miss)"""
+    t: torch.Tensor
+    face: torch.Tensor
+    bary: torch.Tensor
+
+
 class Closest(NamedTuple):
     """dist [M] float64; face [M] int64 (-1 beyond bound); point [M, 3] float64: the closest point of the mesh; bary
     [M, 3] float64: its weights at the corners of `face`, in the face's corner order (NaN beyond bound, as point)"""
@@ -335,8 +353,8 @@ def _stage(events, name):
 
 
 class MeshIndex:
-    """the faces of a mesh binned into a uniform grid for closest_on_mesh: every face is listed in each cell its
-    axis-aligned box touches (csrc/meshdist.hip tribin_count / tribin_emit, a torch int64 scan between them), the
+    """the faces of a mesh binned into a uniform grid for closest_on_mesh and cast_rays: every face is listed in each cell
+    its axis-aligned box touches (csrc/meshdist.hip tribin_count / tribin_emit, a torch int64 scan between them), the
     (cell, face) references sorted by cell (stable: ascending face inside a cell), the occupied-cell table and its hash
     (nudf_pc_cells).  Build once, query many times.
 
@@ -454,6 +472,52 @@ class MeshIndex:
         d.query = d.query_idx = d.dist = d.idx = d.md_point = d.md_bary = None
         return out
 
+    def cast(self, origins, directions, t_min=0.0, t_max=math.inf, mode="first", _events=None):
+        """rays against the mesh of this index (cast_rays with index=self): `mode` "first" -> RayHits(t, face, bary), "any" ->
+        [N] bool, "count" -> [N] int64, in the caller's order.  t_min / t_max: numbers, or [N] tensors for a window per ray.
+        (`_events`: receives the stages ray_sort and cast.)"""
+        if mode not in RAY_MODES:
+            raise ValueError(f"mode must be one of {RAY_MODES} (got {mode!r})")
+        _shape3(origins, "origins"), _shape3(directions, "directions")
+        dev = self.vertices.device
+        o, d = _rays(origins, directions, dev)
+        n = o.shape[0]
+        t_min, t_max, window = _window(t_min, t_max, n, dev)
+        if mode == "first":
+            out = RayHits(torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+                          torch.empty((n, 3), dtype=torch.float64, device=dev))
+            count = None
+        else:
+            out, count = None, torch.empty(n, dtype=torch.int64, device=dev)
+        if n:
+            _stage(_events, "ray_sort")
+            # coherence only: the cell in which the ray enters the grid's box (the origin's when it starts inside; for a
+            # ray that misses the box, a point of its line clamped into it); the order changes no result
+            lo = torch.tensor(self.lo, dtype=torch.float64, device=dev)
+            hi = torch.tensor(self.hi, dtype=torch.float64, device=dev)
+            inv = 1.0 / torch.where(d == 0, torch.full_like(d, 1e-300), d)
+            ta, tb = (lo - o) * inv, (hi - o) * inv
+            enter = torch.minimum(ta, tb).amax(1).clamp_min(0.0)
+            entry = torch.nan_to_num(o + enter[:, None] * d, nan=0.0, posinf=0.0, neginf=0.0)
+            entry = torch.maximum(torch.minimum(entry, hi), lo).contiguous()
+            order = torch.sort(self.keys_of(entry), stable=True).indices
+            so, sd = o[order].contiguous(), d[order].contiguous()
+            sw = None if window is None else window[order].contiguous()
+            _stage(_events, "cast")
+            r = self.d
+            r.md_ray_o, r.md_ray_d, r.query_idx, r.n_query = ptr(so), ptr(sd), ptr(order), n
+            r.md_t_min, r.md_t_max, r.md_ray_window, r.md_mode = t_min, t_max, ptr(sw), RAY_MODES.index(mode)
+            if mode == "first":
+                r.dist, r.idx, r.md_bary = ptr(out.t), ptr(out.face), ptr(out.bary)
+            else:
+                r.md_count = ptr(count)
+            call("nudf_pc_raycast", r)
+            _stage(_events, None)
+            r.md_ray_o = r.md_ray_d = r.query_idx = r.md_ray_window = r.dist = r.idx = r.md_bary = r.md_count = None
+        if mode == "first":
+            return out
+        return count != 0 if mode == "any" else count
+
 
 def closest_on_mesh(query, vertices=None, faces=None, bound=math.inf, *, index=None, cell=None):
     """the closest point of a triangle mesh for every point of `query` [M, 3], exactly (what
@@ -476,6 +540,96 @@ def closest_on_mesh(query, vertices=None, faces=None, bound=math.inf, *, index=N
     elif not isinstance(index, MeshIndex):
         raise ValueError("index must be a MeshIndex")
     return index.closest(query, bound)
+
+
+# ---- rays against the mesh -------------------------------------------------------------------------------------------
+def _rays(origins, directions, dev):
+    o, d = _points(origins, "origins", dev), _points(directions, "directions", dev)
+    if o.shape != d.shape:
+        raise ValueError(f"origins and directions differ in shape ({tuple(o.shape)}, {tuple(d.shape)})")
+    if d.numel() and not bool((d != 0).any(1).all()):
+        raise ValueError("directions hold a zero vector")
+    return o, d
+
+
+def _window(t_min, t_max, n, dev):
+    """(t_min, t_max, None) for two numbers, (0.0, inf, [n, 2] float64) when either is given per ray"""
+    if not isinstance(t_min, torch.Tensor) and not isinstance(t_max, torch.Tensor):
+        t_min, t_max = float(t_min), float(t_max)
+        if math.isnan(t_min) or not t_max >= t_min:
+            raise ValueError(f"the window needs t_min <= t_max (got {t_min}, {t_max})")
+        return t_min, t_max, None
+    w = torch.empty((n, 2), dtype=torch.float64, device=dev)
+    for k, t in enumerate((t_min, t_max)):
+        t = torch.as_tensor(t, dtype=torch.float64, device=dev)
+        if t.dim() > 1 or (t.dim() == 1 and t.shape[0] != n):
+            raise ValueError(f"a per-ray window must be [N] (got {tuple(t.shape)} for {n} rays)")
+        w[:, k] = t
+    if n and not bool((w[:, 1] >= w[:, 0]).all()):
+        raise ValueError("the window needs t_min <= t_max on every ray (and no NaN)")
+    return 0.0, math.inf, w
+
+
+def cast_rays(origins, directions, vertices=None, faces=None, *, index=None, cell=None, t_min=0.0, t_max=math.inf,
+              mode="first"):
+    """rays origins [N, 3] + t directions [N, 3] against a triangle mesh, exactly (what trimesh.ray answers on the CPU:
+    intersects_first / intersects_any / the length of intersects_location), on the GPU, in the caller's order.  `t` is in
+    units of the direction, which need not be a unit vector; a hit needs t_min <= t <= t_max (numbers, or [N] tensors for
+    a window per ray).
+
+        mode="first"  -> RayHits(t, face, bary): the smallest (t, face index); a miss is +inf / -1 / NaN.  Inclusive at
+                         edges and vertices: a ray through a shared edge or a vertex of a sheet never leaks through.
+        mode="any"    -> [N] bool: some face is hit in the window (the same inclusive rule, early exit).
+        mode="count"  -> [N] int64: the faces crossed in the window.  An edge function that is exactly zero counts as
+                         positive in the edge's direction from its lower vertex index to its higher, so a crossing through
+                         the interior of an edge that two faces share counts once, whatever their windings.  A ray
+                         through a vertex gets a deterministic count that is not guaranteed to be one crossing.
+
+    Per face the test is Woop-Benthin-Wald's (axes permuted so that the largest |d| is z, sheared, each edge function
+    evaluated once from the lower vertex index to the higher) in float64 without contraction: it equals
+    tests/meshray_ref.py bit for bit, and the winding and the corner a face starts at change no bit of t.  The walk
+    through the index is conservative, so the result depends neither on the cell size nor on the order of traversal.  A
+    face with a NaN vertex or a zero determinant is absent.  Non-finite origins and zero or non-finite directions raise
+    ValueError; empty input gives empty output.  Pass either (vertices, faces[, cell]) or a MeshIndex as `index`."""
+    if index is None:
+        if vertices is None or faces is None:
+            raise ValueError("cast_rays needs (vertices, faces) or index=MeshIndex(...)")
+        if mode not in RAY_MODES:
+            raise ValueError(f"mode must be one of {RAY_MODES} (got {mode!r})")
+        _shape3(origins, "origins"), _shape3(directions, "directions")
+        index = MeshIndex(vertices, faces, cell=cell)
+    elif vertices is not None or faces is not None or cell is not None:
+        raise ValueError("pass either (vertices, faces[, cell]) or index, not both")
+    elif not isinstance(index, MeshIndex):
+        raise ValueError("index must be a MeshIndex")
+    return index.cast(origins, directions, t_min, t_max, mode)
+
+
+def contains_points(points, mesh):
+    """[M] bool: which of `points` [M, 3] lie inside the closed mesh `mesh` ((vertices, faces) or a MeshIndex; what
+    trimesh.Trimesh.contains answers): the parity of the faces crossed (cast_rays mode="count") along each of the three
+    fixed generic directions INSIDE_DIRECTIONS, the majority of the three.  Meant for closed meshes (the zero set of an
+    SDF network, extract_iso_mesh), where a generic ray from an inside point crosses the surface an odd number of times;
+    the vote guards against a ray that happens to pass through a vertex.  An open mesh has no inside: the answer is
+    still the majority parity, i.e. whether most of the three rays cross the sheet an odd number of times -- behind a
+    single open sheet as seen along those directions, not enclosed by it."""
+    index = _as_index(mesh, "mesh")
+    _shape3(points, "points")
+    p = _points(points, "points", index.vertices.device)
+    votes = torch.zeros(p.shape[0], dtype=torch.int64, device=p.device)
+    for dk in INSIDE_DIRECTIONS:
+        d = torch.tensor(dk, dtype=torch.float64, device=p.device).expand(p.shape[0], 3)
+        votes += index.cast(p, d, mode="count") & 1
+    return 2 * votes > len(INSIDE_DIRECTIONS)
+
+
+def signed_distance(points, mesh, bound=math.inf):
+    """[M] float64: closest_on_mesh's distance from `points` to `mesh` ((vertices, faces) or a MeshIndex), negative
+    where contains_points says inside -- the magnitude is that distance bit for bit, +inf beyond `bound` with its sign
+    kept.  For closed meshes; see contains_points for what the sign means on an open one."""
+    index = _as_index(mesh, "mesh")
+    dist = index.closest(points, bound).dist
+    return torch.where(contains_points(points, index), -dist, dist)
 
 
 def _as_index(m, name):

@@ -539,10 +539,13 @@ class Trainer:
         return vertices, triangles
 
     @torch.no_grad()
-    def render_image(self, source, img_idx, resolution_level=4, chunk=65536, cos_anneal_ratio=1.0):
+    def render_image(self, source, img_idx, resolution_level=4, chunk=65536, cos_anneal_ratio=1.0, mesh=None):
         """validation render of one view (the loop of exp_runner_blending.py:506-560 without the file output): whole-image
         rays from the source, rendered in chunks of `chunk` rays -- large chunks, the renderer's working set at 65 536
-        rays x 146 samples is a few GB of the 288 GB -- -> dict(color [H', W', 3], depth [H', W'], normals [H', W', 3])."""
+        rays x 146 samples is a few GB of the 288 GB -- -> dict(color [H', W', 3], depth [H', W'], normals [H', W', 3]).
+        With `mesh` ((vertices, faces) or an evaluation.MeshIndex) the dict gains mesh_depth [H', W'] float64: the first-hit
+        t of the very rays that were rendered against that mesh (evaluation.cast_rays), +inf where they miss.  The
+        directions are unit vectors, so this is the unit of `depth`; nothing else changes."""
         rays_o, rays_d = source.gen_rays_at(img_idx, resolution_level=resolution_level)
         Hh, Ww, _ = rays_o.shape
         rays_o, rays_d = rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
@@ -553,5 +556,10 @@ class Trainer:
             r = self.renderer.render(o, d, near, far, cos_anneal_ratio=cos_anneal_ratio, perturb_overwrite=0,
                                      flip_saturation=1.0)
             outs["color"].append(r["color"]); outs["depth"].append(r["depth"].reshape(-1)); outs["normals"].append(r["normals"])
-        return {"color": torch.cat(outs["color"]).reshape(Hh, Ww, 3), "depth": torch.cat(outs["depth"]).reshape(Hh, Ww),
-                "normals": torch.cat(outs["normals"]).reshape(Hh, Ww, 3)}
+        res = {"color": torch.cat(outs["color"]).reshape(Hh, Ww, 3), "depth": torch.cat(outs["depth"]).reshape(Hh, Ww),
+               "normals": torch.cat(outs["normals"]).reshape(Hh, Ww, 3)}
+        if mesh is not None:
+            from . import evaluation
+            index = mesh if isinstance(mesh, evaluation.MeshIndex) else evaluation.MeshIndex(*mesh)
+            res["mesh_depth"] = index.cast(rays_o, rays_d).t.reshape(Hh, Ww)
+        return res
