@@ -21,7 +21,8 @@ extern "C" {
  * caller that mirrors this header by hand (neuraludf_amd/_lib.py) refuses a library whose nudf_version() differs.
  *   111: nudf_pc_tribin_count / nudf_pc_tribin_emit / nudf_pc_closest (point-to-mesh distance); NudfPointCloud grows by the
  *        md_ fields, appended at its end.  (nudf_pc_raycast and its md_ray_o ... md_count fields were appended later under
- *        the same number: the size table below refuses a package and a library that disagree on the struct's size)
+ *        the same number: the size table below refuses a package and a library that disagree on the struct's size;
+ *        nudf_meshsmooth_* and the sm_ fields at the end of NudfMeshOrient likewise: the version stays 111)
  *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
@@ -1323,12 +1324,63 @@ typedef struct NudfMeshOrient {
   int64_t n_verts;
   int64_t n_medges;
   int64_t n_comps;
+  /* smoothing and denoising (appended, the version stays 111: see nudf_meshsmooth_* below)                           */
+  const int64_t* sm_nbr_off; /* [n_verts + 1] CSR offsets of the one-ring of each vertex (laplace, uniform)          */
+  const int64_t* sm_nbr;     /* [sm_n_nbr] the neighbours of each vertex, ascending (laplace, uniform)               */
+  const uint8_t* sm_fixed;   /* NULL, or [n_verts]: non-zero = the vertex keeps its position (laplace, update)       */
+  double* sm_pos_out;        /* [n_verts, 3] the positions after the step; must not alias pos (laplace, update)      */
+  const double* sm_fnormal;  /* [n_faces, 3] unit face normals, (0, 0, 0) = the face takes no part (normals, update) */
+  double* sm_fnormal_out;    /* [n_faces, 3] (frames, normals); must not alias sm_fnormal                            */
+  double* sm_farea;          /* [n_faces] (frames: written; normals: read)                                           */
+  double* sm_fcentre;        /* [n_faces, 3] (frames: written; normals: read)                                        */
+  int64_t sm_n_nbr;          /* entries of sm_nbr                                                                    */
+  double sm_step;            /* laplace: lambda or mu                                                                */
+  double sm_inv2sc;          /* normals: 1 / (2 sigma_c^2), the spatial term                                         */
+  double sm_inv2ss;          /* normals: 1 / (2 sigma_s^2), the normal term                                          */
+  int32_t sm_weights;        /* laplace: 0 uniform, 1 cotangent                                                      */
+  int32_t sm_pad_;
 } NudfMeshOrient;
 int nudf_meshorient_hook(const NudfMeshOrient* args, void* stream);        /* one thread per manifold edge    */
 int nudf_meshorient_jump(const NudfMeshOrient* args, void* stream);        /* one thread per face             */
 int nudf_meshorient_check(const NudfMeshOrient* args, void* stream);       /* one thread per manifold edge    */
 int nudf_meshorient_outward(const NudfMeshOrient* args, void* stream);     /* one wavefront per component     */
 int nudf_meshorient_normals(const NudfMeshOrient* args, void* stream);     /* one thread per vertex           */
+
+/* ------------------------------------------------------------------------------------
+ * Mesh smoothing and denoising (neuraludf_amd/meshclean.py smooth_mesh, denoise_mesh): Taubin's lambda | mu smoothing with
+ * uniform or cotangent weights and the bilateral normal filter with a vertex update, the filters the reference's users
+ * take to trimesh.smoothing or open3d on the CPU; the reference itself smooths border vertices only
+ * (extract_mesh.py:238-265, nudf_meshtopo_smooth).  NudfMeshOrient grew at its end by the sm_ fields WITHOUT a version
+ * step, as NudfPointCloud did for nudf_pc_raycast: the size table of nudf_abi_struct refuses a package and a library that
+ * disagree.  faces, pos, corner_off, corner, n_faces and n_verts are those of nudf_meshorient_normals.  float64 without
+ * contraction, every sum in list order inside one thread, no atomics; laplace, frames and update equal
+ * tests/meshsmooth_ref.py bit for bit, normals up to the exp of its weight.  An index out of range
+ * skips the corner, the neighbour or the face.
+ *   laplace  one thread per vertex v: sm_pos_out[v] = pos[v] + sm_step (m - pos[v]).  sm_weights 0: m = the sum of pos[w]
+ *            over sm_nbr[sm_nbr_off[v] .. sm_nbr_off[v + 1]) in list order, divided by their number.  1: over the corners
+ *            of v in list order, corner (f, k) with a / b the next / previous vertex of f adds wa pos[a], then wb pos[b],
+ *            wa = max(cot at b, 0) / 2, wb = max(cot at a, 0) / 2, the cot at c = (x - c) . (y - c) / |(x - c) x (y - c)|
+ *            with x / y the next / previous vertex of c in f; a face in which one of the two lengths is 0 or not finite
+ *            adds nothing; m = the sum / W, W = the sum of (wa + wb).  A vertex with sm_fixed[v] != 0, or whose W (or
+ *            number of neighbours) is not finite or <= 0, copies its position;
+ *   frames   one thread per face: with n = (p1 - p0) x (p2 - p0), sm_fnormal_out = n / |n|, (0, 0, 0) where |n| is 0 or
+ *            not finite; sm_farea = |n| / 2; sm_fcentre = (p0 + (p1 + p2)) / 3.  All zero for a face with an index out of
+ *            range;
+ *   normals  one thread per face i: s = the sum of w n_j' over the faces j that share a vertex with i, met by walking the
+ *            corner lists of i's vertices in ascending vertex index; j is skipped when j = i, when sm_fnormal[j] is
+ *            (0, 0, 0) or when j holds a vertex of i walked earlier.  n_j' = n_j where n_i . n_j >= 0, else -n_j;
+ *            w = sm_farea[j] exp(-(|c_i - c_j|^2 sm_inv2sc + |n_i - n_j'|^2 sm_inv2ss)).  sm_fnormal_out[i] = s / |s|, or
+ *            n_i where |s| is 0 or not finite or n_i is (0, 0, 0);
+ *   update   one thread per vertex v: sm_pos_out[v] = pos[v] + (the sum over the corners of v in list order of
+ *            n_f (n_f . (c_f - pos[v]))) / count, n_f = sm_fnormal[f], c_f the centre of f from pos, count the corners
+ *            with n_f != (0, 0, 0); a vertex with sm_fixed[v] != 0 or count = 0 copies its position.
+ * Host-side refusals (no launch): n_verts >= 2^31, n_faces >= 2^36, a negative count, NULL buffers, sm_weights outside
+ * {0, 1}, sm_step not finite, sm_inv2sc or sm_inv2ss not finite or <= 0.  Empty descriptors return 0.
+ * ---------------------------------------------------------------------------------- */
+int nudf_meshsmooth_laplace(const NudfMeshOrient* args, void* stream);     /* one thread per vertex           */
+int nudf_meshsmooth_frames(const NudfMeshOrient* args, void* stream);      /* one thread per face             */
+int nudf_meshsmooth_normals(const NudfMeshOrient* args, void* stream);     /* one thread per face             */
+int nudf_meshsmooth_update(const NudfMeshOrient* args, void* stream);      /* one thread per vertex           */
 
 /* ------------------------------------------------------------------------------------
  * Triangle rasteriser with a depth buffer (neuraludf_amd/meshrender.py rasterize, vertex_visibility, color_vertices): depth,

@@ -256,7 +256,11 @@ class MeshOrient(C.Structure):
     _fields_ = [("faces", c_fp), ("me_a", c_fp), ("me_b", c_fp), ("word", c_fp), ("changed", c_fp), ("nonorient", c_fp),
                 ("comp_off", c_fp), ("comp_face", c_fp), ("comp_sum", c_fp), ("pos", c_fp), ("corner_off", c_fp),
                 ("corner", c_fp), ("normals", c_fp), ("origin", C.c_double * 3), ("n_faces", C.c_int64),
-                ("n_verts", C.c_int64), ("n_medges", C.c_int64), ("n_comps", C.c_int64)]
+                ("n_verts", C.c_int64), ("n_medges", C.c_int64), ("n_comps", C.c_int64),
+                ("sm_nbr_off", c_fp), ("sm_nbr", c_fp), ("sm_fixed", c_fp), ("sm_pos_out", c_fp), ("sm_fnormal", c_fp),
+                ("sm_fnormal_out", c_fp), ("sm_farea", c_fp), ("sm_fcentre", c_fp), ("sm_n_nbr", C.c_int64),
+                ("sm_step", C.c_double), ("sm_inv2sc", C.c_double), ("sm_inv2ss", C.c_double), ("sm_weights", i32),
+                ("sm_pad_", i32)]
 
 
 class MeshRaster(C.Structure):
@@ -359,7 +363,8 @@ SIGNATURES = {
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces")),
-        (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals")),
+        (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals",
+                      "meshsmooth_laplace", "meshsmooth_frames", "meshsmooth_normals", "meshsmooth_update")),
         (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",
                       "meshraster_resolve", "meshraster_visible", "meshraster_colour")),
     ) for n in names},

@@ -8,7 +8,10 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
     orientation  orient_faces        consistent winding per component (csrc/meshorient.hip); the reference leaves it out
                                      (extract_mesh.py:218-219: trimesh's serial traversal is "too slow")
     normals      vertex_normals      extract_mesh.py:272-275 (trimesh weighted_vertex_normals, angle-weighted)
-    simplify     simplify_mesh, simplify_to_faces     vertex clustering with quadric placement (csrc/meshsimplify.hip);
+    smoothing    smooth_mesh, denoise_mesh, vertex_adjacency     Taubin's lambda | mu smoothing (uniform or cotangent) and the
+                                     bilateral normal filter with its vertex update (csrc/meshsmooth.hip); the reference
+                                     smooths the border only, its users take the rest to trimesh or open3d on the CPU
+    simplify     simplify_mesh, simplify_to_faces    vertex clustering with quadric placement (csrc/meshsimplify.hip);
                                      the reference's users take this step to trimesh or open3d on the CPU
     measure      simplify_to_error, transfer_attributes   simplification to a measured two-sided deviation, attributes
                                      carried to the closest point of another mesh (evaluation.closest_on_mesh,
@@ -352,6 +355,15 @@ def orient_faces(verts, faces, outward_from=None, _info=None):
     return Orientation(out, flipped, labels, orientable)
 
 
+def _corner_lists(faces, n_verts):
+    """-> (corner_off [V + 1], corner [3 F]): the corners 3 f + k by vertex, ascending inside each"""
+    flat = faces.reshape(-1)
+    corner = torch.sort(flat, stable=True).indices
+    corner_off = torch.zeros(n_verts + 1, dtype=torch.int64, device=faces.device)
+    torch.cumsum(torch.bincount(flat, minlength=n_verts), 0, out=corner_off[1:])
+    return corner_off, corner
+
+
 def vertex_normals(verts, faces, dtype=torch.float32):
     """angle-weighted vertex normals -> [V, 3] `dtype` (float32 or float64), computed in float64 and cast at the end:
     trimesh's weighted_vertex_normals, which the reference calls (extract_mesh.py:272-275).  With n_f = (p1 - p0) x
@@ -367,14 +379,194 @@ def vertex_normals(verts, faces, dtype=torch.float32):
     if n_verts == 0 or faces.shape[0] == 0:
         return normals.to(dtype)
     pos = verts.double().contiguous()
-    flat = faces.reshape(-1)
-    corner = torch.sort(flat, stable=True).indices                       # corners 3 f + k by vertex, ascending inside
-    corner_off = torch.zeros(n_verts + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(torch.bincount(flat, minlength=n_verts), 0, out=corner_off[1:])
+    corner_off, corner = _corner_lists(faces, n_verts)
     d = _lib.MeshOrient(faces=ptr(faces), pos=ptr(pos), corner_off=ptr(corner_off), corner=ptr(corner),
                         normals=ptr(normals), n_faces=faces.shape[0], n_verts=n_verts)
     call("nudf_meshorient_normals", d)
     return normals.to(dtype)
+
+
+def vertex_adjacency(faces, n_verts, table=None):
+    """the one-ring of every vertex -> (nbr_off [V + 1], nbr) int64, a CSR with the neighbours of each vertex ascending:
+    the other ends of the unique edges at the vertex (an edge from a vertex to itself, which a face with a repeated vertex
+    has, is none).  Both directions of the edge table's rows under one stable key sort; `table`: the mesh's EdgeTable
+    where the caller has one."""
+    faces, n_verts = _check_faces(faces, n_verts)
+    return _vertex_adjacency(faces, n_verts, table)
+
+
+def _vertex_adjacency(faces, n_verts, table=None):
+    dev = faces.device
+    nbr_off = torch.zeros(n_verts + 1, dtype=torch.int64, device=dev)
+    if faces.shape[0] == 0 or n_verts == 0:
+        return nbr_off, torch.zeros(0, dtype=torch.int64, device=dev)
+    e = (table if table is not None else _mesh_edges(faces, n_verts)).edges
+    e = e[e[:, 0] != e[:, 1]]
+    key = torch.sort(torch.cat([e[:, 0] * n_verts + e[:, 1], e[:, 1] * n_verts + e[:, 0]]), stable=True).values
+    src = key // n_verts
+    torch.cumsum(torch.bincount(src, minlength=n_verts), 0, out=nbr_off[1:])
+    return nbr_off, (key - src * n_verts).contiguous()
+
+
+def _count(x, name):
+    try:
+        n = int(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be an integer >= 0 (got {x!r})") from None
+    if n < 0 or n != x:
+        raise ValueError(f"{name} must be an integer >= 0 (got {x!r})")
+    return n
+
+
+def _finite(x, name, positive=False):
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a finite number (got {x!r})") from None
+    if not math.isfinite(v) or (positive and not v > 0):
+        raise ValueError(f"{name} must be a {'positive ' if positive else ''}finite number (got {x!r})")
+    return v
+
+
+def _fixed_mask(verts, table, boundary, fixed):
+    """the vertices that keep their positions -> uint8 [V], or None when there are none to keep: the caller's mask and,
+    with boundary="fixed", the ends of the edges with one face"""
+    if boundary not in ("fixed", "free"):
+        raise ValueError(f"boundary must be 'fixed' or 'free' (got {boundary!r})")
+    n_verts, dev = verts.shape[0], verts.device
+    mask = None
+    if fixed is not None:
+        mask = torch.as_tensor(fixed, device=dev)
+        if mask.dim() != 1 or mask.shape[0] != n_verts or mask.is_floating_point() or mask.is_complex():
+            raise ValueError(f"fixed must be a [{n_verts}] boolean mask (got {mask.dtype} {tuple(mask.shape)})")
+        mask = mask != 0
+    if boundary == "fixed" and table is not None:
+        e = table.edges
+        b = e[e[:, 2] == 1]
+        mask = torch.zeros(n_verts, dtype=torch.bool, device=dev) if mask is None else mask.clone()
+        mask[b[:, 0]] = True
+        mask[b[:, 1]] = True
+    return None if mask is None else mask.to(torch.uint8).contiguous()
+
+
+def _laplace_step(d, pos, out, step):
+    d.pos, d.sm_pos_out, d.sm_step = ptr(pos), ptr(out), step
+    call("nudf_meshsmooth_laplace", d)
+    return out
+
+
+def smooth_mesh(verts, faces, iterations=10, lam=0.5, mu=-0.53, weights="uniform", boundary="fixed", fixed=None):
+    """Laplacian smoothing of the whole mesh, by default Taubin's lambda | mu scheme -> verts' [V, 3] in the input's dtype
+    (csrc/meshsmooth.hip; trimesh.smoothing.filter_taubin and open3d's filter_smooth_taubin on the CPU).  Each of
+    `iterations` rounds is a Jacobi step p + lam (m - p) and, unless mu = 0, a second one with mu (negative: it undoes the
+    shrinkage of the first; mu = 0 is plain Laplacian smoothing), every step from the positions of the one before.
+    weights="uniform": m is the mean of the one-ring (vertex_adjacency), summed in ascending index.  "cotangent": m is
+    the mean weighted by max(cot, 0) / 2 of the angles opposite each edge, summed over the vertex's corners in ascending
+    3 f + k from the positions of the current step; a face of zero area adds nothing.  boundary="fixed" keeps the ends of
+    the edges with exactly one face where they are, "free" lets them move (an open surface then shrinks at its border);
+    `fixed` [V] marks further vertices to keep.  A vertex without neighbours, or with cotangent weights one whose faces
+    are all degenerate, stays.  float64 inside, cast at the end; identical from run to run.  An empty mesh and
+    iterations = 0 return the input."""
+    iterations = _count(iterations, "iterations")
+    lam, mu = _finite(lam, "lam"), _finite(mu, "mu")
+    if weights not in ("uniform", "cotangent"):
+        raise ValueError(f"weights must be 'uniform' or 'cotangent' (got {weights!r})")
+    verts, faces = _check_mesh(verts, faces)
+    n_verts, n_faces = verts.shape[0], faces.shape[0]
+    table = _mesh_edges(faces, n_verts) if n_faces and n_verts and (weights == "uniform" or boundary == "fixed") else None
+    mask = _fixed_mask(verts, table, boundary, fixed)
+    if n_faces == 0 or n_verts == 0 or iterations == 0:
+        return verts
+    d = _lib.MeshOrient(faces=ptr(faces), n_faces=n_faces, n_verts=n_verts, sm_fixed=ptr(mask),
+                        sm_weights=0 if weights == "uniform" else 1)
+    if weights == "uniform":
+        nbr_off, nbr = _vertex_adjacency(faces, n_verts, table)
+        d.sm_nbr_off, d.sm_nbr, d.sm_n_nbr = ptr(nbr_off), ptr(nbr), nbr.numel()
+    else:
+        corner_off, corner = _corner_lists(faces, n_verts)
+        d.corner_off, d.corner = ptr(corner_off), ptr(corner)
+    pos = verts.double().contiguous()                # may be the caller's tensor: read only
+    bufs = [torch.empty_like(pos), torch.empty_like(pos)]
+    n = 0
+    for _ in range(iterations):
+        for step in (lam, mu) if mu != 0 else (lam,):
+            pos = _laplace_step(d, pos, bufs[n % 2], step)
+            n += 1
+    return pos.to(verts.dtype)
+
+
+def _mean_edge_length(pos, table):
+    """numpy's mean of the float64 lengths of the unique edges (u != v) in the table's order; one copy to the host, so that
+    the value does not depend on the order of a reduction on the GPU"""
+    e = table.edges
+    e = e[e[:, 0] != e[:, 1]]
+    d = pos[e[:, 0]] - pos[e[:, 1]]
+    d2 = d * d
+    length = torch.sqrt((d2[:, 0] + d2[:, 1]) + d2[:, 2])
+    return float(np.mean(length.cpu().numpy())) if length.numel() else math.nan
+
+
+def _face_frames(d, n_faces, dev):
+    """launches frames -> (normals [F, 3], areas [F], centres [F, 3]) float64; d must hold faces and pos"""
+    fnormal = torch.empty((n_faces, 3), dtype=torch.float64, device=dev)
+    area = torch.empty(n_faces, dtype=torch.float64, device=dev)
+    centre = torch.empty((n_faces, 3), dtype=torch.float64, device=dev)
+    d.sm_fnormal_out, d.sm_farea, d.sm_fcentre = ptr(fnormal), ptr(area), ptr(centre)
+    call("nudf_meshsmooth_frames", d)
+    return fnormal, area, centre
+
+
+def denoise_mesh(verts, faces, normal_iterations=5, vertex_iterations=10, sigma_s=0.35, sigma_c=None, boundary="fixed",
+                 fixed=None):
+    """feature-preserving denoising: a bilateral filter on the face normals, then the vertices moved to fit them
+    -> (verts' [V, 3], face normals [F, 3]), both in the input's dtype (csrc/meshsmooth.hip; Zheng et al. 2011, "Bilateral
+    normal filtering for mesh denoising", with the vertex update of Sun et al. 2007).  The normals, areas and centres of
+    the faces are taken once from the input.  Each of `normal_iterations` steps replaces the normal of face i by the
+    normalised sum, over the faces j that share a vertex with i, of area_j exp(-|c_i - c_j|^2 / (2 sigma_c^2)
+    - |n_i - n_j'|^2 / (2 sigma_s^2)) n_j', where n_j' is n_j turned into the half-space of n_i: the mesher's faces are not
+    consistently wound, and without the turn neighbours of opposite winding would cancel.  The returned normals keep the
+    side of the input's faces.  sigma_c = None: the mean length of the unique edges.  Each of `vertex_iterations` Jacobi
+    steps then moves a vertex by the mean over its faces of n_f (n_f . (c_f - p)), c_f the current centre of the face.
+    `boundary` and `fixed` as in smooth_mesh; a vertex whose faces all have zero area stays, a face of zero area has the
+    normal (0, 0, 0) and takes no part.  The neighbours of a face are visited through its vertices in ascending index, so
+    the result does not depend on the winding: flipping faces leaves the positions bit for bit and the normals up to
+    sign.  float64 inside, cast at the end; identical from run to run.  An empty mesh returns the input and no normals."""
+    normal_iterations = _count(normal_iterations, "normal_iterations")
+    vertex_iterations = _count(vertex_iterations, "vertex_iterations")
+    sigma_s = _finite(sigma_s, "sigma_s", positive=True)
+    if sigma_c is not None:
+        sigma_c = _finite(sigma_c, "sigma_c", positive=True)
+    verts, faces = _check_mesh(verts, faces)
+    n_verts, n_faces, dev = verts.shape[0], faces.shape[0], verts.device
+    table = None
+    if n_faces and n_verts and (boundary == "fixed" or (sigma_c is None and normal_iterations)):
+        table = _mesh_edges(faces, n_verts)
+    mask = _fixed_mask(verts, table, boundary, fixed)
+    if n_faces == 0 or n_verts == 0:
+        return verts, torch.zeros((n_faces, 3), dtype=verts.dtype, device=dev)
+    pos = verts.double().contiguous()                # may be the caller's tensor: read only
+    corner_off, corner = _corner_lists(faces, n_verts)
+    d = _lib.MeshOrient(faces=ptr(faces), pos=ptr(pos), corner_off=ptr(corner_off), corner=ptr(corner), n_faces=n_faces,
+                        n_verts=n_verts, sm_fixed=ptr(mask))
+    fnormal, area, centre = _face_frames(d, n_faces, dev)
+    if normal_iterations:
+        if sigma_c is None:
+            sigma_c = _mean_edge_length(pos, table)
+            if not (sigma_c > 0 and math.isfinite(sigma_c)):
+                raise ValueError(f"the mean edge length {sigma_c} is not positive and finite: give sigma_c")
+        d.sm_inv2sc, d.sm_inv2ss = 1.0 / (2.0 * sigma_c * sigma_c), 1.0 / (2.0 * sigma_s * sigma_s)
+        other = torch.empty_like(fnormal)
+        for _ in range(normal_iterations):
+            d.sm_fnormal, d.sm_fnormal_out = ptr(fnormal), ptr(other)
+            call("nudf_meshsmooth_normals", d)
+            fnormal, other = other, fnormal
+    d.sm_fnormal = ptr(fnormal)
+    bufs = [torch.empty_like(pos), torch.empty_like(pos)] if vertex_iterations else []
+    for i in range(vertex_iterations):
+        d.pos, d.sm_pos_out = ptr(pos), ptr(bufs[i % 2])
+        call("nudf_meshsmooth_update", d)
+        pos = bufs[i % 2]
+    return pos.to(verts.dtype), fnormal.to(verts.dtype)
 
 
 def compact_mesh(verts, faces, vertex_mask=None, face_mask=None, drop_unreferenced=True):
