@@ -22,7 +22,8 @@ extern "C" {
  *   111: nudf_pc_tribin_count / nudf_pc_tribin_emit / nudf_pc_closest (point-to-mesh distance); NudfPointCloud grows by the
  *        md_ fields, appended at its end.  (nudf_pc_raycast and its md_ray_o ... md_count fields were appended later under
  *        the same number: the size table below refuses a package and a library that disagree on the struct's size;
- *        nudf_meshsmooth_* and the sm_ fields at the end of NudfMeshOrient likewise: the version stays 111)
+ *        nudf_meshsmooth_* and the sm_ fields at the end of NudfMeshOrient likewise, and nudf_meshsubdiv_* with the sp_sd_
+ *        fields at the end of NudfMeshTopo: the version stays 111)
  *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
@@ -1238,6 +1239,29 @@ typedef struct NudfMeshTopo {
                                  /* edges / he_edge are not read                                                     */
   int32_t sp_attr_width;
   int32_t sp_placement;          /* place: 0 quadric, 1 mean (no corner walk, sp_accepted all 0)                     */
+  /* subdivision (nudf_meshsubdiv_*, below), appended WITHOUT a version step.  The prefix is sp_sd_ because the tests of
+   * the simplification pin that every field after pad_ is named sp_... (or n_clusters); `faces`, `edges`, `he_edge`,
+   * `he_id`, `edge_start`, `nbr_off` / `nbr`, `pos`, sp_attr, sp_attr_width, n_faces, n_verts and n_edges are read too */
+  uint8_t* sp_sd_mark;               /* [n_edges] 1: the edge is split (mark)                                        */
+  const int64_t* sp_sd_edge_vertex;  /* [n_edges] n_verts + rank among the marked edges, or -1 (count, emit)         */
+  const int64_t* sp_sd_marked;       /* [sp_sd_n_marked] the marked edges, ascending (odd)                           */
+  const int64_t* sp_sd_ring_off;     /* [n_verts + 1] CSR offsets of the one-rings (even, scheme 1)                  */
+  const int64_t* sp_sd_ring;         /* [sp_sd_n_ring] the one-ring of each vertex, ascending (even, scheme 1)       */
+  const uint8_t* sp_sd_vclass;       /* [n_verts] 0 smooth, 1 border, 2 stays (even, scheme 1)                       */
+  double* sp_sd_pos_out;             /* [n_verts + sp_sd_n_marked, 3] (even: the first n_verts rows, odd: the rest;  */
+                                     /* emit reads it)                                                               */
+  double* sp_sd_attr_out;            /* [n_verts + sp_sd_n_marked, sp_attr_width], rows as in sp_sd_pos_out          */
+  int64_t* sp_sd_fcount;             /* [n_faces] children of each face (count)                                      */
+  const int64_t* sp_sd_foff;         /* [n_faces] exclusive prefix sum of sp_sd_fcount (emit)                        */
+  int64_t* sp_sd_faces_out;          /* [sp_sd_n_out, 3] (emit)                                                      */
+  int64_t* sp_sd_parent;             /* [sp_sd_n_out] the input face of each output face (emit)                      */
+  int64_t sp_sd_n_ring;
+  int64_t sp_sd_n_border;            /* entries of `nbr` (even, scheme 1)                                            */
+  int64_t sp_sd_n_marked;
+  int64_t sp_sd_n_out;
+  double sp_sd_max_edge;             /* mark: > 0 and finite unless sp_sd_mark_all                                   */
+  int32_t sp_sd_scheme;              /* odd, even: 0 midpoint, 1 loop                                                */
+  int32_t sp_sd_mark_all;            /* mark: non-zero marks every edge with u != v                                  */
 } NudfMeshTopo;
 int nudf_meshtopo_edges(const NudfMeshTopo* args, void* stream);       /* one thread per unique edge      */
 int nudf_meshtopo_fill_count(const NudfMeshTopo* args, void* stream);  /* one thread per boundary vertex  */
@@ -1278,6 +1302,45 @@ int nudf_meshtopo_views(const NudfMeshTopo* args, void* stream);       /* one th
 int nudf_meshsimplify_keys(const NudfMeshTopo* args, void* stream);    /* one thread per vertex           */
 int nudf_meshsimplify_place(const NudfMeshTopo* args, void* stream);   /* one thread per cluster          */
 int nudf_meshsimplify_faces(const NudfMeshTopo* args, void* stream);   /* one thread per face             */
+
+/* ------------------------------------------------------------------------------------
+ * Mesh subdivision (neuraludf_amd/meshclean.py subdivide_mesh, subdivide_to_edge): Loop and midpoint subdivision and
+ * splitting of the edges longer than a bound.  The reference has no such step: its users take the mesh to
+ * trimesh.remesh.subdivide / subdivide_loop / subdivide_to_size or open3d on the CPU.  The entry points take NudfMeshTopo
+ * and read the sp_sd_ fields at its end (no version step: the size table of nudf_abi_struct refuses a package and a library
+ * that disagree).  An edge is a row of `edges`.  The caller ranks the marked edges and scans the face counts between the
+ * launches; float64 without contracted multiply-adds, every sum in list order inside one thread, no atomics: every result
+ * is identical from run to run and equals tests/meshsubdiv_ref.py bit for bit.
+ *   mark    one thread per edge (u, v): sp_sd_mark[e] = u != v && (sp_sd_mark_all || (dx dx + dy dy) + dz dz >
+ *           sp_sd_max_edge sp_sd_max_edge), d = pos[u] - pos[v]; a NaN length is not marked.  The new vertex of the j-th
+ *           marked edge is n_verts + j: the output vertices are the old ones followed by one per marked edge;
+ *   odd     one thread per marked edge: row n_verts + j of sp_sd_pos_out.  Scheme 0: (p_u + p_v) 0.5.  Scheme 1: an edge
+ *           with exactly two half-edges h0 = he_id[edge_start[e]] and h1 = he_id[edge_start[e] + 1] gets
+ *           (p_u + p_v) 0.375 + (p_a + p_b) 0.125, a and b = faces[h / 3][(h % 3 + 2) % 3] of h0 and h1; every other
+ *           edge is a crease and gets the midpoint;
+ *   even    one thread per old vertex: row v of sp_sd_pos_out.  Scheme 0: a copy.  Scheme 1: class 2 stays; class 1, with
+ *           exactly two border neighbours b0 <= b1 in `nbr`, moves to p 0.75 + (p_b0 + p_b1) 0.125; class 0 with a
+ *           one-ring of n > 0 vertices moves to p (1 - n beta) + s beta, beta = 3 / 16 for n = 3 and 3 / (8 n) otherwise,
+ *           s the sum of the ring in list order starting from its first entry; anything else stays.  The caller sets
+ *           class 2 for a vertex on an edge with three or more half-edges or with a number of border edges other than 0
+ *           and 2, class 1 for one with two border edges;
+ *   count   one thread per face: sp_sd_fcount[f] = 1 + its marked half-edges;
+ *   emit    one thread per face, children at sp_sd_foff[f] in the parent's winding, m_k the new vertex of half-edge
+ *           k (v_k -> v_k+1):  none marked: (v0, v1, v2);  one, k, with (a, b, c) = (v_k, v_k+1, v_k+2): (a, m, c),
+ *           (m, b, c);  two, k unmarked, (a, b, c) as before, m1 = m_k+1, m2 = m_k+2: (m1, c, m2), then the quad
+ *           a b m1 m2 along the shorter of a-m1 and b-m2 (squared float64 lengths in sp_sd_pos_out, on a tie a-m1 exactly
+ *           when a < b): (a, b, m1), (a, m1, m2) or (a, b, m2), (b, m1, m2);  three: (v0, m0, m2), (m0, v1, m1),
+ *           (m2, m1, v2), (m0, m1, m2).  sp_sd_parent[i] = f for each child i.
+ * sp_attr columns go through the weights of the positions into sp_sd_attr_out.  An index read from a table that is out
+ * of range makes its item a copy (odd: a zero row; emit: nothing written); nothing is addressed outside the buffers.
+ * Host-side refusals (no launch): negative counts, n_verts + sp_sd_n_marked >= 2^31, n_faces >= 2^31, NULL buffers,
+ * sp_sd_max_edge not positive and finite without sp_sd_mark_all, an unknown sp_sd_scheme.  Empty jobs return 0.
+ * ---------------------------------------------------------------------------------- */
+int nudf_meshsubdiv_mark(const NudfMeshTopo* args, void* stream);      /* one thread per unique edge      */
+int nudf_meshsubdiv_odd(const NudfMeshTopo* args, void* stream);       /* one thread per marked edge      */
+int nudf_meshsubdiv_even(const NudfMeshTopo* args, void* stream);      /* one thread per vertex           */
+int nudf_meshsubdiv_count(const NudfMeshTopo* args, void* stream);     /* one thread per face             */
+int nudf_meshsubdiv_emit(const NudfMeshTopo* args, void* stream);      /* one thread per face             */
 
 /* ------------------------------------------------------------------------------------
  * Consistent face orientation and vertex normals (neuraludf_amd/meshclean.py orient_faces, vertex_normals): the step the

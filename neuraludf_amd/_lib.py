@@ -249,7 +249,13 @@ class MeshTopo(C.Structure):
                 ("sp_accepted", c_fp), ("sp_quadric", c_fp), ("sp_attr_out", c_fp), ("sp_faces", c_fp),
                 ("sp_triple", c_fp), ("sp_degenerate", c_fp), ("n_clusters", C.c_int64), ("sp_grid", C.c_int64 * 3),
                 ("sp_origin", C.c_double * 3), ("sp_cell", C.c_double), ("sp_lambda", C.c_double),
-                ("sp_boundary_weight", C.c_double), ("sp_attr_width", i32), ("sp_placement", i32)]
+                ("sp_boundary_weight", C.c_double), ("sp_attr_width", i32), ("sp_placement", i32),
+                ("sp_sd_mark", c_fp), ("sp_sd_edge_vertex", c_fp), ("sp_sd_marked", c_fp), ("sp_sd_ring_off", c_fp),
+                ("sp_sd_ring", c_fp), ("sp_sd_vclass", c_fp), ("sp_sd_pos_out", c_fp), ("sp_sd_attr_out", c_fp),
+                ("sp_sd_fcount", c_fp), ("sp_sd_foff", c_fp), ("sp_sd_faces_out", c_fp), ("sp_sd_parent", c_fp),
+                ("sp_sd_n_ring", C.c_int64), ("sp_sd_n_border", C.c_int64), ("sp_sd_n_marked", C.c_int64),
+                ("sp_sd_n_out", C.c_int64), ("sp_sd_max_edge", C.c_double), ("sp_sd_scheme", i32),
+                ("sp_sd_mark_all", i32)]
 
 
 class MeshOrient(C.Structure):
@@ -362,7 +368,8 @@ SIGNATURES = {
                       "pc_tribin_count", "pc_tribin_emit", "pc_closest", "pc_raycast")),
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
-                    "meshsimplify_faces")),
+                    "meshsimplify_faces", "meshsubdiv_mark", "meshsubdiv_odd", "meshsubdiv_even", "meshsubdiv_count",
+                    "meshsubdiv_emit")),
         (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals",
                       "meshsmooth_laplace", "meshsmooth_frames", "meshsmooth_normals", "meshsmooth_update")),
         (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",

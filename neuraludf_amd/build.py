@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libnudf.so")
 SOURCES = ["nudf_api.hip", "gemm_f32_mfma.hip", "gemm_tn_f32_mfma.hip", "rays_embed.hip", "composite.hip", "upsample.hip",
            "blend.hip", "optim.hip", "mlp_chain.hip", "mlp_chain_rows.hip", "raybatch.hip", "meshudf.hip",
            "meshudf_sparse.hip", "isosurface.hip", "pointcloud.hip", "meshtopo.hip", "meshorient.hip", "meshraster.hip",
-           "meshsimplify.hip", "meshdist.hip", "meshray.hip", "meshsmooth.hip"]
+           "meshsimplify.hip", "meshdist.hip", "meshray.hip", "meshsmooth.hip", "meshsubdiv.hip"]
 
 
 # the sources that decide what a kernel class reads and writes (bench.py `roofline.traffic_stale`: a PMC traffic file under
@@ -41,6 +41,7 @@ KERNEL_SOURCES = {
     "meshdist": ["csrc/meshdist.hip", "csrc/nudf_common.h", "../include/nudf.h"],
     "meshray": ["csrc/meshray.hip", "csrc/nudf_common.h", "../include/nudf.h"],
     "meshsmooth": ["csrc/meshsmooth.hip", "csrc/nudf_common.h", "../include/nudf.h"],
+    "meshsubdiv": ["csrc/meshsubdiv.hip", "csrc/nudf_common.h", "../include/nudf.h"],
     "meshraster": ["csrc/meshraster.hip", "csrc/meshraster_pixel.h", "csrc/nudf_common.h", "../include/nudf.h"],
 }
 

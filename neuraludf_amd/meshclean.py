@@ -16,6 +16,9 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
     measure      simplify_to_error, transfer_attributes   simplification to a measured two-sided deviation, attributes
                                      carried to the closest point of another mesh (evaluation.closest_on_mesh,
                                      csrc/meshdist.hip; trimesh.proximity.closest_point on the CPU)
+    subdivide    subdivide_mesh, subdivide_to_edge    Loop and midpoint subdivision, and midpoint splits of the edges above
+                                     a length (csrc/meshsubdiv.hip; trimesh.remesh.subdivide / subdivide_loop /
+                                     subdivide_to_size on the CPU)
     views        clean_by_views, clean_dtu_mesh         clean_dtu_mesh.py:36-154 (mask and visual-hull cleaning)
     masks        ellipse_footprint, dilate_masks, load_dtu_views
 
@@ -982,6 +985,171 @@ def transfer_attributes(src_verts, src_faces, src_attributes, dst_points, bound=
     out[~hit] = math.nan
     return out.to(src_attributes.dtype)
 
+
+class Subdivided(NamedTuple):
+    """verts [V', 3] in the input's dtype, the first V rows being the input's vertices; faces [F', 3] int64; attributes
+    [V', k] in their input's dtype, or None; parent_face [F'] int64: the input face each output face lies in; rounds: the
+    rounds that split an edge; longest_edge: the float64 length of the result's longest edge; converged: False only when
+    subdivide_to_edge stopped at max_rounds with edges above the bound left"""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    attributes: torch.Tensor | None
+    parent_face: torch.Tensor
+    rounds: int
+    longest_edge: float
+    converged: bool
+
+
+_SUBDIVIDE_SCHEMES = {"midpoint": 0, "loop": 1}
+
+
+def _longest_edge(pos, table):
+    """the float64 length of the longest edge with two different ends, 0.0 without one: the maximum of
+    (dx dx + dy dy) + dz dz on the GPU (a maximum does not depend on its order) and one square root on the host"""
+    e = table.edges
+    e = e[e[:, 0] != e[:, 1]]
+    if e.shape[0] == 0:
+        return 0.0
+    d = pos[e[:, 0]] - pos[e[:, 1]]
+    d2 = d * d
+    return math.sqrt(float(((d2[:, 0] + d2[:, 1]) + d2[:, 2]).max()))
+
+
+def _loop_classes(table, boundary, n_verts):
+    """-> uint8 [V]: 2 (stays) for the ends of an edge with three or more half-edges and for a vertex whose number of
+    border edges is neither 0 nor 2, 1 (border) for one with two border edges, 0 (smooth) otherwise"""
+    e = table.edges
+    bdeg = boundary.nbr_off[1:] - boundary.nbr_off[:-1]
+    vclass = torch.zeros(n_verts, dtype=torch.uint8, device=e.device)
+    vclass[bdeg == 2] = 1
+    vclass[(bdeg != 0) & (bdeg != 2)] = 2
+    multi = e[e[:, 2] >= 3]
+    vclass[multi[:, 0]] = 2
+    vclass[multi[:, 1]] = 2
+    return vclass
+
+
+def _subdivide_round(pos, faces, attr, scheme, max_edge, split=True, events=None, state=None):
+    """one round on float64 positions (and attributes or None): marks every edge (max_edge None) or those longer than
+    max_edge and, with `split`, splits them -> (edges marked, pos', faces', attr', parent, table); faces' is None when
+    nothing was split, and `table` is the input's EdgeTable"""
+    n_verts, n_faces, dev = pos.shape[0], faces.shape[0], pos.device
+    _stage(events, state, "edges")
+    table = _mesh_edges(faces, n_verts)
+    n_edges = table.edges.shape[0]
+    d = _topo(faces, n_verts, table)
+    d.pos = ptr(pos)
+    _stage(events, state, "mark")
+    mark = torch.empty(n_edges, dtype=torch.uint8, device=dev)
+    d.sp_sd_mark, d.sp_sd_mark_all, d.sp_sd_max_edge = ptr(mark), int(max_edge is None), 0.0 if max_edge is None else max_edge
+    call("nudf_meshsubdiv_mark", d)
+    marked = torch.nonzero(mark).reshape(-1)
+    n_marked = marked.numel()
+    if n_marked == 0 or not split:
+        _stage(events, state, None)
+        return n_marked, pos, None, attr, None, table
+    if n_verts + n_marked >= MAX_VERTS:
+        raise ValueError(f"{n_verts} vertices and {n_marked} split edges: the result would have 2^31 vertices or more")
+    rank = torch.cumsum(mark, 0, dtype=torch.int64)
+    edge_vertex = torch.where(mark != 0, rank + (n_verts - 1), torch.full_like(rank, -1))
+    d.sp_sd_marked, d.sp_sd_edge_vertex, d.sp_sd_n_marked, d.sp_sd_scheme = ptr(marked), ptr(edge_vertex), n_marked, scheme
+    pos_out = torch.empty((n_verts + n_marked, 3), dtype=torch.float64, device=dev)
+    d.sp_sd_pos_out = ptr(pos_out)
+    attr_out = None
+    if attr is not None:
+        attr_out = torch.empty((n_verts + n_marked, attr.shape[1]), dtype=torch.float64, device=dev)
+        if attr.shape[1]:
+            d.sp_attr, d.sp_sd_attr_out, d.sp_attr_width = ptr(attr), ptr(attr_out), attr.shape[1]
+    if scheme == 1:
+        _stage(events, state, "adjacency")
+        ring_off, ring = _vertex_adjacency(faces, n_verts, table)
+        boundary = _boundary(table, n_verts)
+        vclass = _loop_classes(table, boundary, n_verts)
+        d.sp_sd_ring_off, d.sp_sd_ring, d.sp_sd_n_ring = ptr(ring_off), ptr(ring), ring.numel()
+        d.nbr_off, d.nbr, d.sp_sd_n_border = ptr(boundary.nbr_off), ptr(boundary.nbr), boundary.nbr.numel()
+        d.sp_sd_vclass = ptr(vclass)
+    _stage(events, state, "vertices")
+    call("nudf_meshsubdiv_odd", d)
+    call("nudf_meshsubdiv_even", d)
+    _stage(events, state, "faces")
+    fcount = torch.empty(n_faces, dtype=torch.int64, device=dev)
+    d.sp_sd_fcount = ptr(fcount)
+    call("nudf_meshsubdiv_count", d)
+    fend = torch.cumsum(fcount, 0)
+    foff = fend - fcount
+    n_out = int(fend[-1])
+    faces_out = torch.empty((n_out, 3), dtype=torch.int64, device=dev)
+    parent = torch.empty(n_out, dtype=torch.int64, device=dev)
+    d.sp_sd_foff, d.sp_sd_faces_out, d.sp_sd_parent, d.sp_sd_n_out = ptr(foff), ptr(faces_out), ptr(parent), n_out
+    call("nudf_meshsubdiv_emit", d)
+    _stage(events, state, None)
+    return n_marked, pos_out, faces_out, attr_out, parent, table
+
+
+def _subdivide(verts, faces, attributes, scheme, max_edge, rounds_cap, _info):
+    """the rounds of both drivers: `rounds_cap` rounds of `scheme` on every edge (max_edge None), or rounds of midpoint
+    splits of the edges above max_edge until none is left or the cap is reached"""
+    verts, faces = _check_mesh(verts, faces)
+    attributes = _check_attributes(attributes, verts)
+    n_faces, dev = faces.shape[0], verts.device
+    parent = torch.arange(n_faces, dtype=torch.int64, device=dev)
+    if verts.shape[0] == 0 or n_faces == 0:
+        return Subdivided(verts, faces, attributes, parent, 0, 0.0, True)
+    events = None if _info is None else _info.get("events")
+    pos = verts.double().contiguous()                    # may be the caller's tensor: read only
+    attr = None if attributes is None else attributes.double().contiguous()
+    out_faces, rounds, converged, table = faces, 0, True, None
+    while max_edge is not None or rounds < rounds_cap:
+        stages = None if events is None else events.setdefault(f"round{rounds}", {})
+        n_marked, new_pos, new_faces, new_attr, new_parent, table = _subdivide_round(
+            pos, out_faces, attr, scheme, max_edge, rounds < rounds_cap, stages, {})
+        if new_faces is None:                            # nothing to split, or the cap: only the marks were looked at
+            converged = n_marked == 0
+            break
+        pos, out_faces, attr, parent, rounds, table = new_pos, new_faces, new_attr, parent[new_parent], rounds + 1, None
+    if table is None:
+        table = _mesh_edges(out_faces, pos.shape[0])
+    return Subdivided(pos.to(verts.dtype), out_faces, None if attributes is None else attr.to(attributes.dtype), parent,
+                      rounds, _longest_edge(pos, table), converged)
+
+
+def subdivide_mesh(verts, faces, levels=1, scheme="loop", attributes=None, _info=None):
+    """uniform subdivision, `levels` times, each level from the one before (csrc/meshsubdiv.hip; trimesh.remesh.subdivide
+    and subdivide_loop, open3d's subdivide_midpoint and subdivide_loop on the CPU) -> Subdivided.  A level splits every
+    edge with two different ends (the rows of the EdgeTable, in its order: the new vertices follow the old ones in edge
+    order) and every face into four, (v0, m0, m2), (m0, v1, m1), (m2, m1, v2), (m0, m1, m2) with m_k on the edge from
+    corner k to the next: V + E vertices, 4 F faces, the parent's winding.  A face with a repeated vertex goes through the
+    templates of subdivide_to_edge and stays degenerate.
+    scheme="midpoint": a new vertex is (p_u + p_v) 0.5 and the old ones stay; the surface does not change.
+    scheme="loop": Loop's scheme with Warren's weights.  A new vertex on an edge with exactly two faces is
+    (p_u + p_v) 0.375 + (p_a + p_b) 0.125, a and b the opposite corners; on any other edge (a border, or three and more
+    faces: a crease) the midpoint.  An old vertex on an edge with three or more faces, one whose number of border edges
+    is neither 0 nor 2, and one without neighbours stay; one with two border edges moves to p 0.75 + (p_b0 + p_b1) 0.125;
+    any other moves to p (1 - n beta) + s beta with s the sum of its n neighbours in ascending index and beta = 3 / 16
+    for n = 3, else 3 / (8 n).  trimesh's subdivide_loop knows borders but no creases.
+    `attributes` [V, k] go through the weights of the positions column by column.  float64 inside, cast at the end;
+    no atomics, identical from run to run.  An empty mesh and levels = 0 return the input."""
+    levels = _count(levels, "levels")
+    if scheme not in _SUBDIVIDE_SCHEMES:
+        raise ValueError(f"scheme must be 'loop' or 'midpoint' (got {scheme!r})")
+    return _subdivide(verts, faces, attributes, _SUBDIVIDE_SCHEMES[scheme], None, levels, _info)
+
+
+def subdivide_to_edge(verts, faces, max_edge, max_rounds=32, attributes=None, _info=None):
+    """splits edges at their midpoints until none is longer than `max_edge` -> Subdivided.  A round marks the edges with
+    (dx dx + dy dy) + dz dz > max_edge max_edge in float64 (a NaN length is not marked), gives each a new vertex at its
+    midpoint and replaces every face by the template of its marked half-edges, in the parent's winding: none, the face;
+    one, on the half-edge a -> b opposite c: (a, m, c), (m, b, c); two, a -> b unmarked: (m1, c, m2) and the quad
+    a b m1 m2 along the shorter of its diagonals a-m1 and b-m2 (on a tie a-m1 exactly when a < b): (a, b, m1),
+    (a, m1, m2) or (a, b, m2), (b, m1, m2); three: the four faces of subdivide_mesh.  Marks are per edge, so the faces on
+    both sides split it and the mesh stays conforming; the surface does not change.  The rounds end when one marks
+    nothing or after `max_rounds` of them: then `converged` is False and `longest_edge` says where the mesh stands.  After
+    k rounds the longest edge is at most max_edge + (L - max_edge) / 2^k for an input whose longest is L (a diagonal of
+    the two-marked template is a median, at most half the sum of two sides).  trimesh's subdivide_to_size splits every
+    face in four until all edges are short.  One read-back per round; identical from run to run."""
+    max_edge = _finite(max_edge, "max_edge", positive=True)
+    max_rounds = _count(max_rounds, "max_rounds")
+    return _subdivide(verts, faces, attributes, 0, max_edge, max_rounds, _info)
 
 def ellipse_footprint(ksize):
     """OpenCV's MORPH_ELLIPSE structuring element of size ksize x ksize -> np.uint8 [ksize, ksize], restated from the

@@ -1,0 +1,48 @@
+"""CPU: the float64 kernels of csrc/meshsubdiv.hip compile without contracted multiply-adds, as
+tests/test_meshsmooth_asm.py checks for csrc/meshsmooth.hip: the fused instructions the gfx950 assembly holds belong to the
+expansion of the one division (Warren's 3 / (8 n)), so their count per kernel equals that of a build with contraction
+switched off for the whole translation unit."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.join(os.path.dirname(HERE), "neuraludf_amd")
+SRC = os.path.join(PKG, "csrc", "meshsubdiv.hip")
+KERNELS = {"sd_mark_kernel", "sd_odd_kernel", "sd_even_kernel", "sd_count_kernel", "sd_emit_kernel"}
+
+
+def _hipcc():
+    for c in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
+        if c and os.path.exists(c):
+            return c
+    pytest.skip("hipcc not found")
+
+
+def _per_kernel(tmp_path, extra):
+    out = tmp_path / ("sd%d.s" % len(extra))
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", SRC, "-o", str(out),
+           "-I", os.path.join(PKG, "csrc"), "-I", os.path.join(os.path.dirname(PKG), "include")] + extra
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    counts, cur = {}, None
+    for line in out.read_text().splitlines():
+        m = re.match(r"^(_Z\w+):", line)
+        if m:
+            cur = re.sub(r"^_Z\d+", "", m.group(1)).split("12NudfMeshTopo")[0]
+            counts[cur] = dict(fused=0, mul=0)
+        elif cur:
+            counts[cur]["fused"] += bool(re.search(r"\bv_fmac?_f64\b", line))
+            counts[cur]["mul"] += bool(re.search(r"\bv_mul_f64\b", line))
+    return counts
+
+
+def test_no_contracted_float64_multiply_add(tmp_path):
+    built = _per_kernel(tmp_path, [])
+    off = _per_kernel(tmp_path, ["-ffp-contract=off"])
+    assert KERNELS <= set(built), sorted(built)
+    for k in KERNELS:
+        assert built[k] == off[k], (k, built[k], off[k])
