@@ -23,6 +23,8 @@ SOURCES = ["nudf_api.hip", "gemm_f32_mfma.hip", "gemm_tn_f32_mfma.hip", "rays_em
 
 # the sources that decide what a kernel class reads and writes (bench.py `roofline.traffic_stale`: a PMC traffic file under
 # profiles/ is only as good as the kernel it was recorded on)
+_MESH_COMMON = ["csrc/f64_exact.h", "csrc/mesh_launch.h", "csrc/nudf_common.h", "../include/nudf.h"]   # every mesh file
+_CELL_INDEX = ["csrc/cell_index.h"]                        # the three that build or search the hashed grid
 KERNEL_SOURCES = {
     "mlp_chain": ["csrc/mlp_chain.hip", "csrc/mlp_chain_rows.hip", "csrc/mlp_chain_shared.h", "csrc/nudf_common.h",
                   "../include/nudf.h", "mlp.py"],
@@ -34,15 +36,15 @@ KERNEL_SOURCES = {
                        "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
     "isosurface": ["csrc/isosurface.hip", "csrc/mc_pipeline.h", "csrc/isosurface_cell.h", "csrc/meshudf_cell.h",
                    "csrc/mc_tables.inc", "csrc/nudf_common.h", "../include/nudf.h"],
-    "pointcloud": ["csrc/pointcloud.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshtopo": ["csrc/meshtopo.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshorient": ["csrc/meshorient.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshsimplify": ["csrc/meshsimplify.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshdist": ["csrc/meshdist.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshray": ["csrc/meshray.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshsmooth": ["csrc/meshsmooth.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshsubdiv": ["csrc/meshsubdiv.hip", "csrc/nudf_common.h", "../include/nudf.h"],
-    "meshraster": ["csrc/meshraster.hip", "csrc/meshraster_pixel.h", "csrc/nudf_common.h", "../include/nudf.h"],
+    "pointcloud": ["csrc/pointcloud.hip", *_CELL_INDEX, *_MESH_COMMON],
+    "meshtopo": ["csrc/meshtopo.hip", *_MESH_COMMON],
+    "meshorient": ["csrc/meshorient.hip", *_MESH_COMMON],
+    "meshsimplify": ["csrc/meshsimplify.hip", *_MESH_COMMON],
+    "meshdist": ["csrc/meshdist.hip", *_CELL_INDEX, *_MESH_COMMON],
+    "meshray": ["csrc/meshray.hip", *_CELL_INDEX, *_MESH_COMMON],
+    "meshsmooth": ["csrc/meshsmooth.hip", *_MESH_COMMON],
+    "meshsubdiv": ["csrc/meshsubdiv.hip", *_MESH_COMMON],
+    "meshraster": ["csrc/meshraster.hip", "csrc/meshraster_pixel.h", *_MESH_COMMON],
 }
 
 

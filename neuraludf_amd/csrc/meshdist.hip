@@ -6,77 +6,20 @@
 //                   of the counts.  The caller sorts by key and builds the cell table and its hash with nudf_pc_cells;
 //   closest      -- one thread per query (cell-sorted): the closest point of the mesh by Chebyshev rings of cells, up to
 //                   `bound`: distance, face, point and barycentric weights.
-// The cell key, the hash and the ring search with its stop tests are those of pointcloud.hip (the two files keep the same
-// helpers: a cell coordinate must be the same number in both).  The ring stop holds for faces as it does for points: a
-// face is listed in every cell its box touches, so a face not met in the rings <= k has its whole box, and with it every
-// one of its points, outside the cube of those rings.
+// The cell key, the hash and the ring walk with its stop tests are those of cell_index.h, shared with pointcloud.hip,
+// whose kernels build the table.  The ring stop holds for faces as it does for points: a face is listed in every cell
+// its box touches, so a face not met in the rings <= k has its whole box, and with it every one of its points, outside
+// the cube of those rings.
 // The per-face rule (restated in tests/meshdist_ref.py) is float64 with no contraction: products and sums
-// go through mul / add / sub, plain operators under the pragma; the only fused instructions left are inside the correctly
-// rounded __ddiv_rn / __dsqrt_rn expansions (tests/test_meshdist_asm.py).
+// go through mul / add / sub of f64_exact.h, plain operators under the pragma; the only fused instructions left are
+// inside the correctly rounded __ddiv_rn / __dsqrt_rn expansions (tests/test_meshdist_asm.py).
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
-#include "../../include/nudf.h"
+#include "cell_index.h"
+#include "mesh_launch.h"
 
 #define MD_BLOCK 256
-#define PC_AXIS_BITS 21
-#define PC_AXIS_MAX ((1 << PC_AXIS_BITS) - 1)
-#define PC_EMPTY (-1LL)
-#define PC_CELL_MARGIN 0x1p-20          // pointcloud.hip: the rounding allowance of a cell coordinate
 #define MD_MAX_CAP (1LL << 40)          // largest reference count a caller may accept: F cap stays below 2^63
-
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
-
-__device__ __forceinline__ double dot3(double x, double y, double z) {
-  return add(add(mul(x, x), mul(y, y)), mul(z, z));
-}
-
-struct V3 {
-  double x, y, z;
-};
-
-__device__ __forceinline__ V3 vsub(const V3& a, const V3& b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-__device__ __forceinline__ double vdot(const V3& a, const V3& b) {
-  return add(add(mul(a.x, b.x), mul(a.y, b.y)), mul(a.z, b.z));
-}
-__device__ __forceinline__ V3 vcross(const V3& a, const V3& b) {          // np.cross order
-  return {sub(mul(a.y, b.z), mul(a.z, b.y)), sub(mul(a.z, b.x), mul(a.x, b.z)), sub(mul(a.x, b.y), mul(a.y, b.x))};
-}
-__device__ __forceinline__ V3 vload(const double* p) { return {p[0], p[1], p[2]}; }
-
-// ---- the cell index (as in pointcloud.hip) ------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t cell_coord(double x, double origin, double cell) {
-  double u = floor(__ddiv_rn(sub(x, origin), cell));
-  u = u < -0x1p30 ? -0x1p30 : (u > 0x1p30 ? 0x1p30 : u);
-  return (int64_t)u;
-}
-
-__device__ __forceinline__ int64_t pack_key(int64_t x, int64_t y, int64_t z) {
-  return (x << (2 * PC_AXIS_BITS)) | (y << PC_AXIS_BITS) | z;
-}
-
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {    // the murmur3 64-bit finaliser
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-__device__ int64_t cell_row(const NudfPointCloud& a, int64_t key) {
-  const uint64_t mask = (uint64_t)a.hash_cap - 1;
-  uint64_t h = hash_mix((uint64_t)key) & mask;
-  for (int64_t probe = 0; probe < a.hash_cap; ++probe) {
-    const int64_t k = a.hash_key[h];
-    if (k == key) return a.hash_row[h];
-    if (k == PC_EMPTY) return -1;
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
 
 // ---- binning: a face goes into every cell its box touches ------------------------------------------------------------------
 struct CellBox {
@@ -95,7 +38,7 @@ __device__ bool face_cells(const NudfPointCloud& a, int64_t f, CellBox& b) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const double v = a.verts[3 * fi[k] + x];
-      if (!(fabs(v) < __longlong_as_double(0x7ff0000000000000LL))) return false;
+      if (!is_finite(v)) return false;
       int64_t c = cell_coord(v, a.origin[x], a.cell);
       c = c < 0 ? 0 : (c >= a.grid[x] ? a.grid[x] - 1 : c);          // the grid holds every usable vertex: a safety net
       lo = (k == 0 || c < lo) ? c : lo;
@@ -205,7 +148,7 @@ __device__ __forceinline__ Cand face_candidate(const NudfPointCloud& a, int64_t 
 #undef MD_ORDER
   const V3 n = vcross(vsub(B, A), vsub(C, A));
   const double nn = dot3(n.x, n.y, n.z);
-  if (nn > 0.0 && nn < __longlong_as_double(0x7ff0000000000000LL)) {
+  if (positive_finite(nn)) {
     const double sa = vdot(vcross(vsub(C, B), vsub(p, B)), n);
     const double sb = vdot(vcross(vsub(A, C), vsub(p, C)), n);
     const double sc = vdot(vcross(vsub(B, A), vsub(p, A)), n);
@@ -246,53 +189,21 @@ __global__ __launch_bounds__(MD_BLOCK) void pc_closest_kernel(NudfPointCloud a) 
   const double inf = __longlong_as_double(0x7ff0000000000000LL);
   double best_d2 = inf;
   int64_t best_f = -1;
-  const double bx = fmax(fmax(sub(a.box_lo[0], p.x), sub(p.x, a.box_hi[0])), 0.0);
-  const double by = fmax(fmax(sub(a.box_lo[1], p.y), sub(p.y, a.box_hi[1])), 0.0);
-  const double bz = fmax(fmax(sub(a.box_lo[2], p.z), sub(p.z, a.box_hi[2])), 0.0);
-  if (!(dot3(bx, by, bz) > a.box_bound2)) {
-    const int64_t c[3] = {cell_coord(p.x, a.origin[0], a.cell), cell_coord(p.y, a.origin[1], a.cell),
-                          cell_coord(p.z, a.origin[2], a.cell)};
-    int64_t k = 0;
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      const int64_t off = c[x] < 0 ? -c[x] : (c[x] >= a.grid[x] ? c[x] - (a.grid[x] - 1) : 0);
-      k = off > k ? off : k;
-    }
-    auto visit = [&](int64_t x, int64_t y, int64_t z) {
-      const int64_t row = cell_row(a, pack_key(x, y, z));
-      if (row < 0) return;
-      const int64_t b = a.cell_start[row], e = b + a.cell_count[row];
-      for (int64_t s = b; s < e; ++s) {
-        const int64_t f = a.md_cell_face[s];
-        if (f == best_f || f < 0 || f >= a.n_faces) continue;   // met again in another cell: the same pair
-        const double d2 = face_candidate(a, f, p).d2;
-        if (d2 < best_d2 || (d2 == best_d2 && f < best_f)) {
-          best_d2 = d2;
-          best_f = f;
-        }
+  auto visit = [&](int64_t x, int64_t y, int64_t z) {
+    const int64_t row = cell_row(a, pack_key(x, y, z));
+    if (row < 0) return;
+    const int64_t b = a.cell_start[row], e = b + a.cell_count[row];
+    for (int64_t s = b; s < e; ++s) {
+      const int64_t f = a.md_cell_face[s];
+      if (f == best_f || f < 0 || f >= a.n_faces) continue;   // met again in another cell: the same pair
+      const double d2 = face_candidate(a, f, p).d2;
+      if (d2 < best_d2 || (d2 == best_d2 && f < best_f)) {
+        best_d2 = d2;
+        best_f = f;
       }
-    };
-    for (;; ++k) {
-      const int64_t x0 = c[0] - k < 0 ? 0 : c[0] - k, x1 = c[0] + k >= a.grid[0] ? a.grid[0] - 1 : c[0] + k;
-      const int64_t y0 = c[1] - k < 0 ? 0 : c[1] - k, y1 = c[1] + k >= a.grid[1] ? a.grid[1] - 1 : c[1] + k;
-      const int64_t z0 = c[2] - k < 0 ? 0 : c[2] - k, z1 = c[2] + k >= a.grid[2] ? a.grid[2] - 1 : c[2] + k;
-      for (int64_t x = x0; x <= x1; ++x) {
-        for (int64_t y = y0; y <= y1; ++y) {
-          if (x == c[0] - k || x == c[0] + k || y == c[1] - k || y == c[1] + k) {
-            for (int64_t z = z0; z <= z1; ++z) visit(x, y, z);
-          } else {                                   // k >= 1: only the ring's two z faces are new in this column
-            if (c[2] - k >= 0) visit(x, y, c[2] - k);
-            if (c[2] + k < a.grid[2]) visit(x, y, c[2] + k);
-          }
-        }
-      }
-      const double reach = mul(sub((double)k, PC_CELL_MARGIN), a.cell);
-      if (__dsqrt_rn(best_d2) < reach || reach > a.bound) break;
-      if (c[0] - k <= 0 && c[1] - k <= 0 && c[2] - k <= 0 && c[0] + k >= a.grid[0] - 1 && c[1] + k >= a.grid[1] - 1 &&
-          c[2] + k >= a.grid[2] - 1)
-        break;                                             // every cell has been seen
     }
-  }
+  };
+  ring_walk(a, p.x, p.y, p.z, visit, [&] { return __dsqrt_rn(best_d2); });
   const double nan = __longlong_as_double(0x7ff8000000000000LL);
   double dist = __dsqrt_rn(best_d2);
   Cand w;
@@ -313,27 +224,6 @@ __global__ __launch_bounds__(MD_BLOCK) void pc_closest_kernel(NudfPointCloud a) 
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n) { return (unsigned)((n + MD_BLOCK - 1) / MD_BLOCK); }
-
-static int refuse(const char* entry, const char* why) {
-  char msg[192];
-  snprintf(msg, sizeof msg, "%s: %s", entry, why);
-  nudf_set_error(msg, hipErrorInvalidValue);          // copies the text
-  return (int)hipErrorInvalidValue;
-}
-
-static bool grid_ok(const NudfPointCloud& a) {
-  for (int x = 0; x < 3; ++x)
-    if (a.grid[x] < 1 || a.grid[x] > PC_AXIS_MAX + 1) return false;
-  return true;
-}
-
-static bool origin_ok(const NudfPointCloud& a) {
-  for (int x = 0; x < 3; ++x)
-    if (!(a.origin[x] - a.origin[x] == 0.0)) return false;
-  return true;
-}
-
 #define MD_2_31 (1LL << 31)
 
 // what the two binning entry points share; NULL when the descriptor is in order
@@ -353,18 +243,14 @@ extern "C" int nudf_pc_tribin_count(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
   if (a.n_faces <= 0) return 0;
   if (const char* why = tribin_check(a, false)) return refuse("nudf_pc_tribin_count", why);
-  hipLaunchKernelGGL(pc_tribin_count_kernel, dim3(blocks(a.n_faces)), dim3(MD_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_tribin_count");
-  return 0;
+  MESH_LAUNCH(pc_tribin_count_kernel, a.n_faces, MD_BLOCK, MD_BLOCK, "nudf_pc_tribin_count");
 }
 
 extern "C" int nudf_pc_tribin_emit(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
   if (a.n_faces <= 0) return 0;
   if (const char* why = tribin_check(a, true)) return refuse("nudf_pc_tribin_emit", why);
-  hipLaunchKernelGGL(pc_tribin_emit_kernel, dim3(blocks(a.n_faces)), dim3(MD_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_tribin_emit");
-  return 0;
+  MESH_LAUNCH(pc_tribin_emit_kernel, a.n_faces, MD_BLOCK, MD_BLOCK, "nudf_pc_tribin_emit");
 }
 
 extern "C" int nudf_pc_closest(const NudfPointCloud* args, void* stream) {
@@ -383,7 +269,5 @@ extern "C" int nudf_pc_closest(const NudfPointCloud* args, void* stream) {
   if (!a.verts || !a.faces || !a.query || !a.query_idx || !a.cell_start || !a.cell_count || !a.hash_key || !a.hash_row ||
       !a.md_cell_face || !a.dist || !a.idx || !a.md_point || !a.md_bary)
     return refuse(entry, "NULL buffer");
-  hipLaunchKernelGGL(pc_closest_kernel, dim3(blocks(a.n_query)), dim3(MD_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_closest");
-  return 0;
+  MESH_LAUNCH(pc_closest_kernel, a.n_query, MD_BLOCK, MD_BLOCK, entry);
 }

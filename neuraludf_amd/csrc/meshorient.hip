@@ -16,18 +16,15 @@
 // that follows from the edges seen so far: in an orientable component all of them agree with its one solution, whatever
 // the order in which the atomics land, and in any component the fixed point of the labels is the smallest face index.
 // No kernel waits on another workgroup.  The float64 expressions follow the numpy restatement (tests/meshorient_ref.py)
-// operation by operation: products and sums go through mul / add / sub under the pragma, as in meshtopo.hip.
+// operation by operation: products and sums go through mul / add / sub of f64_exact.h under the pragma.
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
+#include "f64_exact.h"
+#include "mesh_launch.h"
 #include "../../include/nudf.h"
 
 #define MO_BLOCK 256
 #define MO_WAVE 64
-
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
 
 // ---- (a) parity union-find ---------------------------------------------------------------------------------------------
 // root of face f and, in `parity`, whether f and the root need opposite flips
@@ -166,54 +163,49 @@ __global__ __launch_bounds__(MO_BLOCK) void mo_normals_kernel(NudfMeshOrient a) 
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-static int refuse(const char* where) {
-  nudf_set_error(where, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 static bool sizes_ok(const NudfMeshOrient& a) {
   return a.n_faces >= 0 && a.n_faces < (1LL << 36) && a.n_verts >= 0 && a.n_verts < (1LL << 31) && a.n_medges >= 0 &&
          a.n_medges <= 3 * a.n_faces / 2 && a.n_comps >= 0 && a.n_comps <= a.n_faces;
 }
 
-#define MO_LAUNCH(kernel, n, per_block, name)                                                             \
-  hipLaunchKernelGGL(kernel, dim3(blocks(n, per_block)), dim3(MO_BLOCK), 0, (hipStream_t)stream, a);      \
-  NUDF_CHECK_LAUNCH(name);                                                                                \
-  return 0
+#define MO_SIZES_MEDGES "bad sizes (n_verts must be < 2^31, n_medges <= 3 n_faces / 2)"
 
 extern "C" int nudf_meshorient_hook(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshorient_hook: bad sizes (n_verts must be < 2^31, n_medges <= 3 n_faces / 2)");
+  const char* const entry = "nudf_meshorient_hook";
+  if (!sizes_ok(a)) return refuse(entry, MO_SIZES_MEDGES);
   if (a.n_medges <= 0) return 0;
-  MO_LAUNCH(mo_hook_kernel, a.n_medges, MO_BLOCK, "nudf_meshorient_hook");
+  MESH_LAUNCH(mo_hook_kernel, a.n_medges, MO_BLOCK, MO_BLOCK, entry);
 }
 
 extern "C" int nudf_meshorient_jump(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshorient_jump: bad sizes (n_verts must be < 2^31, n_medges <= 3 n_faces / 2)");
+  const char* const entry = "nudf_meshorient_jump";
+  if (!sizes_ok(a)) return refuse(entry, MO_SIZES_MEDGES);
   if (a.n_faces <= 0) return 0;
-  MO_LAUNCH(mo_jump_kernel, a.n_faces, MO_BLOCK, "nudf_meshorient_jump");
+  MESH_LAUNCH(mo_jump_kernel, a.n_faces, MO_BLOCK, MO_BLOCK, entry);
 }
 
 extern "C" int nudf_meshorient_check(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshorient_check: bad sizes (n_verts must be < 2^31, n_medges <= 3 n_faces / 2)");
+  const char* const entry = "nudf_meshorient_check";
+  if (!sizes_ok(a)) return refuse(entry, MO_SIZES_MEDGES);
   if (a.n_medges <= 0) return 0;
-  MO_LAUNCH(mo_check_kernel, a.n_medges, MO_BLOCK, "nudf_meshorient_check");
+  MESH_LAUNCH(mo_check_kernel, a.n_medges, MO_BLOCK, MO_BLOCK, entry);
 }
 
 extern "C" int nudf_meshorient_outward(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshorient_outward: bad sizes (n_verts must be < 2^31, n_comps <= n_faces)");
+  const char* const entry = "nudf_meshorient_outward";
+  if (!sizes_ok(a)) return refuse(entry, "bad sizes (n_verts must be < 2^31, n_comps <= n_faces)");
   if (a.n_comps <= 0) return 0;
-  MO_LAUNCH(mo_outward_kernel, a.n_comps, MO_BLOCK / MO_WAVE, "nudf_meshorient_outward");
+  MESH_LAUNCH(mo_outward_kernel, a.n_comps, MO_BLOCK, MO_BLOCK / MO_WAVE, entry);
 }
 
 extern "C" int nudf_meshorient_normals(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshorient_normals: bad sizes (n_verts must be < 2^31)");
+  const char* const entry = "nudf_meshorient_normals";
+  if (!sizes_ok(a)) return refuse(entry, "bad sizes (n_verts must be < 2^31)");
   if (a.n_verts <= 0) return 0;
-  MO_LAUNCH(mo_normals_kernel, a.n_verts, MO_BLOCK, "nudf_meshorient_normals");
+  MESH_LAUNCH(mo_normals_kernel, a.n_verts, MO_BLOCK, MO_BLOCK, entry);
 }

@@ -12,10 +12,11 @@
 // bits, so a 64-bit unsigned atomicMin keeps the nearest face and, among equal depths, the smallest face index -- whatever
 // the order in which the atomics land.  No floating-point atomics, no kernel waits on another workgroup.  The float64
 // expressions follow the numpy restatement (tests/meshraster_ref.py) operation by operation: products and sums go through
-// mul / add / sub under the pragma, as in meshorient.hip.
+// mul / add / sub of f64_exact.h under the pragma.
 #pragma clang fp contract(off)
 
 #include "meshraster_pixel.h"
+#include "mesh_launch.h"
 
 #define MR_BLOCK 256
 #define MR_WAVE 64
@@ -134,31 +135,31 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_colour_kernel(NudfMeshRaster a) {
     mr_project(a.proj + 12 * view, p, s);
     const double fx0 = floor(s[0]), fy0 = floor(s[1]);
     // (vis is the caller's: the clamps below keep every tap inside the image whatever the projection is, NaN included)
-    const double fx = mr_sub(s[0], fx0), fy = mr_sub(s[1], fy0);
+    const double fx = sub(s[0], fx0), fy = sub(s[1], fy0);
     const double wmax = (double)(a.W - 1), hmax = (double)(a.H - 1);
-    const int64_t xa = (int64_t)fmin(fmax(fx0, 0.0), wmax), xb = (int64_t)fmin(fmax(mr_add(fx0, 1.0), 0.0), wmax);
-    const int64_t ya = (int64_t)fmin(fmax(fy0, 0.0), hmax), yb = (int64_t)fmin(fmax(mr_add(fy0, 1.0), 0.0), hmax);
+    const int64_t xa = (int64_t)fmin(fmax(fx0, 0.0), wmax), xb = (int64_t)fmin(fmax(add(fx0, 1.0), 0.0), wmax);
+    const int64_t ya = (int64_t)fmin(fmax(fy0, 0.0), hmax), yb = (int64_t)fmin(fmax(add(fy0, 1.0), 0.0), hmax);
     const int64_t base = view * a.H * (int64_t)a.W;
     const int64_t p00 = base + ya * a.W + xa, p10 = base + ya * a.W + xb;
     const int64_t p01 = base + yb * a.W + xa, p11 = base + yb * a.W + xb;
-    const double gx = mr_sub(1.0, fx), gy = mr_sub(1.0, fy);
-    const double w00 = mr_mul(gx, gy), w10 = mr_mul(fx, gy), w01 = mr_mul(gx, fy), w11 = mr_mul(fx, fy);
+    const double gx = sub(1.0, fx), gy = sub(1.0, fy);
+    const double w00 = mul(gx, gy), w10 = mul(fx, gy), w01 = mul(gx, fy), w11 = mul(fx, fy);
     double g = 1.0;
     if (a.normals) {
       const double* cam = a.cam_pos + 3 * view;
       const double* nv = a.normals + 3 * v;
-      const double dx = mr_sub(cam[0], p[0]), dy = mr_sub(cam[1], p[1]), dz = mr_sub(cam[2], p[2]);
-      const double len = __dsqrt_rn(mr_add(mr_add(mr_mul(dx, dx), mr_mul(dy, dy)), mr_mul(dz, dz)));
-      const double dot = mr_add(mr_add(mr_mul(nv[0], __ddiv_rn(dx, len)), mr_mul(nv[1], __ddiv_rn(dy, len))),
-                                mr_mul(nv[2], __ddiv_rn(dz, len)));
+      const double dx = sub(cam[0], p[0]), dy = sub(cam[1], p[1]), dz = sub(cam[2], p[2]);
+      const double len = __dsqrt_rn(add(add(mul(dx, dx), mul(dy, dy)), mul(dz, dz)));
+      const double dot = add(add(mul(nv[0], __ddiv_rn(dx, len)), mul(nv[1], __ddiv_rn(dy, len))),
+                                mul(nv[2], __ddiv_rn(dz, len)));
       g = pow(fabs(dot), a.power);
     }
     for (int c = 0; c < 3; ++c) {
-      const double col = mr_add(mr_add(mr_mul(w00, mr_tap(a, p00, c)), mr_mul(w10, mr_tap(a, p10, c))),
-                                mr_add(mr_mul(w01, mr_tap(a, p01, c)), mr_mul(w11, mr_tap(a, p11, c))));
-      sc[c] = mr_add(sc[c], mr_mul(g, col));
+      const double col = add(add(mul(w00, mr_tap(a, p00, c)), mul(w10, mr_tap(a, p10, c))),
+                                add(mul(w01, mr_tap(a, p01, c)), mul(w11, mr_tap(a, p11, c))));
+      sc[c] = add(sc[c], mul(g, col));
     }
-    sw = mr_add(sw, g);
+    sw = add(sw, g);
     ++n;
   }
   const bool ok = sw > 0.0 && sw < HUGE_VAL;
@@ -169,13 +170,6 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_colour_kernel(NudfMeshRaster a) {
 // ---- launchers --------------------------------------------------------------------------------------------------------
 #define MR_MAX_THREADS (1LL << 38)                   // one-dimensional grids of MR_BLOCK threads: < 2^31 blocks
 
-static unsigned blocks(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-static int refuse(const char* where) {
-  nudf_set_error(where, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 static bool sizes_ok(const NudfMeshRaster& a) {
   if (a.n_faces < 0 || a.n_faces >= (1LL << 31) || a.n_verts < 0 || a.n_verts >= (1LL << 31)) return false;
   if (a.n_views < 0 || a.H < 0 || a.W < 0 || a.n_entries < 0) return false;
@@ -185,70 +179,72 @@ static bool sizes_ok(const NudfMeshRaster& a) {
   return a.n_entries <= a.n_views * a.n_faces;
 }
 
-#define MR_BAD_SIZES(name) \
-  name ": bad sizes (n_faces, n_verts and H * W must be < 2^31, n_views * H * W, n_views * n_faces and n_views * n_verts " \
-       "<= 2^38, n_entries <= n_views * n_faces, nothing negative)"
-
-#define MR_LAUNCH(kernel, n, per_block, name)                                                             \
-  hipLaunchKernelGGL(kernel, dim3(blocks(n, per_block)), dim3(MR_BLOCK), 0, (hipStream_t)stream, a);      \
-  NUDF_CHECK_LAUNCH(name);                                                                                \
-  return 0
+#define MR_BAD_SIZES \
+  "bad sizes (n_faces, n_verts and H * W must be < 2^31, n_views * H * W, n_views * n_faces and n_views * n_verts " \
+  "<= 2^38, n_entries <= n_views * n_faces, nothing negative)"
 
 // an image is needed as soon as there is something to do per view
-#define MR_NEED_IMAGE(name) \
-  if (a.H < 1 || a.W < 1) return refuse(name ": H and W must be >= 1")
+#define MR_NEED_IMAGE \
+  if (a.H < 1 || a.W < 1) return refuse(entry, "H and W must be >= 1")
 
 extern "C" int nudf_meshraster_project(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_project"));
+  const char* const entry = "nudf_meshraster_project";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_views <= 0 || a.n_verts <= 0) return 0;
-  MR_LAUNCH(mr_project_kernel, a.n_views * a.n_verts, MR_BLOCK, "nudf_meshraster_project");
+  MESH_LAUNCH(mr_project_kernel, a.n_views * a.n_verts, MR_BLOCK, MR_BLOCK, entry);
 }
 
 extern "C" int nudf_meshraster_bounds(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_bounds"));
+  const char* const entry = "nudf_meshraster_bounds";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_views <= 0 || a.n_faces <= 0) return 0;
-  MR_NEED_IMAGE("nudf_meshraster_bounds");
-  MR_LAUNCH(mr_bounds_kernel, a.n_views * a.n_faces, MR_BLOCK, "nudf_meshraster_bounds");
+  MR_NEED_IMAGE;
+  MESH_LAUNCH(mr_bounds_kernel, a.n_views * a.n_faces, MR_BLOCK, MR_BLOCK, entry);
 }
 
 extern "C" int nudf_meshraster_draw_small(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_draw_small"));
+  const char* const entry = "nudf_meshraster_draw_small";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_entries <= 0) return 0;
-  MR_NEED_IMAGE("nudf_meshraster_draw_small");
-  MR_LAUNCH(mr_draw_small_kernel, a.n_entries, MR_BLOCK, "nudf_meshraster_draw_small");
+  MR_NEED_IMAGE;
+  MESH_LAUNCH(mr_draw_small_kernel, a.n_entries, MR_BLOCK, MR_BLOCK, entry);
 }
 
 extern "C" int nudf_meshraster_draw_large(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_draw_large"));
+  const char* const entry = "nudf_meshraster_draw_large";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_entries <= 0) return 0;
-  MR_NEED_IMAGE("nudf_meshraster_draw_large");
-  MR_LAUNCH(mr_draw_large_kernel, a.n_entries, MR_BLOCK / MR_WAVE, "nudf_meshraster_draw_large");
+  MR_NEED_IMAGE;
+  MESH_LAUNCH(mr_draw_large_kernel, a.n_entries, MR_BLOCK, MR_BLOCK / MR_WAVE, entry);
 }
 
 extern "C" int nudf_meshraster_resolve(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_resolve"));
+  const char* const entry = "nudf_meshraster_resolve";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_views <= 0) return 0;
-  MR_NEED_IMAGE("nudf_meshraster_resolve");
-  MR_LAUNCH(mr_resolve_kernel, (int64_t)a.n_views * a.H * a.W, MR_BLOCK, "nudf_meshraster_resolve");
+  MR_NEED_IMAGE;
+  MESH_LAUNCH(mr_resolve_kernel, (int64_t)a.n_views * a.H * a.W, MR_BLOCK, MR_BLOCK, entry);
 }
 
 extern "C" int nudf_meshraster_visible(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_visible"));
+  const char* const entry = "nudf_meshraster_visible";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_views <= 0 || a.n_verts <= 0) return 0;
-  MR_NEED_IMAGE("nudf_meshraster_visible");
-  MR_LAUNCH(mr_visible_kernel, a.n_views * a.n_verts, MR_BLOCK, "nudf_meshraster_visible");
+  MR_NEED_IMAGE;
+  MESH_LAUNCH(mr_visible_kernel, a.n_views * a.n_verts, MR_BLOCK, MR_BLOCK, entry);
 }
 
 extern "C" int nudf_meshraster_colour(const NudfMeshRaster* args, void* stream) {
   const NudfMeshRaster& a = *args;
-  if (!sizes_ok(a)) return refuse(MR_BAD_SIZES("nudf_meshraster_colour"));
+  const char* const entry = "nudf_meshraster_colour";
+  if (!sizes_ok(a)) return refuse(entry, MR_BAD_SIZES);
   if (a.n_verts <= 0) return 0;
-  if (a.n_views > 0) { MR_NEED_IMAGE("nudf_meshraster_colour"); }
-  MR_LAUNCH(mr_colour_kernel, a.n_verts, MR_BLOCK, "nudf_meshraster_colour");
+  if (a.n_views > 0) { MR_NEED_IMAGE; }
+  MESH_LAUNCH(mr_colour_kernel, a.n_verts, MR_BLOCK, MR_BLOCK, entry);
 }

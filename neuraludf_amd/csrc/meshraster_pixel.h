@@ -1,30 +1,26 @@
 // The per-face and per-pixel functions of the rasteriser (csrc/meshraster.hip), shared by draw_small, draw_large and
 // resolve so that the three evaluate the same float64 expressions in the same order (include/nudf.h NudfMeshRaster,
-// tests/meshraster_ref.py).  The including translation unit switches contraction off.
+// tests/meshraster_ref.py).  The including translation unit switches contraction off (f64_exact.h).
 #pragma once
+#include "f64_exact.h"
 #include "nudf_common.h"
 #include "../../include/nudf.h"
 
 #define MR_EMPTY 0xffffffffffffffffULL
 
-__device__ __forceinline__ double mr_mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double mr_add(double x, double y) { return x + y; }
-__device__ __forceinline__ double mr_sub(double x, double y) { return x - y; }
-__device__ __forceinline__ bool mr_finite(double x) { return fabs(x) < HUGE_VAL; }      // false for NaN
-
 // q = P p of view `view`: (q.x / q.z, q.y / q.z, q.z)
 __device__ __forceinline__ void mr_project(const double* P, const double* p, double* out) {
   const double x = p[0], y = p[1], z = p[2];
-  const double qx = mr_add(mr_add(mr_add(mr_mul(P[0], x), mr_mul(P[1], y)), mr_mul(P[2], z)), P[3]);
-  const double qy = mr_add(mr_add(mr_add(mr_mul(P[4], x), mr_mul(P[5], y)), mr_mul(P[6], z)), P[7]);
-  const double qz = mr_add(mr_add(mr_add(mr_mul(P[8], x), mr_mul(P[9], y)), mr_mul(P[10], z)), P[11]);
+  const double qx = add(add(add(mul(P[0], x), mul(P[1], y)), mul(P[2], z)), P[3]);
+  const double qy = add(add(add(mul(P[4], x), mul(P[5], y)), mul(P[6], z)), P[7]);
+  const double qz = add(add(add(mul(P[8], x), mul(P[9], y)), mul(P[10], z)), P[11]);
   out[0] = __ddiv_rn(qx, qz);
   out[1] = __ddiv_rn(qy, qz);
   out[2] = qz;
 }
 
 __device__ __forceinline__ bool mr_valid(const double* s) {
-  return mr_finite(s[0]) && mr_finite(s[1]) && mr_finite(s[2]) && s[2] > 0.0;
+  return is_finite(s[0]) && is_finite(s[1]) && is_finite(s[2]) && s[2] > 0.0;
 }
 
 // a face in one view: its three screen vertices and its pixel box, clamped to the image
@@ -46,9 +42,9 @@ __device__ __forceinline__ bool mr_face(const NudfMeshRaster& a, int64_t view, i
   t->x0 = s0[0], t->y0 = s0[1], t->z0 = s0[2];
   t->x1 = s1[0], t->y1 = s1[1], t->z1 = s1[2];
   t->x2 = s2[0], t->y2 = s2[1], t->z2 = s2[2];
-  const double area = mr_sub(mr_mul(mr_sub(t->x1, t->x0), mr_sub(t->y2, t->y0)),
-                             mr_mul(mr_sub(t->x2, t->x0), mr_sub(t->y1, t->y0)));
-  if (!mr_finite(area) || area == 0.0) return false;
+  const double area = sub(mul(sub(t->x1, t->x0), sub(t->y2, t->y0)),
+                             mul(sub(t->x2, t->x0), sub(t->y1, t->y0)));
+  if (!is_finite(area) || area == 0.0) return false;
   // the clamps are taken in float64: the screen coordinates are finite but need not fit an integer
   const double xlo = fmax(ceil(fmin(fmin(t->x0, t->x1), t->x2)), 0.0);
   const double xhi = fmin(floor(fmax(fmax(t->x0, t->x1), t->x2)), (double)(a.W - 1));
@@ -63,19 +59,19 @@ __device__ __forceinline__ bool mr_face(const NudfMeshRaster& a, int64_t view, i
 // the per-pixel function: whether the face covers (px, py) and, where it does, the barycentrics and the depth
 __device__ __forceinline__ bool mr_pixel(const MrFace& t, int32_t px, int32_t py, double* b, double* z) {
   const double x = (double)px, y = (double)py;
-  const double ax = mr_sub(t.x0, x), ay = mr_sub(t.y0, y);
-  const double bx = mr_sub(t.x1, x), by = mr_sub(t.y1, y);
-  const double cx = mr_sub(t.x2, x), cy = mr_sub(t.y2, y);
-  const double w0 = mr_sub(mr_mul(bx, cy), mr_mul(cx, by));
-  const double w1 = mr_sub(mr_mul(cx, ay), mr_mul(ax, cy));
-  const double w2 = mr_sub(mr_mul(ax, by), mr_mul(bx, ay));
+  const double ax = sub(t.x0, x), ay = sub(t.y0, y);
+  const double bx = sub(t.x1, x), by = sub(t.y1, y);
+  const double cx = sub(t.x2, x), cy = sub(t.y2, y);
+  const double w0 = sub(mul(bx, cy), mul(cx, by));
+  const double w1 = sub(mul(cx, ay), mul(ax, cy));
+  const double w2 = sub(mul(ax, by), mul(bx, ay));
   if (!((w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0))) return false;
-  const double s = mr_add(mr_add(w0, w1), w2);
-  if (!mr_finite(s) || s == 0.0) return false;
+  const double s = add(add(w0, w1), w2);
+  if (!is_finite(s) || s == 0.0) return false;
   b[0] = __ddiv_rn(w0, s);
   b[1] = __ddiv_rn(w1, s);
   b[2] = __ddiv_rn(w2, s);
-  *z = __ddiv_rn(1.0, mr_add(mr_add(__ddiv_rn(b[0], t.z0), __ddiv_rn(b[1], t.z1)), __ddiv_rn(b[2], t.z2)));
+  *z = __ddiv_rn(1.0, add(add(__ddiv_rn(b[0], t.z0), __ddiv_rn(b[1], t.z1)), __ddiv_rn(b[2], t.z2)));
   return true;
 }
 

@@ -4,70 +4,23 @@
 //              table that MeshIndex built for meshdist.hip (every face listed in every cell its box touches) and applies
 //              the per-(ray, face) rule to the faces of the cells it visits.  Three modes: the first hit (smallest
 //              (t, face)), any hit (early exit), the number of faces crossed.
-// The cell key, the hash and PC_CELL_MARGIN are those of pointcloud.hip / meshdist.hip (the three files keep the same
-// helpers: a cell coordinate must be the same number in all of them).
+// The cell key, the hash and PC_CELL_MARGIN are those of cell_index.h, shared with pointcloud.hip and meshdist.hip, whose
+// kernels build the table.
 // The rule (restated in tests/meshray_ref.py) is float64 with no contraction: products and sums go through
-// mul / add / sub, plain operators under the pragma; the only fused instructions left are inside the correctly rounded
-// __ddiv_rn expansion.  The walk decides which faces are looked at, never what a face answers: it is conservative, so the
-// result depends neither on the cell size nor on the order of traversal.
+// mul / add / sub of f64_exact.h, plain operators under the pragma; the only fused instructions left are inside the
+// correctly rounded __ddiv_rn expansion.  The walk decides which faces are looked at, never what a face answers: it is
+// conservative, so the result depends neither on the cell size nor on the order of traversal.
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
-#include "../../include/nudf.h"
+#include "cell_index.h"
+#include "mesh_launch.h"
 
 #define MR_BLOCK 256
-#define PC_AXIS_BITS 21
-#define PC_AXIS_MAX ((1 << PC_AXIS_BITS) - 1)
-#define PC_EMPTY (-1LL)
-#define PC_CELL_MARGIN 0x1p-20          // pointcloud.hip: the rounding allowance of a cell coordinate
 #define MR_FIRST 0
 #define MR_ANY 1
 #define MR_COUNT 2
 
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
-
-struct V3 {
-  double x, y, z;
-};
-
-__device__ __forceinline__ V3 vsub(const V3& a, const V3& b) { return {sub(a.x, b.x), sub(a.y, b.y), sub(a.z, b.z)}; }
-__device__ __forceinline__ V3 vload(const double* p) { return {p[0], p[1], p[2]}; }
 __device__ __forceinline__ double pick(const V3& v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __longlong_as_double(0x7ff0000000000000LL); }
-
-// ---- the cell index (as in pointcloud.hip and meshdist.hip) ---------------------------------------------------------------
-__device__ __forceinline__ int64_t cell_coord(double x, double origin, double cell) {
-  double u = floor(__ddiv_rn(sub(x, origin), cell));
-  u = u < -0x1p30 ? -0x1p30 : (u > 0x1p30 ? 0x1p30 : u);
-  return (int64_t)u;
-}
-
-__device__ __forceinline__ int64_t pack_key(int64_t x, int64_t y, int64_t z) {
-  return (x << (2 * PC_AXIS_BITS)) | (y << PC_AXIS_BITS) | z;
-}
-
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {    // the murmur3 64-bit finaliser
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-__device__ int64_t cell_row(const NudfPointCloud& a, int64_t key) {
-  const uint64_t mask = (uint64_t)a.hash_cap - 1;
-  uint64_t h = hash_mix((uint64_t)key) & mask;
-  for (int64_t probe = 0; probe < a.hash_cap; ++probe) {
-    const int64_t k = a.hash_key[h];
-    if (k == key) return a.hash_row[h];
-    if (k == PC_EMPTY) return -1;
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
 
 // ---- the per-(ray, face) rule ---------------------------------------------------------------------------------------------
 struct Ray {
@@ -290,13 +243,6 @@ __global__ __launch_bounds__(MR_BLOCK) void pc_raycast_kernel(NudfPointCloud a) 
 }
 
 // ---- the launcher ---------------------------------------------------------------------------------------------------------
-static int refuse(const char* entry, const char* why) {
-  char msg[192];
-  snprintf(msg, sizeof msg, "%s: %s", entry, why);
-  nudf_set_error(msg, hipErrorInvalidValue);          // copies the text
-  return (int)hipErrorInvalidValue;
-}
-
 #define MR_2_31 (1LL << 31)
 
 extern "C" int nudf_pc_raycast(const NudfPointCloud* args, void* stream) {
@@ -306,10 +252,8 @@ extern "C" int nudf_pc_raycast(const NudfPointCloud* args, void* stream) {
   if (a.n_query >= MR_2_31 || a.n_faces >= MR_2_31 || a.n_verts >= MR_2_31 || a.n_faces < 0 || a.n_verts < 0)
     return refuse(entry, "n_query, n_faces and n_verts must lie in [0, 2^31)");
   if (!(a.cell > 0.0) || !(a.cell < __builtin_inf())) return refuse(entry, "cell must be a positive finite number");
-  for (int x = 0; x < 3; ++x)
-    if (a.grid[x] < 1 || a.grid[x] > PC_AXIS_MAX + 1) return refuse(entry, "grid must lie in [1, 2^21] on every axis");
-  for (int x = 0; x < 3; ++x)
-    if (!(a.origin[x] - a.origin[x] == 0.0)) return refuse(entry, "origin must be finite");
+  if (!grid_ok(a)) return refuse(entry, "grid must lie in [1, 2^21] on every axis");
+  if (!origin_ok(a)) return refuse(entry, "origin must be finite");
   if (a.md_mode != MR_FIRST && a.md_mode != MR_ANY && a.md_mode != MR_COUNT)
     return refuse(entry, "unknown mode (md_mode must be 0 first, 1 any or 2 count)");
   if (a.md_t_min != a.md_t_min) return refuse(entry, "t_min is NaN");
@@ -322,8 +266,5 @@ extern "C" int nudf_pc_raycast(const NudfPointCloud* args, void* stream) {
     return refuse(entry, "NULL buffer");
   if (a.md_mode == MR_FIRST ? (!a.dist || !a.idx || !a.md_bary) : !a.md_count)
     return refuse(entry, "NULL output buffer (first: dist, idx, md_bary; any, count: md_count)");
-  hipLaunchKernelGGL(pc_raycast_kernel, dim3((unsigned)((a.n_query + MR_BLOCK - 1) / MR_BLOCK)), dim3(MR_BLOCK), 0,
-                     (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_raycast");
-  return 0;
+  MESH_LAUNCH(pc_raycast_kernel, a.n_query, MR_BLOCK, MR_BLOCK, entry);
 }

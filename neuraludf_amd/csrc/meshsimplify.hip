@@ -12,18 +12,15 @@
 //             for the caller's sort.
 // Every sum runs in list order inside one thread: no atomics, the result is identical from run to run.  No kernel waits on
 // another workgroup.  The float64 expressions follow the numpy restatement (tests/meshsimplify_ref.py) operation by
-// operation: products and sums go through mul / add / sub under the pragma, as in meshtopo.hip.
+// operation: products and sums go through mul / add / sub of f64_exact.h under the pragma.
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
+#include "f64_exact.h"
+#include "mesh_launch.h"
 #include "../../include/nudf.h"
 
 #define SP_BLOCK 256
 #define SP_MAX_GRID (1LL << 20)
-
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
 
 __device__ __forceinline__ double dot3(const double* a, const double* b) {
   return add(add(mul(a[0], b[0]), mul(a[1], b[1])), mul(a[2], b[2]));
@@ -34,8 +31,6 @@ __device__ __forceinline__ void cross3(const double* a, const double* b, double*
   o[1] = sub(mul(a[2], b[0]), mul(a[0], b[2]));
   o[2] = sub(mul(a[0], b[1]), mul(a[1], b[0]));
 }
-
-__device__ __forceinline__ bool positive_finite(double x) { return x > 0.0 && x < HUGE_VAL; }
 
 // ---- (a) keys -----------------------------------------------------------------------------------------------------------
 // key = (cx Gy + cy) Gz + cz with c = floor((p - origin) / cell) per axis, or -1 when a coordinate is not finite or its
@@ -228,13 +223,6 @@ __global__ __launch_bounds__(SP_BLOCK) void sp_faces_kernel(NudfMeshTopo a) {
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n) { return (unsigned)((n + SP_BLOCK - 1) / SP_BLOCK); }
-
-static int refuse(const char* where) {
-  nudf_set_error(where, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 static bool sizes_ok(const NudfMeshTopo& a) {
   if (!(a.n_faces >= 0 && a.n_verts >= 0 && a.n_verts < (1LL << 31) && a.n_faces < (1LL << 40))) return false;
   if (a.n_clusters < 0 || a.n_clusters > a.n_verts || a.n_edges < 0 || a.n_edges > 3 * a.n_faces) return false;
@@ -253,42 +241,40 @@ static bool grid_ok(const NudfMeshTopo& a) {
 #define SP_SIZES "bad sizes (n_verts must be < 2^31, a grid dimension <= 2^20, the attribute width >= 0)"
 #define SP_GRID "the cell must be positive and finite, the origin finite and every grid dimension >= 1"
 
-#define SP_LAUNCH(kernel, n, name)                                                                        \
-  hipLaunchKernelGGL(kernel, dim3(blocks(n)), dim3(SP_BLOCK), 0, (hipStream_t)stream, a);                 \
-  NUDF_CHECK_LAUNCH(name);                                                                                \
-  return 0
-
 extern "C" int nudf_meshsimplify_keys(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsimplify_keys: " SP_SIZES);
+  const char* const entry = "nudf_meshsimplify_keys";
+  if (!sizes_ok(a)) return refuse(entry, SP_SIZES);
   if (a.n_verts <= 0) return 0;
-  if (!grid_ok(a)) return refuse("nudf_meshsimplify_keys: " SP_GRID);
-  if (!a.pos || !a.sp_key) return refuse("nudf_meshsimplify_keys: pos or sp_key is NULL");
-  SP_LAUNCH(sp_keys_kernel, a.n_verts, "nudf_meshsimplify_keys");
+  if (!grid_ok(a)) return refuse(entry, SP_GRID);
+  if (!a.pos || !a.sp_key) return refuse(entry, "pos or sp_key is NULL");
+  MESH_LAUNCH(sp_keys_kernel, a.n_verts, SP_BLOCK, SP_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsimplify_place(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsimplify_place: " SP_SIZES);
+  const char* const entry = "nudf_meshsimplify_place";
+  if (!sizes_ok(a)) return refuse(entry, SP_SIZES);
   if (a.n_clusters <= 0) return 0;
-  if (!grid_ok(a)) return refuse("nudf_meshsimplify_place: " SP_GRID);
-  if (a.sp_placement != 0 && a.sp_placement != 1) return refuse("nudf_meshsimplify_place: sp_placement not 0 or 1");
+  if (!grid_ok(a)) return refuse(entry, SP_GRID);
+  if (a.sp_placement != 0 && a.sp_placement != 1) return refuse(entry, "sp_placement not 0 or 1");
   if (!(a.sp_lambda > 0.0 && a.sp_lambda < HUGE_VAL) || !(a.sp_boundary_weight >= 0.0 && a.sp_boundary_weight < HUGE_VAL))
-    return refuse("nudf_meshsimplify_place: sp_lambda must be positive, sp_boundary_weight not negative, both finite");
+    return refuse(entry, "sp_lambda must be positive, sp_boundary_weight not negative, both finite");
   if (!a.pos || !a.sp_cluster_key || !a.sp_member_off || !a.sp_member || !a.sp_rep || !a.sp_accepted)
-    return refuse("nudf_meshsimplify_place: pos, sp_cluster_key, sp_member_off, sp_member, sp_rep or sp_accepted is NULL");
+    return refuse(entry, "pos, sp_cluster_key, sp_member_off, sp_member, sp_rep or sp_accepted is NULL");
   if (a.sp_placement == 0 && (!a.faces || !a.sp_corner_off || !a.sp_corner))
-    return refuse("nudf_meshsimplify_place: faces, sp_corner_off or sp_corner is NULL");
+    return refuse(entry, "faces, sp_corner_off or sp_corner is NULL");
   if (a.sp_attr_width > 0 && (!a.sp_attr || !a.sp_attr_out))
-    return refuse("nudf_meshsimplify_place: sp_attr or sp_attr_out is NULL with sp_attr_width > 0");
-  SP_LAUNCH(sp_place_kernel, a.n_clusters, "nudf_meshsimplify_place");
+    return refuse(entry, "sp_attr or sp_attr_out is NULL with sp_attr_width > 0");
+  MESH_LAUNCH(sp_place_kernel, a.n_clusters, SP_BLOCK, SP_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsimplify_faces(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsimplify_faces: " SP_SIZES);
+  const char* const entry = "nudf_meshsimplify_faces";
+  if (!sizes_ok(a)) return refuse(entry, SP_SIZES);
   if (a.n_faces <= 0) return 0;
   if (!a.faces || !a.sp_vcluster || !a.sp_faces || !a.sp_triple || !a.sp_degenerate)
-    return refuse("nudf_meshsimplify_faces: faces, sp_vcluster, sp_faces, sp_triple or sp_degenerate is NULL");
-  SP_LAUNCH(sp_faces_kernel, a.n_faces, "nudf_meshsimplify_faces");
+    return refuse(entry, "faces, sp_vcluster, sp_faces, sp_triple or sp_degenerate is NULL");
+  MESH_LAUNCH(sp_faces_kernel, a.n_faces, SP_BLOCK, SP_BLOCK, entry);
 }

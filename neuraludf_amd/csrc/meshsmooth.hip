@@ -13,23 +13,18 @@
 //              the vertex's faces.
 // Every thread writes its own item only and sums in list order: no atomics, identical from run to run.  The float64
 // expressions follow the numpy restatement (tests/meshsmooth_ref.py) operation by operation: products and sums go through
-// mul / add / sub under the pragma, as in meshorient.hip; the one library call is the exp of the bilateral weight.
+// mul / add / sub of f64_exact.h under the pragma; the one library call is the exp of the bilateral weight.
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
+#include "f64_exact.h"
+#include "mesh_launch.h"
 #include "../../include/nudf.h"
 
 #define SM_BLOCK 256
 
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
-
 __device__ __forceinline__ double dot3(double ax, double ay, double az, double bx, double by, double bz) {
   return add(add(mul(ax, bx), mul(ay, by)), mul(az, bz));
 }
-
-__device__ __forceinline__ bool positive_finite(double x) { return x > 0.0 && x < HUGE_VAL; }
 
 __device__ __forceinline__ bool in_range(const NudfMeshOrient& a, const int64_t* t) {
   return t[0] >= 0 && t[1] >= 0 && t[2] >= 0 && t[0] < a.n_verts && t[1] < a.n_verts && t[2] < a.n_verts;
@@ -227,63 +222,55 @@ __global__ __launch_bounds__(SM_BLOCK) void sm_update_kernel(NudfMeshOrient a) {
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n) { return (unsigned)((n + SM_BLOCK - 1) / SM_BLOCK); }
-
-static int refuse(const char* where) {
-  nudf_set_error(where, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 static bool sizes_ok(const NudfMeshOrient& a) {
   return a.n_faces >= 0 && a.n_faces < (1LL << 36) && a.n_verts >= 0 && a.n_verts < (1LL << 31) && a.sm_n_nbr >= 0;
 }
 
-static bool positive_finite_host(double x) { return x > 0.0 && x < HUGE_VAL; }
-
-#define SM_LAUNCH(kernel, n, name)                                                                  \
-  hipLaunchKernelGGL(kernel, dim3(blocks(n)), dim3(SM_BLOCK), 0, (hipStream_t)stream, a);           \
-  NUDF_CHECK_LAUNCH(name);                                                                          \
-  return 0
+#define SM_SIZES "bad sizes (n_verts must be < 2^31, n_faces < 2^36, sm_n_nbr >= 0)"
 
 extern "C" int nudf_meshsmooth_laplace(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsmooth_laplace: bad sizes (n_verts must be < 2^31, n_faces < 2^36, sm_n_nbr >= 0)");
+  const char* const entry = "nudf_meshsmooth_laplace";
+  if (!sizes_ok(a)) return refuse(entry, SM_SIZES);
   if (a.n_verts <= 0) return 0;
-  if (a.sm_weights != 0 && a.sm_weights != 1) return refuse("nudf_meshsmooth_laplace: sm_weights must be 0 (uniform) or 1 (cotangent)");
-  if (!(a.sm_step > -HUGE_VAL && a.sm_step < HUGE_VAL)) return refuse("nudf_meshsmooth_laplace: sm_step must be finite");
-  if (!a.pos || !a.sm_pos_out) return refuse("nudf_meshsmooth_laplace: NULL pos or sm_pos_out");
+  if (a.sm_weights != 0 && a.sm_weights != 1) return refuse(entry, "sm_weights must be 0 (uniform) or 1 (cotangent)");
+  if (!(a.sm_step > -HUGE_VAL && a.sm_step < HUGE_VAL)) return refuse(entry, "sm_step must be finite");
+  if (!a.pos || !a.sm_pos_out) return refuse(entry, "NULL pos or sm_pos_out");
   if (a.sm_weights == 0 && (!a.sm_nbr_off || (a.sm_n_nbr > 0 && !a.sm_nbr)))
-    return refuse("nudf_meshsmooth_laplace: NULL sm_nbr_off or sm_nbr");
+    return refuse(entry, "NULL sm_nbr_off or sm_nbr");
   if (a.sm_weights == 1 && (!a.corner_off || (a.n_faces > 0 && (!a.corner || !a.faces))))
-    return refuse("nudf_meshsmooth_laplace: NULL corner_off, corner or faces");
-  SM_LAUNCH(sm_laplace_kernel, a.n_verts, "nudf_meshsmooth_laplace");
+    return refuse(entry, "NULL corner_off, corner or faces");
+  MESH_LAUNCH(sm_laplace_kernel, a.n_verts, SM_BLOCK, SM_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsmooth_frames(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsmooth_frames: bad sizes (n_verts must be < 2^31, n_faces < 2^36, sm_n_nbr >= 0)");
+  const char* const entry = "nudf_meshsmooth_frames";
+  if (!sizes_ok(a)) return refuse(entry, SM_SIZES);
   if (a.n_faces <= 0) return 0;
   if (!a.faces || !a.pos || !a.sm_fnormal_out || !a.sm_farea || !a.sm_fcentre)
-    return refuse("nudf_meshsmooth_frames: NULL faces, pos, sm_fnormal_out, sm_farea or sm_fcentre");
-  SM_LAUNCH(sm_frames_kernel, a.n_faces, "nudf_meshsmooth_frames");
+    return refuse(entry, "NULL faces, pos, sm_fnormal_out, sm_farea or sm_fcentre");
+  MESH_LAUNCH(sm_frames_kernel, a.n_faces, SM_BLOCK, SM_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsmooth_normals(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsmooth_normals: bad sizes (n_verts must be < 2^31, n_faces < 2^36, sm_n_nbr >= 0)");
+  const char* const entry = "nudf_meshsmooth_normals";
+  if (!sizes_ok(a)) return refuse(entry, SM_SIZES);
   if (a.n_faces <= 0) return 0;
-  if (!positive_finite_host(a.sm_inv2sc) || !positive_finite_host(a.sm_inv2ss))
-    return refuse("nudf_meshsmooth_normals: sm_inv2sc and sm_inv2ss (1 / (2 sigma^2)) must be positive and finite");
+  if (!positive_finite(a.sm_inv2sc) || !positive_finite(a.sm_inv2ss))
+    return refuse(entry, "sm_inv2sc and sm_inv2ss (1 / (2 sigma^2)) must be positive and finite");
   if (!a.faces || !a.corner_off || !a.corner || !a.sm_fnormal || !a.sm_fnormal_out || !a.sm_farea || !a.sm_fcentre)
-    return refuse("nudf_meshsmooth_normals: NULL faces, corner_off, corner, sm_fnormal, sm_fnormal_out, sm_farea or sm_fcentre");
-  SM_LAUNCH(sm_normals_kernel, a.n_faces, "nudf_meshsmooth_normals");
+    return refuse(entry, "NULL faces, corner_off, corner, sm_fnormal, sm_fnormal_out, sm_farea or sm_fcentre");
+  MESH_LAUNCH(sm_normals_kernel, a.n_faces, SM_BLOCK, SM_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsmooth_update(const NudfMeshOrient* args, void* stream) {
   const NudfMeshOrient& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshsmooth_update: bad sizes (n_verts must be < 2^31, n_faces < 2^36, sm_n_nbr >= 0)");
+  const char* const entry = "nudf_meshsmooth_update";
+  if (!sizes_ok(a)) return refuse(entry, SM_SIZES);
   if (a.n_verts <= 0) return 0;
   if (!a.pos || !a.sm_pos_out || !a.corner_off || (a.n_faces > 0 && (!a.corner || !a.faces || !a.sm_fnormal)))
-    return refuse("nudf_meshsmooth_update: NULL pos, sm_pos_out, corner_off, corner, faces or sm_fnormal");
-  SM_LAUNCH(sm_update_kernel, a.n_verts, "nudf_meshsmooth_update");
+    return refuse(entry, "NULL pos, sm_pos_out, corner_off, corner, faces or sm_fnormal");
+  MESH_LAUNCH(sm_update_kernel, a.n_verts, SM_BLOCK, SM_BLOCK, entry);
 }

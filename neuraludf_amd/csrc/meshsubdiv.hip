@@ -8,17 +8,14 @@
 //   emit   -- one thread per face: the children of the 0 / 1 / 2 / 3-marked template, in the parent's winding.
 // Every thread writes its own item only and sums in list order: no atomics, identical from run to run.  The float64
 // expressions follow the numpy restatement (tests/meshsubdiv_ref.py) operation by operation: products and sums go through
-// mul / add / sub under the pragma, as in meshsmooth.hip; the one division is Warren's 3 / (8 n).
+// mul / add / sub of f64_exact.h under the pragma; the one division is Warren's 3 / (8 n).
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
+#include "f64_exact.h"
+#include "mesh_launch.h"
 #include "../../include/nudf.h"
 
 #define SD_BLOCK 256
-
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
 
 __device__ __forceinline__ bool vertex_ok(const NudfMeshTopo& a, int64_t v) { return v >= 0 && v < a.n_verts; }
 
@@ -202,14 +199,6 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_emit_kernel(NudfMeshTopo a) {
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n) { return (unsigned)((n + SD_BLOCK - 1) / SD_BLOCK); }
-
-static int refuse(const char* entry, const char* why) {
-  char text[256];
-  snprintf(text, sizeof(text), "nudf_meshsubdiv_%s: %s", entry, why);
-  return nudf_refuse(text);
-}
-
 // the counts every entry point is handed; NULL when they are in order, else what is wrong
 static const char* bad_sizes(const NudfMeshTopo& a) {
   const int64_t lim = 1LL << 31;
@@ -229,59 +218,59 @@ static const char* bad_scheme(const NudfMeshTopo& a) {
   return a.sp_sd_scheme == 0 || a.sp_sd_scheme == 1 ? nullptr : "sp_sd_scheme must be 0 (midpoint) or 1 (loop)";
 }
 
-#define SD_LAUNCH(kernel, n, name)                                                                  \
-  hipLaunchKernelGGL(kernel, dim3(blocks(n)), dim3(SD_BLOCK), 0, (hipStream_t)stream, a);           \
-  NUDF_CHECK_LAUNCH(name);                                                                          \
-  return 0
-
 extern "C" int nudf_meshsubdiv_mark(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (const char* why = bad_sizes(a)) return refuse("mark", why);
+  const char* const entry = "nudf_meshsubdiv_mark";
+  if (const char* why = bad_sizes(a)) return refuse(entry, why);
   if (a.n_edges <= 0) return 0;
   if (!a.sp_sd_mark_all && !(a.sp_sd_max_edge > 0.0 && a.sp_sd_max_edge < HUGE_VAL))
-    return refuse("mark", "sp_sd_max_edge must be positive and finite unless sp_sd_mark_all is set");
-  if (!a.edges || !a.sp_sd_mark || (!a.sp_sd_mark_all && !a.pos)) return refuse("mark", "NULL edges, sp_sd_mark or pos");
-  SD_LAUNCH(sd_mark_kernel, a.n_edges, "nudf_meshsubdiv_mark");
+    return refuse(entry, "sp_sd_max_edge must be positive and finite unless sp_sd_mark_all is set");
+  if (!a.edges || !a.sp_sd_mark || (!a.sp_sd_mark_all && !a.pos)) return refuse(entry, "NULL edges, sp_sd_mark or pos");
+  MESH_LAUNCH(sd_mark_kernel, a.n_edges, SD_BLOCK, SD_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsubdiv_odd(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (const char* why = bad_sizes(a)) return refuse("odd", why);
+  const char* const entry = "nudf_meshsubdiv_odd";
+  if (const char* why = bad_sizes(a)) return refuse(entry, why);
   if (a.sp_sd_n_marked <= 0) return 0;
-  if (const char* why = bad_scheme(a)) return refuse("odd", why);
-  if (!a.sp_sd_marked || !a.edges || !a.pos || !a.sp_sd_pos_out) return refuse("odd", "NULL sp_sd_marked, edges, pos or sp_sd_pos_out");
-  if (a.sp_attr_width > 0 && (!a.sp_attr || !a.sp_sd_attr_out)) return refuse("odd", "NULL sp_attr or sp_sd_attr_out");
-  if (a.sp_sd_scheme == 1 && (!a.faces || !a.he_id || !a.edge_start)) return refuse("odd", "NULL faces, he_id or edge_start");
-  SD_LAUNCH(sd_odd_kernel, a.sp_sd_n_marked, "nudf_meshsubdiv_odd");
+  if (const char* why = bad_scheme(a)) return refuse(entry, why);
+  if (!a.sp_sd_marked || !a.edges || !a.pos || !a.sp_sd_pos_out) return refuse(entry, "NULL sp_sd_marked, edges, pos or sp_sd_pos_out");
+  if (a.sp_attr_width > 0 && (!a.sp_attr || !a.sp_sd_attr_out)) return refuse(entry, "NULL sp_attr or sp_sd_attr_out");
+  if (a.sp_sd_scheme == 1 && (!a.faces || !a.he_id || !a.edge_start)) return refuse(entry, "NULL faces, he_id or edge_start");
+  MESH_LAUNCH(sd_odd_kernel, a.sp_sd_n_marked, SD_BLOCK, SD_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsubdiv_even(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (const char* why = bad_sizes(a)) return refuse("even", why);
+  const char* const entry = "nudf_meshsubdiv_even";
+  if (const char* why = bad_sizes(a)) return refuse(entry, why);
   if (a.n_verts <= 0) return 0;
-  if (const char* why = bad_scheme(a)) return refuse("even", why);
-  if (!a.pos || !a.sp_sd_pos_out) return refuse("even", "NULL pos or sp_sd_pos_out");
-  if (a.sp_attr_width > 0 && (!a.sp_attr || !a.sp_sd_attr_out)) return refuse("even", "NULL sp_attr or sp_sd_attr_out");
+  if (const char* why = bad_scheme(a)) return refuse(entry, why);
+  if (!a.pos || !a.sp_sd_pos_out) return refuse(entry, "NULL pos or sp_sd_pos_out");
+  if (a.sp_attr_width > 0 && (!a.sp_attr || !a.sp_sd_attr_out)) return refuse(entry, "NULL sp_attr or sp_sd_attr_out");
   if (a.sp_sd_scheme == 1 && (!a.sp_sd_vclass || !a.sp_sd_ring_off || !a.nbr_off || (a.sp_sd_n_ring > 0 && !a.sp_sd_ring) ||
                               (a.sp_sd_n_border > 0 && !a.nbr)))
-    return refuse("even", "NULL sp_sd_vclass, sp_sd_ring_off, sp_sd_ring, nbr_off or nbr");
-  SD_LAUNCH(sd_even_kernel, a.n_verts, "nudf_meshsubdiv_even");
+    return refuse(entry, "NULL sp_sd_vclass, sp_sd_ring_off, sp_sd_ring, nbr_off or nbr");
+  MESH_LAUNCH(sd_even_kernel, a.n_verts, SD_BLOCK, SD_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsubdiv_count(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (const char* why = bad_sizes(a)) return refuse("count", why);
+  const char* const entry = "nudf_meshsubdiv_count";
+  if (const char* why = bad_sizes(a)) return refuse(entry, why);
   if (a.n_faces <= 0) return 0;
   if (!a.faces || !a.he_edge || !a.sp_sd_edge_vertex || !a.sp_sd_fcount)
-    return refuse("count", "NULL faces, he_edge, sp_sd_edge_vertex or sp_sd_fcount");
-  SD_LAUNCH(sd_count_kernel, a.n_faces, "nudf_meshsubdiv_count");
+    return refuse(entry, "NULL faces, he_edge, sp_sd_edge_vertex or sp_sd_fcount");
+  MESH_LAUNCH(sd_count_kernel, a.n_faces, SD_BLOCK, SD_BLOCK, entry);
 }
 
 extern "C" int nudf_meshsubdiv_emit(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (const char* why = bad_sizes(a)) return refuse("emit", why);
+  const char* const entry = "nudf_meshsubdiv_emit";
+  if (const char* why = bad_sizes(a)) return refuse(entry, why);
   if (a.n_faces <= 0) return 0;
   if (!a.faces || !a.he_edge || !a.sp_sd_edge_vertex || !a.sp_sd_foff || !a.sp_sd_faces_out || !a.sp_sd_parent || !a.sp_sd_pos_out)
-    return refuse("emit", "NULL faces, he_edge, sp_sd_edge_vertex, sp_sd_foff, sp_sd_faces_out, sp_sd_parent or sp_sd_pos_out");
-  SD_LAUNCH(sd_emit_kernel, a.n_faces, "nudf_meshsubdiv_emit");
+    return refuse(entry, "NULL faces, he_edge, sp_sd_edge_vertex, sp_sd_foff, sp_sd_faces_out, sp_sd_parent or sp_sd_pos_out");
+  MESH_LAUNCH(sd_emit_kernel, a.n_faces, SD_BLOCK, SD_BLOCK, entry);
 }

@@ -14,19 +14,16 @@
 //   views      -- one thread per vertex: the number of views whose mask the vertex projects into.
 // A key is looked up in the sorted table of unique edge keys by bisection: the row depends on the key alone.  No kernel
 // waits on another workgroup.  The float64 expressions follow the numpy restatement (tests/meshclean_ref.py) operation by
-// operation; hipcc would fuse a multiply and an add by default, so they go through mul / add / sub under the pragma
-// (tests/test_meshclean_asm.py).
+// operation; hipcc would fuse a multiply and an add by default, so they go through mul / add / sub of f64_exact.h under
+// the pragma (tests/test_meshclean_asm.py).
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
+#include "f64_exact.h"
+#include "mesh_launch.h"
 #include "../../include/nudf.h"
 
 #define MT_BLOCK 256
 #define MT_MAX_LOOP 4
-
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
 
 // ---- (a) edge table --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(MT_BLOCK) void mt_edges_kernel(NudfMeshTopo a) {
@@ -246,69 +243,63 @@ __global__ __launch_bounds__(MT_BLOCK) void mt_views_kernel(NudfMeshTopo a) {
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n) { return (unsigned)((n + MT_BLOCK - 1) / MT_BLOCK); }
-
-static int refuse(const char* where) {
-  nudf_set_error(where, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
 static bool sizes_ok(const NudfMeshTopo& a) {
   return a.n_faces >= 0 && a.n_verts >= 0 && a.n_verts < (1LL << 31) && a.n_faces < (1LL << 40);
 }
 
-#define MT_LAUNCH(kernel, n, name)                                                                        \
-  hipLaunchKernelGGL(kernel, dim3(blocks(n)), dim3(MT_BLOCK), 0, (hipStream_t)stream, a);                 \
-  NUDF_CHECK_LAUNCH(name);                                                                                \
-  return 0
-
 extern "C" int nudf_meshtopo_edges(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a) || a.n_edges > 3 * a.n_faces) return refuse("nudf_meshtopo_edges: bad sizes (n_verts must be < 2^31)");
+  const char* const entry = "nudf_meshtopo_edges";
+  if (!sizes_ok(a) || a.n_edges > 3 * a.n_faces) return refuse(entry, "bad sizes (n_verts must be < 2^31)");
   if (a.n_edges <= 0) return 0;
-  if (a.n_verts <= 0) return refuse("nudf_meshtopo_edges: edges without vertices");
-  MT_LAUNCH(mt_edges_kernel, a.n_edges, "nudf_meshtopo_edges");
+  if (a.n_verts <= 0) return refuse(entry, "edges without vertices");
+  MESH_LAUNCH(mt_edges_kernel, a.n_edges, MT_BLOCK, MT_BLOCK, entry);
 }
 
 extern "C" int nudf_meshtopo_fill_count(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a) || a.max_loop < 3 || a.max_loop > MT_MAX_LOOP) return refuse("nudf_meshtopo_fill_count: max_loop not 3 or 4");
+  const char* const entry = "nudf_meshtopo_fill_count";
+  if (!sizes_ok(a) || a.max_loop < 3 || a.max_loop > MT_MAX_LOOP) return refuse(entry, "max_loop not 3 or 4");
   if (a.n_bverts <= 0) return 0;
-  MT_LAUNCH(mt_fill_count_kernel, a.n_bverts, "nudf_meshtopo_fill_count");
+  MESH_LAUNCH(mt_fill_count_kernel, a.n_bverts, MT_BLOCK, MT_BLOCK, entry);
 }
 
 extern "C" int nudf_meshtopo_fill_emit(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a) || a.max_loop < 3 || a.max_loop > MT_MAX_LOOP) return refuse("nudf_meshtopo_fill_emit: max_loop not 3 or 4");
+  const char* const entry = "nudf_meshtopo_fill_emit";
+  if (!sizes_ok(a) || a.max_loop < 3 || a.max_loop > MT_MAX_LOOP) return refuse(entry, "max_loop not 3 or 4");
   if (a.n_bverts <= 0 || a.n_new <= 0) return 0;
-  MT_LAUNCH(mt_fill_emit_kernel, a.n_bverts, "nudf_meshtopo_fill_emit");
+  MESH_LAUNCH(mt_fill_emit_kernel, a.n_bverts, MT_BLOCK, MT_BLOCK, entry);
 }
 
 extern "C" int nudf_meshtopo_smooth(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshtopo_smooth: bad sizes");
+  const char* const entry = "nudf_meshtopo_smooth";
+  if (!sizes_ok(a)) return refuse(entry, "bad sizes");
   if (a.n_bverts <= 0) return 0;
-  MT_LAUNCH(mt_smooth_kernel, a.n_bverts, "nudf_meshtopo_smooth");
+  MESH_LAUNCH(mt_smooth_kernel, a.n_bverts, MT_BLOCK, MT_BLOCK, entry);
 }
 
 extern "C" int nudf_meshtopo_cc_hook(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshtopo_cc_hook: bad sizes");
+  const char* const entry = "nudf_meshtopo_cc_hook";
+  if (!sizes_ok(a)) return refuse(entry, "bad sizes");
   if (3 * a.n_faces <= 1) return 0;
-  MT_LAUNCH(mt_cc_hook_kernel, 3 * a.n_faces - 1, "nudf_meshtopo_cc_hook");
+  MESH_LAUNCH(mt_cc_hook_kernel, 3 * a.n_faces - 1, MT_BLOCK, MT_BLOCK, entry);
 }
 
 extern "C" int nudf_meshtopo_cc_jump(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a)) return refuse("nudf_meshtopo_cc_jump: bad sizes");
+  const char* const entry = "nudf_meshtopo_cc_jump";
+  if (!sizes_ok(a)) return refuse(entry, "bad sizes");
   if (a.n_faces <= 0) return 0;
-  MT_LAUNCH(mt_cc_jump_kernel, a.n_faces, "nudf_meshtopo_cc_jump");
+  MESH_LAUNCH(mt_cc_jump_kernel, a.n_faces, MT_BLOCK, MT_BLOCK, entry);
 }
 
 extern "C" int nudf_meshtopo_views(const NudfMeshTopo* args, void* stream) {
   const NudfMeshTopo& a = *args;
-  if (!sizes_ok(a) || a.n_views < 0 || a.H < 1 || a.W < 1 || a.border < 0)
-    return refuse("nudf_meshtopo_views: bad sizes");
+  const char* const entry = "nudf_meshtopo_views";
+  if (!sizes_ok(a) || a.n_views < 0 || a.H < 1 || a.W < 1 || a.border < 0) return refuse(entry, "bad sizes");
   if (a.n_verts <= 0) return 0;
-  MT_LAUNCH(mt_views_kernel, a.n_verts, "nudf_meshtopo_views");
+  MESH_LAUNCH(mt_views_kernel, a.n_verts, MT_BLOCK, MT_BLOCK, entry);
 }

@@ -9,34 +9,19 @@
 //   thin_round -- one thread per undecided point (cell-sorted): the greedy radius thinning as rounds of a
 //                 lexicographically-first maximal independent set in rank order;
 //   nearest    -- one thread per query (cell-sorted): exact nearest neighbour by Chebyshev rings of cells, up to `bound`.
-// Every float64 expression is evaluated in the reference's (numpy's / sklearn's) operation order with no contraction.
-// hipcc fuses a multiply and an add into v_fma_f64 / v_fmac_f64 by default, even through __dmul_rn / __dadd_rn (the
-// HIP headers define those before this file's first line, so no pragma here reaches them).  The products and sums below
-// therefore go through mul / add / sub, plain operators under the pragma.  The only fused instructions left are inside
-// the correctly rounded __ddiv_rn / __dsqrt_rn expansions (tests/test_pointcloud_asm.py).
+// Every float64 expression is evaluated in the reference's (numpy's / sklearn's) operation order with no contraction:
+// products and sums go through mul / add / sub of f64_exact.h, plain operators under the pragma
+// (tests/test_pointcloud_asm.py).  The cell key, the hash and the ring walk are those of cell_index.h, which meshdist.hip
+// and meshray.hip search the same table with.
 #pragma clang fp contract(off)
 
-#include "nudf_common.h"
-#include "../../include/nudf.h"
+#include "cell_index.h"
+#include "mesh_launch.h"
 
 #define PC_BLOCK 256
-#define PC_AXIS_BITS 21
-#define PC_AXIS_MAX ((1 << PC_AXIS_BITS) - 1)
-#define PC_EMPTY (-1LL)
 #define PC_UNDECIDED 0
 #define PC_KEEP 1
 #define PC_DROP 2
-// a cell coordinate is computed with a relative error of a few ulps of its value (< 2^22): at most 2^-29 of a cell.  The
-// ring search and the thinning's 27-cell window allow 2^-20 of a cell for it.
-#define PC_CELL_MARGIN 0x1p-20
-
-__device__ __forceinline__ double mul(double x, double y) { return x * y; }
-__device__ __forceinline__ double add(double x, double y) { return x + y; }
-__device__ __forceinline__ double sub(double x, double y) { return x - y; }
-
-__device__ __forceinline__ double dot3(double x, double y, double z) {
-  return add(add(mul(x, x), mul(y, y)), mul(z, z));
-}
 
 __device__ __forceinline__ double dist2(const double* p, double qx, double qy, double qz) {
   return dot3(sub(qx, p[0]), sub(qy, p[1]), sub(qz, p[2]));
@@ -130,42 +115,7 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_tri_emit_kernel(NudfPointCloud a)
   }
 }
 
-// ---- the cell index --------------------------------------------------------------------------------------------------
-// cell coordinate of x along one axis, unclamped (a query may lie outside the points' box); |value| <= 2^30
-__device__ __forceinline__ int64_t cell_coord(double x, double origin, double cell) {
-  double u = floor(__ddiv_rn(sub(x, origin), cell));
-  u = u < -0x1p30 ? -0x1p30 : (u > 0x1p30 ? 0x1p30 : u);   // far outside the grid: the ring bound still holds
-  return (int64_t)u;
-}
-
-__device__ __forceinline__ int64_t pack_key(int64_t x, int64_t y, int64_t z) {
-  return (x << (2 * PC_AXIS_BITS)) | (y << PC_AXIS_BITS) | z;
-}
-
-__device__ __forceinline__ int64_t clamp_axis(int64_t c) { return c < 0 ? 0 : (c > PC_AXIS_MAX ? PC_AXIS_MAX : c); }
-
-__device__ __forceinline__ uint64_t hash_mix(uint64_t k) {    // the murmur3 64-bit finaliser
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdULL;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ULL;
-  k ^= k >> 33;
-  return k;
-}
-
-// row of the sorted cell table holding `key`, or -1 (the table is at most half full: a probe always meets an empty slot)
-__device__ int64_t cell_row(const NudfPointCloud& a, int64_t key) {
-  const uint64_t mask = (uint64_t)a.hash_cap - 1;
-  uint64_t h = hash_mix((uint64_t)key) & mask;
-  for (int64_t probe = 0; probe < a.hash_cap; ++probe) {
-    const int64_t k = a.hash_key[h];
-    if (k == key) return a.hash_row[h];
-    if (k == PC_EMPTY) return -1;
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
-
+// ---- building the cell index (cell_index.h) ------------------------------------------------------------------------------
 __global__ __launch_bounds__(PC_BLOCK) void pc_keys_kernel(NudfPointCloud a) {
   const int64_t s = (int64_t)blockIdx.x * PC_BLOCK + threadIdx.x;
   if (s >= a.n) return;
@@ -180,7 +130,7 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_cells_kernel(NudfPointCloud a) {
   if (r >= a.n_cells) return;
   const int64_t key = a.cell_key[r];
   const uint64_t mask = (uint64_t)a.hash_cap - 1;
-  uint64_t h = hash_mix((uint64_t)key) & mask;
+  uint64_t h = probe_first(key, mask);                      // the sequence cell_row follows
   for (int64_t probe = 0; probe < a.hash_cap; ++probe) {
     const unsigned long long old =
         atomicCAS((unsigned long long*)(a.hash_key + h), (unsigned long long)PC_EMPTY, (unsigned long long)key);
@@ -188,7 +138,7 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_cells_kernel(NudfPointCloud a) {
       a.hash_row[h] = r;
       return;
     }
-    h = (h + 1) & mask;
+    h = probe_next(h, mask);
   }
 }
 
@@ -233,11 +183,8 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_thin_round_kernel(NudfPointCloud 
 }
 
 // ---- nearest neighbour (sklearn kneighbors, n_neighbors=1) --------------------------------------------------------------
-// Rings k = k0, k0 + 1, ... of cells at Chebyshev distance k from the query's cell.  Once rings up to k are done, every
-// point not seen is more than (k - margin) cells from the query: the search stops when the best distance is below that
-// (no tie can come later), when that exceeds `bound`, or when the rings cover the grid.  Candidates are compared by the
-// reported value sqrt(d2), ties by the lower reference index; d2 screens out the rest (two d2 more than 2^-48 apart
-// relative have different square roots).
+// The ring walk of cell_index.h over the points' cells.  Candidates are compared by the reported value sqrt(d2), ties by
+// the lower reference index; d2 screens out the rest (two d2 more than 2^-48 apart relative have different square roots).
 __global__ __launch_bounds__(PC_BLOCK) void pc_nearest_kernel(NudfPointCloud a) {
   const int64_t t = (int64_t)blockIdx.x * PC_BLOCK + threadIdx.x;
   if (t >= a.n_query) return;
@@ -246,58 +193,26 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_nearest_kernel(NudfPointCloud a) 
   const int64_t out = a.query_idx[t];
   double best = __longlong_as_double(0x7ff0000000000000LL), best_d2 = best;
   int64_t best_i = -1;
-  const double bx = fmax(fmax(sub(a.box_lo[0], qx), sub(qx, a.box_hi[0])), 0.0);
-  const double by = fmax(fmax(sub(a.box_lo[1], qy), sub(qy, a.box_hi[1])), 0.0);
-  const double bz = fmax(fmax(sub(a.box_lo[2], qz), sub(qz, a.box_hi[2])), 0.0);
-  if (!(dot3(bx, by, bz) > a.box_bound2)) {
-    const int64_t c[3] = {cell_coord(qx, a.origin[0], a.cell), cell_coord(qy, a.origin[1], a.cell),
-                          cell_coord(qz, a.origin[2], a.cell)};
-    int64_t k = 0;
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      const int64_t off = c[x] < 0 ? -c[x] : (c[x] >= a.grid[x] ? c[x] - (a.grid[x] - 1) : 0);
-      k = off > k ? off : k;
-    }
-    auto visit = [&](int64_t x, int64_t y, int64_t z) {
-      const int64_t row = cell_row(a, pack_key(x, y, z));
-      if (row < 0) return;
-      const int64_t b = a.cell_start[row], e = b + a.cell_count[row];
-      for (int64_t s = b; s < e; ++s) {
-        const double d2 = dist2(a.pts + 3 * s, qx, qy, qz);
-        if (!(d2 <= mul(best_d2, 1.0 + 0x1p-48))) continue;
-        const double d = __dsqrt_rn(d2);
-        const int64_t i = a.rank[s];
-        if (d < best) {
-          best = d;
-          best_i = i;
-          best_d2 = d2;
-        } else if (d == best && i < best_i) {
-          best_i = i;
-          best_d2 = d2 < best_d2 ? d2 : best_d2;
-        }
+  auto visit = [&](int64_t x, int64_t y, int64_t z) {
+    const int64_t row = cell_row(a, pack_key(x, y, z));
+    if (row < 0) return;
+    const int64_t b = a.cell_start[row], e = b + a.cell_count[row];
+    for (int64_t s = b; s < e; ++s) {
+      const double d2 = dist2(a.pts + 3 * s, qx, qy, qz);
+      if (!(d2 <= mul(best_d2, 1.0 + 0x1p-48))) continue;
+      const double d = __dsqrt_rn(d2);
+      const int64_t i = a.rank[s];
+      if (d < best) {
+        best = d;
+        best_i = i;
+        best_d2 = d2;
+      } else if (d == best && i < best_i) {
+        best_i = i;
+        best_d2 = d2 < best_d2 ? d2 : best_d2;
       }
-    };
-    for (;; ++k) {
-      const int64_t x0 = c[0] - k < 0 ? 0 : c[0] - k, x1 = c[0] + k >= a.grid[0] ? a.grid[0] - 1 : c[0] + k;
-      const int64_t y0 = c[1] - k < 0 ? 0 : c[1] - k, y1 = c[1] + k >= a.grid[1] ? a.grid[1] - 1 : c[1] + k;
-      const int64_t z0 = c[2] - k < 0 ? 0 : c[2] - k, z1 = c[2] + k >= a.grid[2] ? a.grid[2] - 1 : c[2] + k;
-      for (int64_t x = x0; x <= x1; ++x) {
-        for (int64_t y = y0; y <= y1; ++y) {
-          if (x == c[0] - k || x == c[0] + k || y == c[1] - k || y == c[1] + k) {
-            for (int64_t z = z0; z <= z1; ++z) visit(x, y, z);
-          } else {                                   // k >= 1: only the ring's two z faces are new in this column
-            if (c[2] - k >= 0) visit(x, y, c[2] - k);
-            if (c[2] + k < a.grid[2]) visit(x, y, c[2] + k);
-          }
-        }
-      }
-      const double reach = mul(sub((double)k, PC_CELL_MARGIN), a.cell);
-      if (best < reach || reach > a.bound) break;
-      if (c[0] - k <= 0 && c[1] - k <= 0 && c[2] - k <= 0 && c[0] + k >= a.grid[0] - 1 && c[1] + k >= a.grid[1] - 1 &&
-          c[2] + k >= a.grid[2] - 1)
-        break;                                             // every cell has been seen
     }
-  }
+  };
+  ring_walk(a, qx, qy, qz, visit, [&] { return best; });
   if (!(best <= a.bound)) {
     best = __longlong_as_double(0x7ff0000000000000LL);
     best_i = -1;
@@ -307,70 +222,52 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_nearest_kernel(NudfPointCloud a) 
 }
 
 // ---- launchers --------------------------------------------------------------------------------------------------------
-static unsigned blocks(int64_t n) { return (unsigned)((n + PC_BLOCK - 1) / PC_BLOCK); }
-
-static int refuse(const char* where) {
-  nudf_set_error(where, hipErrorInvalidValue);
-  return (int)hipErrorInvalidValue;
-}
-
-static bool grid_ok(const NudfPointCloud& a) {
-  for (int x = 0; x < 3; ++x)
-    if (a.grid[x] < 1 || a.grid[x] > PC_AXIS_MAX + 1) return false;
-  return a.cell > 0.0;
-}
-
 extern "C" int nudf_pc_tri_count(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
+  const char* const entry = "nudf_pc_tri_count";
   if (a.n_faces <= 0) return 0;
-  if (a.cap < 0 || !(a.density > 0.0)) return refuse("nudf_pc_tri_count: cap < 0 or density <= 0");
-  hipLaunchKernelGGL(pc_tri_count_kernel, dim3(blocks(a.n_faces)), dim3(PC_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_tri_count");
-  return 0;
+  if (a.cap < 0 || !(a.density > 0.0)) return refuse(entry, "cap < 0 or density <= 0");
+  MESH_LAUNCH(pc_tri_count_kernel, a.n_faces, PC_BLOCK, PC_BLOCK, entry);
 }
 
 extern "C" int nudf_pc_tri_emit(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
+  const char* const entry = "nudf_pc_tri_emit";
   if (a.n_faces <= 0) return 0;
-  if (a.cap < 0 || !(a.density > 0.0)) return refuse("nudf_pc_tri_emit: cap < 0 or density <= 0");
-  hipLaunchKernelGGL(pc_tri_emit_kernel, dim3(blocks(a.n_faces)), dim3(PC_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_tri_emit");
-  return 0;
+  if (a.cap < 0 || !(a.density > 0.0)) return refuse(entry, "cap < 0 or density <= 0");
+  MESH_LAUNCH(pc_tri_emit_kernel, a.n_faces, PC_BLOCK, PC_BLOCK, entry);
 }
 
 extern "C" int nudf_pc_keys(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
+  const char* const entry = "nudf_pc_keys";
   if (a.n <= 0) return 0;
-  if (!(a.cell > 0.0)) return refuse("nudf_pc_keys: cell <= 0");
-  hipLaunchKernelGGL(pc_keys_kernel, dim3(blocks(a.n)), dim3(PC_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_keys");
-  return 0;
+  if (!(a.cell > 0.0)) return refuse(entry, "cell <= 0");
+  MESH_LAUNCH(pc_keys_kernel, a.n, PC_BLOCK, PC_BLOCK, entry);
 }
 
 extern "C" int nudf_pc_cells(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
+  const char* const entry = "nudf_pc_cells";
   if (a.n_cells <= 0) return 0;
   if (a.hash_cap < 2 * a.n_cells || (a.hash_cap & (a.hash_cap - 1)))
-    return refuse("nudf_pc_cells: hash_cap must be a power of two >= 2 n_cells");
-  hipLaunchKernelGGL(pc_cells_kernel, dim3(blocks(a.n_cells)), dim3(PC_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_cells");
-  return 0;
+    return refuse(entry, "hash_cap must be a power of two >= 2 n_cells");
+  MESH_LAUNCH(pc_cells_kernel, a.n_cells, PC_BLOCK, PC_BLOCK, entry);
 }
 
 extern "C" int nudf_pc_thin_round(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
+  const char* const entry = "nudf_pc_thin_round";
   if (a.n <= 0) return 0;
-  if (!grid_ok(a) || a.hash_cap < 2) return refuse("nudf_pc_thin_round: bad grid, cell or hash table");
-  hipLaunchKernelGGL(pc_thin_round_kernel, dim3(blocks(a.n)), dim3(PC_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_thin_round");
-  return 0;
+  if (!grid_ok(a) || !(a.cell > 0.0) || a.hash_cap < 2) return refuse(entry, "bad grid, cell or hash table");
+  MESH_LAUNCH(pc_thin_round_kernel, a.n, PC_BLOCK, PC_BLOCK, entry);
 }
 
 extern "C" int nudf_pc_nearest(const NudfPointCloud* args, void* stream) {
   const NudfPointCloud& a = *args;
+  const char* const entry = "nudf_pc_nearest";
   if (a.n_query <= 0) return 0;
-  if (!grid_ok(a) || a.hash_cap < 2 || a.n <= 0) return refuse("nudf_pc_nearest: bad grid, cell or hash table");
-  hipLaunchKernelGGL(pc_nearest_kernel, dim3(blocks(a.n_query)), dim3(PC_BLOCK), 0, (hipStream_t)stream, a);
-  NUDF_CHECK_LAUNCH("nudf_pc_nearest");
-  return 0;
+  if (!grid_ok(a) || !(a.cell > 0.0) || a.hash_cap < 2 || a.n <= 0)
+    return refuse(entry, "bad grid, cell or hash table");
+  MESH_LAUNCH(pc_nearest_kernel, a.n_query, PC_BLOCK, PC_BLOCK, entry);
 }

@@ -156,6 +156,18 @@ def test_nearest_bound_edges():
     assert _np(i)[1] == -1
 
 
+def test_nearest_bound_stops_the_walk_among_empty_cells():
+    """two clusters in opposite corners of a 4 x 4 x 4 grid: a query between them, inside the points' box, walks rings of
+    empty cells and stops when the ring's reach passes the bound with nothing met (-1, inf)"""
+    rng = np.random.default_rng(9)
+    r = np.concatenate([rng.uniform(0.0, 0.3, (6, 3)), rng.uniform(3.6, 3.9, (6, 3))])
+    q = np.concatenate([rng.uniform(1.6, 2.4, (30, 3)), rng.uniform(0.0, 0.5, (5, 3)), rng.uniform(3.4, 3.9, (5, 3))])
+    rd = _check_nearest(q, r, bound=0.5, cell=1.0)
+    assert (rd[:30] == math.inf).all() and (rd[30:] <= 0.5).sum() >= 5
+    d, i = _E().nearest(torch.as_tensor(q, device=DEV), torch.as_tensor(r, device=DEV), 0.5, cell=1.0)
+    assert (_np(i)[:30] == -1).all()
+
+
 def test_nearest_far_queries_and_one_point_reference():
     rng = np.random.default_rng(7)
     r = rng.uniform(0, 1, (2000, 3))
