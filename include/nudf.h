@@ -23,7 +23,8 @@ extern "C" {
  *        md_ fields, appended at its end.  (nudf_pc_raycast and its md_ray_o ... md_count fields were appended later under
  *        the same number: the size table below refuses a package and a library that disagree on the struct's size;
  *        nudf_meshsmooth_* and the sm_ fields at the end of NudfMeshOrient likewise, and nudf_meshsubdiv_* with the sp_sd_
- *        fields at the end of NudfMeshTopo: the version stays 111)
+ *        fields at the end of NudfMeshTopo, and nudf_meshhole_* with the sp_sd_hf_ fields after those and the new
+ *        NUDF_HOLE_ constants: the version stays 111)
  *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
@@ -1262,6 +1263,31 @@ typedef struct NudfMeshTopo {
   double sp_sd_max_edge;             /* mark: > 0 and finite unless sp_sd_mark_all                                   */
   int32_t sp_sd_scheme;              /* odd, even: 0 midpoint, 1 loop                                                */
   int32_t sp_sd_mark_all;            /* mark: non-zero marks every edge with u != v                                  */
+  /* hole closing (nudf_meshhole_*, below), appended WITHOUT a version step; the prefix stays sp_sd_ for the reason above.
+   * Read too, in their first meaning: `faces`, `edges`, `he_edge`, `edge_key`, `pos`, n_faces, n_verts, n_edges.  Reused
+   * with the item changed from a boundary vertex to a loop: new_count [sp_sd_hf_n_loops] the triangles of each loop
+   * (count), new_off their exclusive prefix sum (triangulate), new_faces [n_new, 3] and n_new (triangulate), and
+   * max_loop, here the longest loop that is closed, 3 ... NUDF_HOLE_MAX_EDGES (count, triangulate).  `labels`,
+   * `changed`, `nbr*` and `bverts` are not reused: a state's label travels with its jump and distance in one row of
+   * sp_sd_hf_rank_*, no round reports a change, and the border here is a list of edges, not of vertices */
+  const int64_t* sp_sd_hf_bedge;     /* [sp_sd_hf_n_border] the rows of `edges` with count 1, ascending (link)       */
+  const int64_t* sp_sd_hf_brank;     /* [n_edges] position of the edge in sp_sd_hf_bedge, or -1 (link)               */
+  int64_t* sp_sd_hf_link;            /* [2 sp_sd_hf_n_border] partner of state 2 b + end, or -1 (link)               */
+  const int64_t* sp_sd_hf_rank_in;   /* [2 sp_sd_hf_n_border, 3] (jump, smallest state id, distance to it) (rank)    */
+  int64_t* sp_sd_hf_rank_out;        /* [2 sp_sd_hf_n_border, 3] the same after the round; not sp_sd_hf_rank_in      */
+  const int64_t* sp_sd_hf_loop_off;  /* [sp_sd_hf_n_loops + 1] CSR offsets of the loops (count, triangulate)         */
+  const int64_t* sp_sd_hf_loop_vertex; /* [sp_sd_hf_n_items] vertex at which each edge is entered (count, triangulate) */
+  const int64_t* sp_sd_hf_loop_edge; /* [sp_sd_hf_n_items] the rows of `edges` in loop order (count, triangulate)    */
+  const uint8_t* sp_sd_hf_closed;    /* [sp_sd_hf_n_loops] 1: a closed loop, 0: a chain between blocked ends (count) */
+  double* sp_sd_hf_perimeter;        /* [sp_sd_hf_n_loops] (count)                                                   */
+  int8_t* sp_sd_hf_status;           /* [sp_sd_hf_n_loops] NUDF_HOLE_ (count: written; triangulate: read, and        */
+                                     /* NUDF_HOLE_DUPLICATE written for a refused loop)                              */
+  int64_t sp_sd_hf_n_border;
+  int64_t sp_sd_hf_n_loops;
+  int64_t sp_sd_hf_n_items;          /* entries of sp_sd_hf_loop_vertex / _edge: sp_sd_hf_n_border for a full table  */
+  double sp_sd_hf_max_perimeter;     /* count: > 0; +inf for no bound                                                */
+  int32_t sp_sd_hf_round;            /* rank: the round r = 0, 1, ...: the spans read are 2^r states long            */
+  int32_t sp_sd_hf_pad_;
 } NudfMeshTopo;
 int nudf_meshtopo_edges(const NudfMeshTopo* args, void* stream);       /* one thread per unique edge      */
 int nudf_meshtopo_fill_count(const NudfMeshTopo* args, void* stream);  /* one thread per boundary vertex  */
@@ -1341,6 +1367,70 @@ int nudf_meshsubdiv_odd(const NudfMeshTopo* args, void* stream);       /* one th
 int nudf_meshsubdiv_even(const NudfMeshTopo* args, void* stream);      /* one thread per vertex           */
 int nudf_meshsubdiv_count(const NudfMeshTopo* args, void* stream);     /* one thread per face             */
 int nudf_meshsubdiv_emit(const NudfMeshTopo* args, void* stream);      /* one thread per face             */
+
+/* ------------------------------------------------------------------------------------
+ * Hole closing (neuraludf_amd/meshclean.py border_loops, close_holes): the border loops of a mesh, defined through the
+ * fans of its surface, and the minimum-area triangulation of those of up to NUDF_HOLE_MAX_EDGES edges (Barequet and
+ * Sharir 1995; the area term of Liepa's weight).  nudf_meshtopo_fill_* mirror trimesh's fill_holes and stop at 4 edges;
+ * the reference's users take longer holes to MeshLab or pymeshfix on the CPU.  The entry points take NudfMeshTopo and
+ * read the sp_sd_hf_ fields at its end (no version step, as for the subdivision).  The caller sorts and scans between the
+ * launches; float64 without contracted multiply-adds, every sum in list order inside one thread, no atomics: every
+ * result is identical from run to run and equals tests/meshhole_ref.py bit for bit.
+ * A border edge is a row of `edges` with count 1; border edge b = sp_sd_hf_bedge[b] has the ends 0 (its u) and 1 (its v),
+ * and state 2 b + end names the pair.
+ *   link         one thread per state: the fan walk around v, the vertex at that end.  It starts in the edge's face and
+ *                steps across the face's other edge at v into the neighbouring face for as long as that edge has count 2;
+ *                at the first edge of another count it ends: count 1 is the linked border edge b', and
+ *                sp_sd_hf_link[s] = 2 b' + (the end of b' that is v); count 3 and more is a blocked end, -1.  Blocked
+ *                too: a face with a repeated vertex (the first included), a walk that returns to its first face, more
+ *                than NUDF_HOLE_FAN_CAP faces, a linked edge with u = v.  The link pairs the states and does not look at
+ *                the winding; the border edges fall into closed loops and into chains between two blocked ends;
+ *   rank         one thread per directed state (2 b + the end the edge is entered by), one pointer-doubling round r:
+ *                with (j, m, d) = sp_sd_hf_rank_in[s] and (j', m', d') = sp_sd_hf_rank_in[j], sp_sd_hf_rank_out[s] =
+ *                (j', m', 2^r + d') when m' < m, else (j', m, d); a j outside [0, 2 sp_sd_hf_n_border) copies the row.
+ *                The caller starts from (succ(s), s, 0), succ(s) = link[s ^ 1] (across the edge, then along the link) or,
+ *                at a blocked end, s ^ 1 (back along the chain: a chain of n edges is a cycle of 2 n states, a loop two
+ *                cycles of n, one per direction), and runs ceil(log2(2 B)) + 1 rounds between two buffers: then m is the
+ *                smallest state of the cycle and d the steps to it;
+ *   count        one thread per loop l of the CSR sp_sd_hf_loop_off: sp_sd_hf_perimeter[l] = the lengths
+ *                sqrt((dx dx + dy dy) + dz dz), d = pos[u] - pos[v], of its edges summed in loop order from the first;
+ *                sp_sd_hf_status[l] = the first that holds of NUDF_HOLE_OPEN_CHAIN (sp_sd_hf_closed[l] is 0),
+ *                _TOO_MANY_EDGES (more than max_loop), _REPEATED_VERTEX (a vertex twice in sp_sd_hf_loop_vertex),
+ *                _NONFINITE (a coordinate of a loop vertex or the perimeter), _PERIMETER (perimeter >
+ *                sp_sd_hf_max_perimeter), else _FILLED; new_count[l] = n - 2 for _FILLED, else 0;
+ *   triangulate  one wavefront per loop with status _FILLED and vertices v_0 ... v_n-1.  W[i][i + 1] = 0 and, diagonal
+ *                by diagonal d = j - i = 2 ... n - 1 with the cells of one across the lanes, W[i][j] = the minimum over
+ *                i < k < j of (W[i][k] + W[k][j]) + A(i, k, j), A = 0.5 sqrt(|(v_k - v_i) x (v_j - v_i)|^2); k ascends
+ *                and only a strictly smaller value replaces the first, split[i][j] = that k.  W, split and the positions
+ *                live in LDS (under 40 KB for the workgroup).  One lane lists the n - 2 triangles (i, k, j) in pre-order
+ *                from (0, n - 1): the triangle, then (i, k), then (k, j).  Every chord (i, j) of that list but the
+ *                root's is a diagonal and is looked up in edge_key; if one is an edge already, or for n = 3 when the three
+ *                border edges have one and the same face, the loop is refused whole: status _DUPLICATE and its rows of
+ *                new_faces set to -1.  Otherwise row new_off[l] + t is (v_i, v_k, v_j) of triangle t, or (v_i, v_j, v_k)
+ *                when more than half of the loop's border edges run, in the face next to them, in loop direction: the
+ *                patch runs against the majority of its neighbours and keeps the loop's direction on a tie.
+ * An index read from a table that is out of range blocks the end (link), copies the row (rank), gives status _NONFINITE
+ * and a NaN perimeter (count) or leaves the loop's rows as they were (triangulate); nothing is addressed outside the
+ * buffers.  Host-side refusals (no launch): negative counts, counts above their bound (sp_sd_hf_n_border <= n_edges;
+ * sp_sd_hf_n_loops, sp_sd_hf_n_items, n_new <= sp_sd_hf_n_border), NULL buffers, max_loop outside
+ * [3, NUDF_HOLE_MAX_EDGES], a sp_sd_hf_max_perimeter that is not positive, a round outside [0, 40], equal rank buffers.
+ * Empty jobs return 0.
+ * ---------------------------------------------------------------------------------- */
+#define NUDF_HOLE_MAX_EDGES 64
+#define NUDF_HOLE_FAN_CAP 4096
+enum {
+  NUDF_HOLE_FILLED = 0,
+  NUDF_HOLE_OPEN_CHAIN = 1,
+  NUDF_HOLE_TOO_MANY_EDGES = 2,
+  NUDF_HOLE_PERIMETER = 3,
+  NUDF_HOLE_NONFINITE = 4,
+  NUDF_HOLE_DUPLICATE = 5,
+  NUDF_HOLE_REPEATED_VERTEX = 6
+};
+int nudf_meshhole_link(const NudfMeshTopo* args, void* stream);        /* one thread per (border edge, end) */
+int nudf_meshhole_rank(const NudfMeshTopo* args, void* stream);        /* one thread per directed state     */
+int nudf_meshhole_count(const NudfMeshTopo* args, void* stream);       /* one thread per loop               */
+int nudf_meshhole_triangulate(const NudfMeshTopo* args, void* stream); /* one wavefront per loop            */
 
 /* ------------------------------------------------------------------------------------
  * Consistent face orientation and vertex normals (neuraludf_amd/meshclean.py orient_faces, vertex_normals): the step the

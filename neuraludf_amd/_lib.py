@@ -255,7 +255,13 @@ class MeshTopo(C.Structure):
                 ("sp_sd_fcount", c_fp), ("sp_sd_foff", c_fp), ("sp_sd_faces_out", c_fp), ("sp_sd_parent", c_fp),
                 ("sp_sd_n_ring", C.c_int64), ("sp_sd_n_border", C.c_int64), ("sp_sd_n_marked", C.c_int64),
                 ("sp_sd_n_out", C.c_int64), ("sp_sd_max_edge", C.c_double), ("sp_sd_scheme", i32),
-                ("sp_sd_mark_all", i32)]
+                ("sp_sd_mark_all", i32),
+                ("sp_sd_hf_bedge", c_fp), ("sp_sd_hf_brank", c_fp), ("sp_sd_hf_link", c_fp), ("sp_sd_hf_rank_in", c_fp),
+                ("sp_sd_hf_rank_out", c_fp), ("sp_sd_hf_loop_off", c_fp), ("sp_sd_hf_loop_vertex", c_fp),
+                ("sp_sd_hf_loop_edge", c_fp), ("sp_sd_hf_closed", c_fp), ("sp_sd_hf_perimeter", c_fp),
+                ("sp_sd_hf_status", c_fp), ("sp_sd_hf_n_border", C.c_int64), ("sp_sd_hf_n_loops", C.c_int64),
+                ("sp_sd_hf_n_items", C.c_int64), ("sp_sd_hf_max_perimeter", C.c_double), ("sp_sd_hf_round", i32),
+                ("sp_sd_hf_pad_", i32)]
 
 
 class MeshOrient(C.Structure):
@@ -283,6 +289,11 @@ LW_COUNT = 16
 
 EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMOID=7, UDFHEAD=8,
            SKIPSPLIT=9, RELU_DUAL=10, ADDMASK=11, MULSP=12)
+
+# the status of a border loop after close_holes (include/nudf.h NUDF_HOLE_*)
+HOLE = dict(FILLED=0, OPEN_CHAIN=1, TOO_MANY_EDGES=2, PERIMETER=3, NONFINITE=4, DUPLICATE=5, REPEATED_VERTEX=6)
+HOLE_MAX_EDGES = 64
+HOLE_FAN_CAP = 4096
 
 # the ctypes mirror of every argument struct, under the header's name: NudfX is the class X above, without exception
 MIRRORS = {"Nudf" + c.__name__: c for c in C.Structure.__subclasses__() if c.__module__ == __name__}
@@ -369,7 +380,7 @@ SIGNATURES = {
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces", "meshsubdiv_mark", "meshsubdiv_odd", "meshsubdiv_even", "meshsubdiv_count",
-                    "meshsubdiv_emit")),
+                    "meshsubdiv_emit", "meshhole_link", "meshhole_rank", "meshhole_count", "meshhole_triangulate")),
         (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals",
                       "meshsmooth_laplace", "meshsmooth_frames", "meshsmooth_normals", "meshsmooth_update")),
         (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",

@@ -3,6 +3,10 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
 
     edge table   mesh_edges          unique undirected edges with their faces; boundary edges are those of count 1
     holes        fill_holes          extract_mesh.py:222-223 (trimesh fill_holes): loops of 3 get one triangle, of 4 two
+    loops        border_loops, close_holes    the border as canonical closed loops and open chains, linked through the fans of
+                                     the surface, and the loops of up to 64 edges closed with their minimum-area
+                                     triangulation (csrc/meshhole.hip; MeshLab or pymeshfix on the CPU): the holes of 5 to
+                                     30 edges that MeshUDF leaves where its gradient is unreliable
     borders      smooth_borders      extract_mesh.py:238-265: 5 Jacobi steps of the border Laplacian, lambda = 0.3
     components   face_components, filter_components     clean_dtu_mesh.py:158-191
     orientation  orient_faces        consistent winding per component (csrc/meshorient.hip); the reference leaves it out
@@ -28,8 +32,14 @@ torch's (stable sort, integer prefix sums): every result is identical from run t
 Where the definitions differ from the libraries the reference calls:
   * trimesh takes the boundary loops from a networkx cycle basis, which is not canonical where borders touch.  Here a hole
     is a closed loop of 3 or 4 boundary edges all of whose vertices have boundary degree exactly 2 (the loop is then a
-    whole connected component of the boundary graph), and for a 3-loop the triangle must not exist already.  Longer loops
-    stay open.  The winding of a new face is a vote over its boundary edges (see fill_holes).
+    whole connected component of the boundary graph), and for a 3-loop the triangle must not exist already.  fill_holes
+    leaves longer loops open.  The winding of a new face is a vote over its boundary edges (see fill_holes).
+  * border_loops and close_holes do not go by the border degree: two border edges belong together at a vertex when the
+    fan of faces around it leads from one to the other over edges with exactly two faces.  That is canonical where
+    borders touch, does not look at the winding, and ends in an open chain where an edge with three faces or a face with a
+    repeated vertex is in the way.  close_holes closes the closed loops of up to MAX_HOLE_EDGES = 64 edges (Barequet and
+    Sharir's minimum-area triangulation, the area term of Liepa's weight) and says per loop why it did not; refining and
+    fairing a patch is left to subdivide_to_edge and smooth_mesh(fixed=...).
   * two faces are adjacent when they share an undirected edge of any multiplicity; trimesh's face_adjacency pairs only
     the edges with exactly two faces.
   * orient_faces links faces over the edges with exactly two faces only (trimesh's face_adjacency, here on purpose: an
@@ -56,6 +66,11 @@ HULL_BORDER = 50             # clean_dtu_mesh.py:88
 HULL_MAX_OUTSIDE = 5         # clean_dtu_mesh.py:105
 SIMPLIFY_MAX_GRID = 1 << 20  # cells per axis: a cluster key (cx Gy + cy) Gz + cz stays below 2^60
 SIMPLIFY_BISECT_ROUNDS = 24
+MAX_HOLE_EDGES = _lib.HOLE_MAX_EDGES     # close_holes: W of the longest loop, 64 x 64 doubles, fits the LDS of a workgroup
+# close_holes: the status of a border loop, the first that applies in the order of its docstring
+HOLE_FILLED, HOLE_OPEN_CHAIN, HOLE_TOO_MANY_EDGES, HOLE_PERIMETER, HOLE_NONFINITE, HOLE_DUPLICATE, HOLE_REPEATED_VERTEX = (
+    _lib.HOLE[k] for k in ("FILLED", "OPEN_CHAIN", "TOO_MANY_EDGES", "PERIMETER", "NONFINITE", "DUPLICATE", "REPEATED_VERTEX"))
+HOLE_STATUS_NAMES = {v: k.lower() for k, v in _lib.HOLE.items()}
 
 
 class EdgeTable(NamedTuple):
@@ -193,6 +208,225 @@ def fill_holes(verts, faces, max_loop=4):
     d.new_off, d.new_faces, d.n_new = ptr(off), ptr(new), n_new
     call("nudf_meshtopo_fill_emit", d)
     return torch.cat([faces, new]), int((count > 0).sum())
+
+
+class BorderLoops(NamedTuple):
+    """loop_off [L + 1] CSR offsets; loop_vertex: the vertex at which each border edge is entered, in the loop's canonical
+    order (edge i runs from loop_vertex[i] to loop_vertex[i + 1], the last of a closed loop back to the first; the far end of
+    a chain's last edge is not listed); loop_edge: the rows of the EdgeTable, same CSR; closed [L] bool; perimeter [L]
+    float64, the edge lengths summed in loop order; edge_loop [E] int64: the loop of each border edge, -1 for other edges"""
+    loop_off: torch.Tensor
+    loop_vertex: torch.Tensor
+    loop_edge: torch.Tensor
+    closed: torch.Tensor
+    perimeter: torch.Tensor
+    edge_loop: torch.Tensor
+
+
+class ClosedHoles(NamedTuple):
+    """faces [F + n, 3] int64, the input's followed by the patches loop by loop in loop-id order; new_face_loop [n] int64:
+    the loop (border_loops' id) each new face closes; status [L] int8: one HOLE_ code per loop"""
+    faces: torch.Tensor
+    new_face_loop: torch.Tensor
+    status: torch.Tensor
+
+
+def _hole_loops(d, table, n_verts, events=None, state=None, _rounds=None):
+    """link, the rank rounds and the glue between and after them -> (loop_off, loop_vertex, loop_edge, closed uint8,
+    edge_loop, link); d holds the mesh and its table and receives the border lists, which the caller keeps alive through the
+    returned tuple's last entry"""
+    e, dev = table.edges, table.edges.device
+    n_edges = e.shape[0]
+    _stage(events, state, "glue")
+    bedge = torch.nonzero(e[:, 2] == 1).reshape(-1)
+    n_border = bedge.numel()
+    brank = torch.full((n_edges,), -1, dtype=torch.int64, device=dev)
+    brank[bedge] = torch.arange(n_border, dtype=torch.int64, device=dev)
+    link = torch.empty(2 * n_border, dtype=torch.int64, device=dev)
+    d.sp_sd_hf_bedge, d.sp_sd_hf_brank, d.sp_sd_hf_link, d.sp_sd_hf_n_border = ptr(bedge), ptr(brank), ptr(link), n_border
+    _stage(events, state, "link")
+    call("nudf_meshhole_link", d)
+    _stage(events, state, "glue2")
+    s = torch.arange(2 * n_border, dtype=torch.int64, device=dev)
+    over = link[s ^ 1]
+    tab = torch.stack([torch.where(over >= 0, over, s ^ 1), s, torch.zeros_like(s)], 1).contiguous()
+    other = torch.empty_like(tab)
+    _stage(events, state, "rank")
+    for r in range((2 * n_border - 1).bit_length() + 1 if n_border else 0):
+        d.sp_sd_hf_rank_in, d.sp_sd_hf_rank_out, d.sp_sd_hf_round = ptr(tab), ptr(other), r
+        call("nudf_meshhole_rank", d)
+        tab, other = other, tab
+        if _rounds is not None:
+            _rounds.append(tab.clone())
+    _stage(events, state, "glue3")
+    # every state lies on a cycle (a closed loop: one per direction; a chain: there and back): m its smallest state, dist
+    # the steps to it
+    m, dist = tab[:, 1], tab[:, 2]
+    n = 2 * n_border
+    chain = m == m[s ^ 1]
+    length = torch.bincount(m, minlength=n)[m]
+    first = torch.full((n,), n, dtype=torch.int64, device=dev)           # per cycle: the smaller of a chain's two start states
+    starts = s[link < 0]
+    by_cycle = torch.sort(m[starts], stable=True)                         # starts ascend: the first of a cycle is the smaller
+    lead = torch.ones(starts.numel(), dtype=torch.bool, device=dev)
+    if starts.numel():
+        lead[1:] = by_cycle.values[1:] != by_cycle.values[:-1]
+    first[by_cycle.values[lead]] = starts[by_cycle.indices[lead]]
+    origin = torch.where(chain, first[m], m)
+    origin = torch.where(origin < n, origin, m)
+    pos = torch.remainder(dist[origin] - dist, length)
+    canonical = torch.where(chain, 2 * pos < length, m < m[s ^ 1])
+    label = torch.minimum(m, m[s ^ 1]) >> 1                                # the loop's smallest border edge
+    cs = s[canonical]
+    cs = cs[torch.sort(pos[cs], stable=True).indices]
+    cs = cs[torch.sort(label[cs], stable=True).indices]
+    lab = label[cs]
+    head = torch.ones(cs.numel(), dtype=torch.bool, device=dev)
+    if cs.numel():
+        head[1:] = lab[1:] != lab[:-1]
+    start = torch.nonzero(head).reshape(-1)
+    loop_off = torch.cat([start, torch.full((1,), cs.numel(), dtype=torch.int64, device=dev)])
+    loop_edge = bedge[cs >> 1].contiguous()
+    loop_vertex = e[loop_edge, cs & 1].contiguous()
+    closed = (~chain[cs[start]]).to(torch.uint8).contiguous()
+    edge_loop = torch.full((n_edges,), -1, dtype=torch.int64, device=dev)
+    edge_loop[loop_edge] = torch.cumsum(head, 0) - 1
+    return loop_off, loop_vertex, loop_edge, closed, edge_loop, (bedge, brank, link)
+
+
+def _hole_count(d, pos, loops, max_edges, max_perimeter):
+    """launches count -> (perimeter [L], status [L] int8, new_count [L]); d keeps pointers into `loops`"""
+    loop_off, loop_vertex, loop_edge, closed = loops[:4]
+    n_loops, dev = closed.numel(), closed.device
+    perimeter = torch.empty(n_loops, dtype=torch.float64, device=dev)
+    status = torch.empty(n_loops, dtype=torch.int8, device=dev)
+    count = torch.empty(n_loops, dtype=torch.int64, device=dev)
+    d.pos, d.max_loop, d.sp_sd_hf_max_perimeter = ptr(pos), max_edges, math.inf if max_perimeter is None else max_perimeter
+    d.sp_sd_hf_loop_off, d.sp_sd_hf_loop_vertex, d.sp_sd_hf_loop_edge = ptr(loop_off), ptr(loop_vertex), ptr(loop_edge)
+    d.sp_sd_hf_closed, d.sp_sd_hf_n_loops, d.sp_sd_hf_n_items = ptr(closed), n_loops, loop_edge.numel()
+    d.sp_sd_hf_perimeter, d.sp_sd_hf_status, d.new_count = ptr(perimeter), ptr(status), ptr(count)
+    call("nudf_meshhole_count", d)
+    return perimeter, status, count
+
+
+def _empty_loops(n_edges, dev):
+    z = torch.zeros(0, dtype=torch.int64, device=dev)
+    return BorderLoops(torch.zeros(1, dtype=torch.int64, device=dev), z, z.clone(), torch.zeros(0, dtype=torch.bool, device=dev),
+                       torch.zeros(0, dtype=torch.float64, device=dev), torch.full((n_edges,), -1, dtype=torch.int64, device=dev))
+
+
+def border_loops(verts, faces):
+    """the border of the mesh as closed loops and open chains -> BorderLoops (csrc/meshhole.hip).  A border edge is an edge
+    with one face.  At each of its two ends the fan of the surface is walked: from the edge's face across the face's other
+    edge at that vertex into the next face, for as long as that edge has exactly two faces.  The first edge with one face
+    is the border edge linked to this one at this end; an edge with three or more faces blocks the end, as does a face
+    with a repeated vertex.  The link is mutual and does not look at the winding, so the border edges fall into disjoint
+    closed loops and into open chains whose two ends are blocked; borders that touch in a vertex come apart into the loops
+    that the surface around the vertex dictates (trimesh takes the loops from a cycle basis, which is not canonical there).
+    Loops are numbered by their smallest border edge (row of the EdgeTable).  A closed loop starts with that edge, entered
+    at its smaller vertex; a chain starts at the one of its two blocked ends whose (edge, end) pair is smaller.  Found by
+    pointer doubling over the (edge, direction) states, ceil(log2(2 B)) + 1 rounds for B border edges, with stable sorts
+    and scans in torch between the launches: identical from run to run, and unchanged by flipping faces."""
+    verts, faces = _check_mesh(verts, faces)
+    n_verts, dev = verts.shape[0], faces.device
+    if faces.shape[0] == 0:
+        return _empty_loops(0, dev)
+    table = _mesh_edges(faces, n_verts)
+    d = _topo(faces, n_verts, table)
+    loops = _hole_loops(d, table, n_verts)
+    if loops[3].numel() == 0:
+        return _empty_loops(table.edges.shape[0], dev)
+    perimeter, _, _ = _hole_count(d, verts.double().contiguous(), loops, MAX_HOLE_EDGES, None)
+    return BorderLoops(loops[0], loops[1], loops[2], loops[3].bool(), perimeter, loops[4])
+
+
+def _shared_patch_edges(new, face_loop, n_verts):
+    """the loops whose patch has an edge that the patch of a loop with a smaller id has too (two holes through the same two
+    vertices): one stable sort of the patches' half-edge keys"""
+    a, b = new.reshape(-1), new.roll(-1, 1).reshape(-1)
+    key, loop = torch.minimum(a, b) * n_verts + torch.maximum(a, b), face_loop.repeat_interleave(3)
+    sk, order = torch.sort(key, stable=True)
+    sl = loop[order]                                   # ascending inside a key: the rows are in loop order
+    first = torch.ones(sk.numel(), dtype=torch.bool, device=new.device)
+    first[1:] = sk[1:] != sk[:-1]
+    owner = sl[first][torch.cumsum(first, 0) - 1]
+    return torch.unique(sl[sl != owner])
+
+
+def close_holes(verts, faces, max_edges=32, max_perimeter=None, _info=None):
+    """closes the border loops (border_loops) of up to `max_edges` <= MAX_HOLE_EDGES = 64 edges with their minimum-area
+    triangulation -> ClosedHoles(faces, new_face_loop, status) (csrc/meshhole.hip; MeshLab's and pymeshfix's hole filling on
+    the CPU; fill_holes, which mirrors trimesh, stops at 4 edges and at borders that touch).  status [L] holds one code per
+    loop, the first that applies: HOLE_OPEN_CHAIN (not a closed loop), HOLE_TOO_MANY_EDGES, HOLE_REPEATED_VERTEX (the loop
+    passes a vertex twice: left open), HOLE_NONFINITE (a coordinate or the perimeter), HOLE_PERIMETER (perimeter above
+    `max_perimeter`, when given), HOLE_DUPLICATE (the patch would duplicate an edge or face, see below), else HOLE_FILLED.
+    A loop v_0 ... v_n-1 in canonical order gets the triangulation of least total area (Barequet and Sharir; the area
+    term of Liepa's weight, without the dihedral term): W[i][i + 1] = 0, W[i][j] = min over i < k < j of
+    (W[i][k] + W[k][j]) + A(i, k, j) with A = 0.5 sqrt(|(v_k - v_i) x (v_j - v_i)|^2) in float64, k ascending, the first
+    strictly smaller value wins; the n - 2 triangles follow in pre-order from (0, n - 1): (i, k, j), then those of (i, k),
+    then those of (k, j).  Winding: a triangle is (v_i, v_k, v_j) unless more than half of the loop's border edges run in
+    loop direction in the face next to them, then (v_i, v_j, v_k): the patch runs against the majority of its neighbours
+    (the vote of fill_holes), a tie keeps the loop's direction.  Refusal: when a diagonal of the chosen triangulation is an
+    edge of the mesh already, or a 3-loop is the border of a single face, the loop is left open whole; so is a loop whose
+    patch shares an edge with the patch of a loop of smaller id.  No edge gains a third face.  One pass: a patch makes no
+    new border.  The patches are as coarse as their loops: refine and fair them with subdivide_to_edge and
+    smooth_mesh(fixed=...) with every old vertex fixed.  Identical from run to run; unchanged in its set of filled loops by
+    relabelling the vertices.  (`_info`: a dict that receives loops (BorderLoops) and, when it holds a dict under
+    "events", a pair of events per stage.)"""
+    try:
+        ok = int(max_edges) == max_edges and 3 <= int(max_edges) <= MAX_HOLE_EDGES
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"max_edges must be an integer in [3, {MAX_HOLE_EDGES}] (got {max_edges!r})")
+    max_edges = int(max_edges)
+    if max_perimeter is not None:
+        max_perimeter = _finite(max_perimeter, "max_perimeter", positive=True)
+    verts, faces = _check_mesh(verts, faces)
+    n_verts, dev = verts.shape[0], faces.device
+    none = torch.zeros(0, dtype=torch.int64, device=dev)
+    events, state = None if _info is None else _info.get("events"), {}
+    if faces.shape[0] == 0:
+        if _info is not None:
+            _info["loops"] = _empty_loops(0, dev)
+        return ClosedHoles(faces, none, torch.zeros(0, dtype=torch.int8, device=dev))
+    _stage(events, state, "edges")
+    table = _mesh_edges(faces, n_verts)
+    d = _topo(faces, n_verts, table)
+    loops = _hole_loops(d, table, n_verts, events, state)
+    if loops[3].numel() == 0:
+        _stage(events, state, None)
+        if _info is not None:
+            _info["loops"] = _empty_loops(table.edges.shape[0], dev)
+        return ClosedHoles(faces, none, torch.zeros(0, dtype=torch.int8, device=dev))
+    pos = verts.double().contiguous()
+    _stage(events, state, "count")
+    perimeter, status, count = _hole_count(d, pos, loops, max_edges, max_perimeter)
+    if _info is not None:
+        _info["loops"] = BorderLoops(loops[0], loops[1], loops[2], loops[3].bool(), perimeter, loops[4])
+    _stage(events, state, "glue4")
+    ends = torch.cumsum(count, 0)
+    n_new = int(ends[-1])
+    if n_new == 0:
+        _stage(events, state, None)
+        return ClosedHoles(faces, none, status)
+    off = ends - count
+    new = torch.full((n_new, 3), -1, dtype=torch.int64, device=dev)
+    d.new_off, d.new_faces, d.n_new = ptr(off), ptr(new), n_new
+    _stage(events, state, "triangulate")
+    call("nudf_meshhole_triangulate", d)
+    _stage(events, state, "glue5")
+    face_loop = torch.arange(count.numel(), dtype=torch.int64, device=dev).repeat_interleave(count)
+    keep = new[:, 0] >= 0
+    new, face_loop = new[keep], face_loop[keep]
+    bad = _shared_patch_edges(new, face_loop, n_verts)
+    if bad.numel():
+        status[bad] = HOLE_DUPLICATE
+        keep = ~torch.isin(face_loop, bad)
+        new, face_loop = new[keep], face_loop[keep]
+    out = ClosedHoles(torch.cat([faces, new]), face_loop, status)
+    _stage(events, state, None)
+    return out
 
 
 def smooth_borders(verts, faces, iterations=5, lam=0.3):

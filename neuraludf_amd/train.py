@@ -510,8 +510,8 @@ class Trainer:
         """open-surface mesh of the UDF in the [-1, 1]^3 box (Runner.extract_udf_mesh, exp_runner_blending.py:763-800,
         without its file output; neuraludf_amd.meshing.extract_udf_mesh) -> (vertices np.float32 [V, 3], faces np.int64
         [F, 3]).  world_space: map the vertices with `scale_mat` (the dataset's scale_mats_np[0]) as the runner does.
-        `clean`: the clean-up keywords of meshing.extract_udf_mesh (fill_holes, smooth_borders, min_component_faces,
-        keep_largest), all off by default, and its sparse=True, block, lipschitz (query and mesh only the blocks near the
+        `clean`: the clean-up keywords of meshing.extract_udf_mesh (fill_holes, close_holes, close_holes_perimeter,
+        smooth_borders, min_component_faces, keep_largest), all off by default, and its sparse=True, block, lipschitz (query and mesh only the blocks near the
         surface: the same mesh as long as the UDF is no steeper than `lipschitz`, resolutions up to 4096), and
         orient=True / outward_from=(x, y, z) in the box's coordinates (wind the faces of every orientable component
         consistently as the last step, away from that point when given), and color_from=(world_mats, images) -- the pair
