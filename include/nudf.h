@@ -1157,6 +1157,42 @@ int nudf_pc_closest(const NudfPointCloud* args, void* stream);       /* one thre
 int nudf_pc_raycast(const NudfPointCloud* args, void* stream);       /* one thread per ray   */
 
 /* ------------------------------------------------------------------------------------
+ * Intersecting faces (neuraludf_amd/evaluation.py MeshIndex.intersections, self_intersections, mesh_intersections;
+ * meshclean.drop_self_intersections, close_holes_checked): replaces MeshLab's "select self intersecting faces", libigl's
+ * and pymeshfix's tests, which a caller leaves the GPU for.  The index is the one built for nudf_pc_closest.  NO new
+ * struct, field or version step: the two entry points read NudfPointCloud's fields as follows.
+ *   verts, faces, n_verts, n_faces, origin, cell, grid, box_lo, box_hi, cell_start, cell_count, n_cells, hash_key,
+ *   hash_row, hash_cap, md_cell_face, md_n_refs     the indexed mesh, as nudf_pc_closest reads them;
+ *   md_mode      0 self: the query triangles are the faces of the indexed mesh (n_query == n_faces, query unused), only
+ *                pairs g > t are looked at and faces that share vertices by index follow the shared-vertex rules;
+ *                1 two meshes: query [n_query, 3, 3] holds the corner coordinates of the other mesh's triangles;
+ *   md_ref_n     [n_query] the pairs of each query triangle (written by isect_count, read by isect_emit);
+ *   md_ref_off   [n_query] their exclusive prefix sum (isect_emit);
+ *   md_ref_key, md_ref_face, state   [cap] the query triangle, the indexed face and the kind of each pair (isect_emit);
+ *   cap          the rows of those three buffers: the total the caller accepted.  A row at or beyond it is not written.
+ *   isect_count  one thread per query triangle t: md_ref_n[t] = the pairs it reports (0 for an absent triangle: an index
+ *                out of range, a non-finite coordinate);
+ *   isect_emit   one thread per query triangle t: its pairs at rows md_ref_off[t] ..., in the order of its walk through
+ *                the cells.  The caller sorts them.
+ * Both run one device function, without atomics.  Broad phase: t walks the cells its box touches, drops a candidate whose
+ * box does not overlap its own (closed, exact) and handles a pair only in the cell that holds the lower corner of the two
+ * boxes' intersection: each pair once, whatever the cell size.  Narrow phase (equal to
+ * tests/meshintersect_ref.py bit for bit): signs of orient3d / orient2d on input coordinates in Shewchuk's operation
+ * order, certified by his stage-A bound ((7 + 56 e) e permanent, (3 + 16 e) e detsum, e = 2^-53; bound > 2^-960), float64
+ * without contraction.  The contract: a pair that is not reported is disjoint in exact arithmetic, apart from the shared
+ * vertices (the shared edge, where two are shared); a CROSSING pair shares a point in exact arithmetic (one that is not
+ * the shared vertex); COPLANAR and UNCERTAIN pairs touch, overlap in a plane or come closer than float64 can tell.
+ * Host-side refusals (no launch): NULL buffers, cell <= 0 or not finite, a grid axis outside [1, 2^21], a bad hash_cap,
+ * n_faces, n_verts or n_query >= 2^31, an unknown md_mode, n_query != n_faces in self mode, cap < 0.  Empty descriptors
+ * (n_query <= 0; for isect_emit also cap == 0) return 0.
+ * ---------------------------------------------------------------------------------- */
+#define NUDF_ISECT_CROSSING 1   /* the two faces pass through each other                                               */
+#define NUDF_ISECT_COPLANAR 2   /* no certified separating edge in the common (or nearly common) plane; a fold        */
+#define NUDF_ISECT_UNCERTAIN 3  /* a sign that float64 with the stage-A filter cannot certify                          */
+int nudf_pc_isect_count(const NudfPointCloud* args, void* stream);   /* one thread per query triangle */
+int nudf_pc_isect_emit(const NudfPointCloud* args, void* stream);    /* one thread per query triangle */
+
+/* ------------------------------------------------------------------------------------
  * Mesh topology for the mesh clean-up (neuraludf_amd/meshclean.py): replaces what the reference does with trimesh,
  * networkx, scipy.sparse and cv2 on the CPU -- trimesh's fill_holes (extract_mesh.py:222-223), the border smoothing
  * (extract_mesh.py:238-265), clean_mesh_by_faces_num / clean_outliers (evaluation/clean_dtu_mesh.py:158-191) and

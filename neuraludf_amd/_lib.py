@@ -294,6 +294,8 @@ EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMO
 HOLE = dict(FILLED=0, OPEN_CHAIN=1, TOO_MANY_EDGES=2, PERIMETER=3, NONFINITE=4, DUPLICATE=5, REPEATED_VERTEX=6)
 HOLE_MAX_EDGES = 64
 HOLE_FAN_CAP = 4096
+# the kind of a reported pair of faces (include/nudf.h NUDF_ISECT_*, csrc/meshintersect.hip)
+ISECT = dict(CROSSING=1, COPLANAR=2, UNCERTAIN=3)
 
 # the ctypes mirror of every argument struct, under the header's name: NudfX is the class X above, without exception
 MIRRORS = {"Nudf" + c.__name__: c for c in C.Structure.__subclasses__() if c.__module__ == __name__}
@@ -376,7 +378,8 @@ SIGNATURES = {
         (IsoSurfaceSparse, ("isosurface_sparse_classify", "isosurface_sparse_edges", "isosurface_sparse_emit",
                             "isosurface_sparse_vertices")),
         (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest",
-                      "pc_tribin_count", "pc_tribin_emit", "pc_closest", "pc_raycast")),
+                      "pc_tribin_count", "pc_tribin_emit", "pc_closest", "pc_raycast", "pc_isect_count",
+                      "pc_isect_emit")),
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces", "meshsubdiv_mark", "meshsubdiv_odd", "meshsubdiv_even", "meshsubdiv_count",

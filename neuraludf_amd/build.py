@@ -18,13 +18,14 @@ LIB = os.path.join(HERE, "libnudf.so")
 SOURCES = ["nudf_api.hip", "gemm_f32_mfma.hip", "gemm_tn_f32_mfma.hip", "rays_embed.hip", "composite.hip", "upsample.hip",
            "blend.hip", "optim.hip", "mlp_chain.hip", "mlp_chain_rows.hip", "raybatch.hip", "meshudf.hip",
            "meshudf_sparse.hip", "isosurface.hip", "pointcloud.hip", "meshtopo.hip", "meshorient.hip", "meshraster.hip",
-           "meshsimplify.hip", "meshdist.hip", "meshray.hip", "meshsmooth.hip", "meshsubdiv.hip", "meshhole.hip"]
+           "meshsimplify.hip", "meshdist.hip", "meshray.hip", "meshsmooth.hip", "meshsubdiv.hip", "meshhole.hip",
+           "meshintersect.hip"]
 
 
 # the sources that decide what a kernel class reads and writes (bench.py `roofline.traffic_stale`: a PMC traffic file under
 # profiles/ is only as good as the kernel it was recorded on)
 _MESH_COMMON = ["csrc/f64_exact.h", "csrc/mesh_launch.h", "csrc/nudf_common.h", "../include/nudf.h"]   # every mesh file
-_CELL_INDEX = ["csrc/cell_index.h"]                        # the three that build or search the hashed grid
+_CELL_INDEX = ["csrc/cell_index.h"]                        # the files that build or search the hashed grid
 KERNEL_SOURCES = {
     "mlp_chain": ["csrc/mlp_chain.hip", "csrc/mlp_chain_rows.hip", "csrc/mlp_chain_shared.h", "csrc/nudf_common.h",
                   "../include/nudf.h", "mlp.py"],
@@ -42,6 +43,7 @@ KERNEL_SOURCES = {
     "meshsimplify": ["csrc/meshsimplify.hip", *_MESH_COMMON],
     "meshdist": ["csrc/meshdist.hip", *_CELL_INDEX, *_MESH_COMMON],
     "meshray": ["csrc/meshray.hip", *_CELL_INDEX, *_MESH_COMMON],
+    "meshintersect": ["csrc/meshintersect.hip", *_CELL_INDEX, *_MESH_COMMON],
     "meshsmooth": ["csrc/meshsmooth.hip", *_MESH_COMMON],
     "meshsubdiv": ["csrc/meshsubdiv.hip", *_MESH_COMMON],
     "meshhole": ["csrc/meshhole.hip", *_MESH_COMMON],

@@ -20,6 +20,10 @@ their open3d file I/O, Python down-sampling loop and sklearn KD-trees replaced.
                                     (csrc/meshray.hip): first hit, any hit, the number of faces crossed; inside / outside
                                     by crossing parity and the signed distance; what trimesh.ray and Trimesh.contains
                                     answer on the CPU
+    crossings   MeshIndex.intersections, self_intersections, mesh_intersections    the pairs of faces that pass through
+                                    each other, in one mesh or between two (csrc/meshintersect.hip): filtered orient3d /
+                                    orient2d signs over the same index; what MeshLab's "select self intersecting faces",
+                                    libigl and pymeshfix answer on the CPU
 
 Given the permutation, every step is the reference's float64 computation in its operation order, so the points, the
 masks and the distances equal a numpy restatement bit for bit (tests/pointcloud_ref.py); only the means are summed in
@@ -34,6 +38,7 @@ Non-finite points raise ValueError before thinning or a nearest-neighbour search
         [--dataset_dir D --scan N] [--downsample_density ...] [--patch_size ...] [--max_dist ...]
         [--visualize_threshold ...] [--vis_out_dir ...] [--no_vis] [--log ...] [--seed 0]
     python -m neuraludf_amd.evaluation deviation --a A.ply --b B.ply [--density D] [--bound B] [--log FILE]
+    python -m neuraludf_amd.evaluation intersections --mesh A.ply [--other B.ply] [--out FLAGGED.ply]
 """
 from __future__ import annotations
 
@@ -57,6 +62,9 @@ MESH_CELL_FACTOR = 3.0          # MeshIndex: default cell / mean longest box sid
 MAX_MESH_REFS = 1 << 27         # MeshIndex: most (cell, face) references accepted by default (16 B each, and the sort's copy)
 MAX_MESH_REFS_LIMIT = 1 << 40   # the kernels' cap (csrc/meshdist.hip MD_MAX_CAP)
 RAY_MODES = ("first", "any", "count")    # cast_rays: the values of md_mode (csrc/meshray.hip)
+MAX_ISECT_PAIRS = 1 << 26       # intersections: most reported pairs accepted by default (17 B each, and the sort's copy)
+ISECT_KINDS = {"crossing": _lib.ISECT["CROSSING"], "coplanar": _lib.ISECT["COPLANAR"],
+               "uncertain": _lib.ISECT["UNCERTAIN"]}       # the kind of a pair (csrc/meshintersect.hip)
 # contains_points: three fixed directions in general position (no component zero, no two equal in magnitude, pairwise far
 # from parallel), so that a ray meets an edge or a vertex of an axis-aligned or regularly gridded mesh only by accident
 INSIDE_DIRECTIONS = ((0.5370861555295747, 0.2915274230636872, 0.7915368220043530),
@@ -330,6 +338,24 @@ class Closest(NamedTuple):
     bary: torch.Tensor
 
 
+class Intersections(NamedTuple):
+    """pairs [P, 2] int64 sorted by (a, b): in a self run two faces of the mesh, a < b; against another mesh (face of that
+    mesh, face of the indexed mesh).  kind [P] int8, a value of ISECT_KINDS.  face_mask [F] bool: the faces of the indexed
+    mesh that are in a pair."""
+    pairs: torch.Tensor
+    kind: torch.Tensor
+    face_mask: torch.Tensor
+
+
+class MeshIntersections(NamedTuple):
+    """pairs [P, 2] int64 (face of a, face of b) sorted; kind [P] int8; mask_a [Fa] bool, mask_b [Fb] bool: the faces of
+    either mesh that are in a pair"""
+    pairs: torch.Tensor
+    kind: torch.Tensor
+    mask_a: torch.Tensor
+    mask_b: torch.Tensor
+
+
 def _check_face_array(faces):
     f = torch.as_tensor(faces) if not isinstance(faces, torch.Tensor) else faces
     if f.dim() != 2 or f.shape[1] != 3 or f.is_floating_point() or f.is_complex() or f.dtype == torch.bool:
@@ -518,6 +544,59 @@ class MeshIndex:
             return out
         return count != 0 if mode == "any" else count
 
+    def intersections(self, other=None, max_pairs=MAX_ISECT_PAIRS, _events=None):
+        """the faces of this mesh that pass through each other, or with `other` ((vertices, faces) or a MeshIndex) the
+        faces of that mesh against the faces of this one -> Intersections (self_intersections, mesh_intersections;
+        csrc/meshintersect.hip isect_count / isect_emit, a torch int64 scan between them and one stable sort of the pairs
+        after them).  More than `max_pairs` reported pairs raise ValueError after the count pass.
+        (`_events`: receives the stages count, scan, emit, sort.)"""
+        try:
+            ok = int(max_pairs) == max_pairs and int(max_pairs) >= 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"max_pairs must be a non-negative integer (got {max_pairs!r})")
+        max_pairs = int(max_pairs)
+        dev, nf = self.vertices.device, self.faces.shape[0]
+        if other is None:
+            corners, nq = None, nf
+        else:
+            ov, of = _mesh_arrays(other, "other", dev)
+            corners, nq = ov[of].contiguous(), of.shape[0]
+        empty = torch.zeros(0, dtype=torch.int64, device=dev)
+        mask = torch.zeros(nf, dtype=torch.bool, device=dev)
+        if nq == 0:
+            return Intersections(empty.reshape(0, 2), empty.to(torch.int8), mask)
+        ref_n = torch.empty(nq, dtype=torch.int64, device=dev)
+        d, cap = self.d, self.d.cap
+        d.query, d.n_query, d.md_mode, d.md_ref_n, d.cap = ptr(corners), nq, 0 if other is None else 1, ptr(ref_n), max_pairs
+        try:
+            _stage(_events, "count")
+            call("nudf_pc_isect_count", d)
+            _stage(_events, "scan")
+            ends = torch.cumsum(ref_n, 0)
+            total = int(ends[-1])
+            if total > max_pairs:
+                raise ValueError(f"{total} intersecting pairs exceed max_pairs={max_pairs}")
+            _stage(_events, "emit")
+            off = (ends - ref_n).contiguous()
+            a = torch.empty(total, dtype=torch.int64, device=dev)
+            b = torch.empty(total, dtype=torch.int64, device=dev)
+            kind = torch.empty(total, dtype=torch.uint8, device=dev)
+            d.md_ref_off, d.md_ref_key, d.md_ref_face, d.state, d.cap = ptr(off), ptr(a), ptr(b), ptr(kind), total
+            call("nudf_pc_isect_emit", d)
+            _stage(_events, "sort")
+            order = torch.sort(a * nf + b, stable=True).indices
+            pairs, kind = torch.stack([a[order], b[order]], 1), kind[order].to(torch.int8)
+        finally:
+            _stage(_events, None)
+            d.query = d.md_ref_n = d.md_ref_off = d.md_ref_key = d.md_ref_face = d.state = None
+            d.n_query, d.md_mode, d.cap = 0, 0, cap
+        mask[pairs[:, 1]] = True
+        if other is None:
+            mask[pairs[:, 0]] = True
+        return Intersections(pairs, kind, mask)
+
 
 def closest_on_mesh(query, vertices=None, faces=None, bound=math.inf, *, index=None, cell=None):
     """the closest point of a triangle mesh for every point of `query` [M, 3], exactly (what
@@ -638,6 +717,80 @@ def _as_index(m, name):
     if not isinstance(m, (tuple, list)) or len(m) != 2:
         raise ValueError(f"{name} must be (vertices, faces) or a MeshIndex")
     return MeshIndex(m[0], m[1])
+
+
+def _mesh_arrays(m, name, dev):
+    """(vertices float64 [V, 3], faces int64 [F, 3]) on dev of a MeshIndex or a (vertices, faces) pair; ValueError for an
+    index out of range"""
+    if isinstance(m, MeshIndex):
+        return m.vertices.to(dev), m.faces.to(dev)
+    if not isinstance(m, (tuple, list)) or len(m) != 2:
+        raise ValueError(f"{name} must be (vertices, faces) or a MeshIndex")
+    _shape3(m[0], f"{name} vertices")
+    f = _check_face_array(m[1]).to(device=dev, dtype=torch.int64).contiguous()
+    v = _points(m[0], f"{name} vertices", dev, finite=False)
+    if f.numel() and (int(f.min()) < 0 or int(f.max()) >= v.shape[0]):
+        raise ValueError(f"{name}: face index out of range [0, {v.shape[0]})")
+    return v, f
+
+
+# ---- intersecting faces --------------------------------------------------------------------------------------------------
+def self_intersections(vertices=None, faces=None, *, index=None, cell=None, max_pairs=MAX_ISECT_PAIRS):
+    """the pairs of faces of a mesh that pass through each other (MeshLab's "select self intersecting faces", libigl's
+    and pymeshfix's test on the CPU) -> Intersections(pairs [P, 2] with a < b, kind, face_mask) on the GPU.
+
+    Every decision is the sign of an orient3d or orient2d of input coordinates, in Shewchuk's operation order with his
+    stage-A error bound: a certified sign is the exact sign, anything else is uncertain.  Kinds (ISECT_KINDS):
+    "crossing": the faces share a point in exact arithmetic (Guigue and Devillers' interval test; for faces with one
+    common vertex, the edge opposite to it in one face pierces the other); "coplanar": the faces lie in one plane as far
+    as float64 can tell and no edge separates them, or two faces over a common edge are folded onto each other;
+    "uncertain": some sign could not be certified and the six edges, each against the other face, do not decide either
+    -- the faces touch or come closer than float64 resolves.  A pair that
+    is not reported is disjoint in exact arithmetic apart from its shared vertices (its shared edge); faces with the same
+    three vertices are not reported (the edge table sees them).  The kind is a function of the ordered pair and of the
+    corner order of its faces: certification, not the exact answer, can differ between the two orders of a nearly
+    degenerate pair.  The pairs and kinds equal tests/meshintersect_ref.py bit for bit and do not depend on the cell
+    size.  A face with a NaN vertex is absent.  Pass either (vertices, faces[, cell]) or a MeshIndex as `index`."""
+    if index is None:
+        if vertices is None or faces is None:
+            raise ValueError("self_intersections needs (vertices, faces) or index=MeshIndex(...)")
+        index = MeshIndex(vertices, faces, cell=cell)
+    elif vertices is not None or faces is not None or cell is not None:
+        raise ValueError("pass either (vertices, faces[, cell]) or index, not both")
+    elif not isinstance(index, MeshIndex):
+        raise ValueError("index must be a MeshIndex")
+    return index.intersections(max_pairs=max_pairs)
+
+
+def mesh_intersections(a, b, max_pairs=MAX_ISECT_PAIRS):
+    """the faces of mesh `a` that pass through faces of mesh `b`, each (vertices, faces) or a MeshIndex ->
+    MeshIntersections(pairs (face of a, face of b), kind, mask_a, mask_b); the rule of self_intersections for faces
+    without a common vertex.  The mesh with more faces is indexed (b on a tie), unless one of them comes as a MeshIndex
+    already; the triangles of the other are the queries."""
+    if isinstance(a, MeshIndex) and not isinstance(b, MeshIndex):
+        index_a = True
+    elif isinstance(b, MeshIndex):
+        index_a = False
+    else:
+        for m, name in ((a, "a"), (b, "b")):
+            if not isinstance(m, (tuple, list)) or len(m) != 2:
+                raise ValueError(f"{name} must be (vertices, faces) or a MeshIndex")
+        index_a = _check_face_array(a[1]).shape[0] > _check_face_array(b[1]).shape[0]
+    if index_a:
+        ia = _as_index(a, "a")
+        r = ia.intersections(b, max_pairs)                       # (face of b, face of a)
+        nb = _mesh_arrays(b, "b", ia.vertices.device)[1].shape[0]
+        order = torch.sort(r.pairs[:, 1] * max(nb, 1) + r.pairs[:, 0], stable=True).indices
+        pairs, kind, mask_a = r.pairs[order].flip(1).contiguous(), r.kind[order], r.face_mask
+        mask_b = torch.zeros(nb, dtype=torch.bool, device=pairs.device)
+        mask_b[pairs[:, 1]] = True
+        return MeshIntersections(pairs, kind, mask_a, mask_b)
+    ib = _as_index(b, "b")
+    r = ib.intersections(a, max_pairs)
+    na = _mesh_arrays(a, "a", ib.vertices.device)[1].shape[0]
+    mask_a = torch.zeros(na, dtype=torch.bool, device=r.pairs.device)
+    mask_a[r.pairs[:, 0]] = True
+    return MeshIntersections(r.pairs, r.kind, mask_a, r.face_mask)
 
 
 def _one_sided(src, dst, density, bound):
@@ -898,12 +1051,49 @@ def _main_deviation(argv):
     return 0
 
 
+def _main_intersections(argv):
+    from .meshing import read_ply, write_ply
+    ap = argparse.ArgumentParser(prog="python -m neuraludf_amd.evaluation intersections",
+                                 description="the faces of a mesh that pass through each other, or through another mesh")
+    ap.add_argument("--mesh", type=str, required=True, help="the mesh (PLY with faces)")
+    ap.add_argument("--other", type=str, default=None, help="a second mesh: its faces against the first's")
+    ap.add_argument("--out", type=str, default=None, help="write the mesh with its flagged faces coloured (PLY)")
+    a = ap.parse_args(argv)
+    meshes = []
+    for path in (a.mesh, a.other):
+        if path is None:
+            continue
+        v, f = read_ply(path)
+        if f is None:
+            raise SystemExit(f"{path} holds no faces")
+        meshes.append((torch.as_tensor(np.asarray(v, dtype=np.float64)), torch.as_tensor(np.asarray(f))))
+    if a.other is None:
+        res = self_intersections(*meshes[0])
+        mask = res.face_mask
+    else:
+        res = mesh_intersections(meshes[0], meshes[1])
+        mask = res.mask_a
+    counts = {name: int((res.kind == k).sum()) for name, k in ISECT_KINDS.items()}
+    print(f"pairs: {res.pairs.shape[0]}; " + "; ".join(f"{k}: {v}" for k, v in counts.items())
+          + f"; flagged faces: {int(mask.sum())} of {mask.numel()}.")
+    if a.out is not None:
+        # a vertex of a flagged face is red, the others grey (PLY colours live on vertices)
+        v, f = meshes[0]
+        flagged = torch.zeros(v.shape[0], dtype=torch.bool)
+        flagged[f.to(torch.int64)[mask.cpu()].reshape(-1)] = True
+        colors = np.where(flagged.numpy()[:, None], np.array([[255, 0, 0]], np.uint8), np.array([[160, 160, 160]], np.uint8))
+        write_ply(a.out, v.numpy(), f.numpy(), colors=colors)
+    return 0
+
+
 def main(argv=None):
     from pathlib import Path
     from .meshing import read_ply
     argv = sys.argv[1:] if argv is None else list(argv)
     if argv and argv[0] == "deviation":            # the third protocol word has arguments of its own
         return _main_deviation(argv[1:])
+    if argv and argv[0] == "intersections":
+        return _main_intersections(argv[1:])
     ap = argparse.ArgumentParser(prog="python -m neuraludf_amd.evaluation", description=__doc__.split("\n\n")[0])
     ap.add_argument("protocol", choices=sorted(PROTOCOLS))
     ap.add_argument("--data", type=str, default="data_in.ply")

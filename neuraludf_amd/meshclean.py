@@ -7,6 +7,9 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
                                      the surface, and the loops of up to 64 edges closed with their minimum-area
                                      triangulation (csrc/meshhole.hip; MeshLab or pymeshfix on the CPU): the holes of 5 to
                                      30 edges that MeshUDF leaves where its gradient is unreliable
+    crossings    close_holes_checked, drop_self_intersections    the patches that pass through the surface taken back, the
+                                     faces that pass through or lie folded onto each other dropped
+                                     (evaluation.self_intersections, csrc/meshintersect.hip; MeshLab or pymeshfix on the CPU)
     borders      smooth_borders      extract_mesh.py:238-265: 5 Jacobi steps of the border Laplacian, lambda = 0.3
     components   face_components, filter_components     clean_dtu_mesh.py:158-191
     orientation  orient_faces        consistent winding per component (csrc/meshorient.hip); the reference leaves it out
@@ -427,6 +430,67 @@ def close_holes(verts, faces, max_edges=32, max_perimeter=None, _info=None):
     out = ClosedHoles(torch.cat([faces, new]), face_loop, status)
     _stage(events, state, None)
     return out
+
+
+def _isect_kinds(kinds):
+    from . import evaluation                                 # lazily: evaluation imports meshing, which imports this file
+    kinds = (kinds,) if isinstance(kinds, str) else tuple(kinds)
+    for k in kinds:
+        if k not in evaluation.ISECT_KINDS:
+            raise ValueError(f"kinds must be among {tuple(evaluation.ISECT_KINDS)} (got {k!r})")
+    return [evaluation.ISECT_KINDS[k] for k in kinds]
+
+
+def _pairs_of_kinds(res, kinds):
+    """the pairs of an evaluation.Intersections whose kind is one of the codes `kinds`"""
+    hit = torch.zeros_like(res.kind, dtype=torch.bool)
+    for k in kinds:
+        hit |= res.kind == k
+    return res.pairs[hit]
+
+
+def drop_self_intersections(verts, faces, kinds=("crossing", "coplanar")):
+    """drops every face that is in a pair of evaluation.self_intersections of one of `kinds` ("crossing", "coplanar",
+    "uncertain"; csrc/meshintersect.hip), then the vertices no face uses any more (compact_mesh) -> (verts', faces', the
+    number of faces dropped).  Both faces of a pair go: which of the two is the wrong one is not a question signs answer.
+    Dropping faces makes no new pair, so a second call finds nothing of these kinds.  The repair stops here: the holes
+    this leaves are border loops like any other (close_holes)."""
+    from . import evaluation
+    codes = _isect_kinds(kinds)
+    verts, faces = _check_mesh(verts, faces)
+    if faces.shape[0] == 0:
+        return verts, faces, 0
+    res = evaluation.self_intersections(verts, faces)
+    keep = torch.ones(faces.shape[0], dtype=torch.bool, device=faces.device)
+    keep[_pairs_of_kinds(res, codes).reshape(-1)] = False
+    dropped = int((~keep).sum())
+    if dropped == 0:
+        return verts, faces, 0
+    return compact_mesh(verts, faces, face_mask=keep) + (dropped,)
+
+
+def close_holes_checked(verts, faces, max_edges=32, max_perimeter=None):
+    """close_holes, then evaluation.self_intersections on the closed mesh: the patch of every loop that has a new face in a
+    "crossing" or "coplanar" pair -- with an old face or with a face of another patch -- is taken back whole, since the
+    minimum-area triangulation of a rim looks at the rim alone and can cut through the surface next to it or through
+    something standing in the hole -> (ClosedHoles of what is kept, the ids [K] int64 of the loops taken back,
+    ascending).  The status of a loop taken back stays what close_holes gave it (HOLE_FILLED); its faces are gone from
+    `faces` and `new_face_loop`.  Pairs among the old faces take nothing back: they were there before."""
+    from . import evaluation
+    closed = close_holes(verts, faces, max_edges, max_perimeter)
+    n_old, n_new = faces.shape[0], closed.new_face_loop.numel()
+    none = torch.zeros(0, dtype=torch.int64, device=closed.faces.device)
+    if n_new == 0:
+        return closed, none
+    res = evaluation.self_intersections(verts, closed.faces)
+    hit = _pairs_of_kinds(res, _isect_kinds(("crossing", "coplanar"))).reshape(-1)
+    hit = hit[hit >= n_old] - n_old
+    if hit.numel() == 0:
+        return closed, none
+    bad = torch.unique(closed.new_face_loop[hit])
+    keep = ~torch.isin(closed.new_face_loop, bad)
+    kept = torch.cat([closed.faces[:n_old], closed.faces[n_old:][keep]])
+    return ClosedHoles(kept, closed.new_face_loop[keep], closed.status), bad
 
 
 def smooth_borders(verts, faces, iterations=5, lam=0.3):
