@@ -1193,6 +1193,42 @@ int nudf_pc_isect_count(const NudfPointCloud* args, void* stream);   /* one thre
 int nudf_pc_isect_emit(const NudfPointCloud* args, void* stream);    /* one thread per query triangle */
 
 /* ------------------------------------------------------------------------------------
+ * Generalised winding numbers (neuraludf_amd/evaluation.py MeshIndex.winding, winding_number, contains_points and
+ * signed_distance with method="winding"): inside / outside that survives holes and open sheets; replaces libigl's
+ * fast_winding_number, which a caller leaves the GPU for.  NO new struct, field or version step: the three entry points
+ * read NudfPointCloud's fields as follows (restated in tests/meshwinding_ref.py).
+ *   verts, faces, n_verts, n_faces, origin, cell, grid    the mesh and the leaf grid: origin is the lower corner of the box
+ *                of the usable faces, cell the leaf edge, grid the cells per axis (all three entry points check them);
+ *   wn_faces     one thread per item t < n_query.  md_mode 0 (n_query == n_faces): keys[t] = the Morton interleave (x the
+ *                highest bit of each triple) of the leaf cell of the centroid (p0 + (p1 + p2)) / 3 of face t, clamped into
+ *                the grid; -1 for an absent face (an index out of range, a non-finite vertex, an area vector
+ *                1/2 (p1 - p0) x (p2 - p0) of zero or non-finite length).  md_mode 1: keys[t] = the key of the cell of point
+ *                query[t] (the driver's coherence sort);
+ *   md_cell_face, md_n_refs   the usable faces sorted by key (stable) and their number;
+ *   n, rank, cell_start, cell_count   the nodes of the linear octree in preorder, rank[i] = skip[i] the first node behind
+ *                node i's subtree (a leaf has skip[i] == i + 1), cell_start / cell_count the range of node i's faces in
+ *                md_cell_face;
+ *   wn_nodes     one thread per node query_idx[t], t < n_query: the nodes of ONE level, the lowest level first.  Writes
+ *                out[40 i ...] = the raw moments about origin (W, M[3], S[3], T0[9], Q0[18], box lo[3], hi[3]): a leaf adds
+ *                its faces in sorted order, a parent the raw moments of its children in preorder; and md_point[32 i ...] =
+ *                the node record (centre[3], r2, S[3], T diagonal[3], T_jk + T_kj[3], Q[18], tr T), moments shifted to
+ *                the area-weighted centre;
+ *   winding      pts [n, 32] the node records (what wn_nodes wrote through md_point), r2 = beta * beta (>= 1; inf: no node
+ *                is ever replaced, the exact sum), query [n_query, 3] / query_idx (NULL: the identity) / n_query the
+ *                points.  Writes dist[query_idx[t]] = w, and where the pointers are not NULL md_count[...] = the faces
+ *                evaluated exactly and idx[...] = the nodes replaced by their expansion.  One wavefront walks the preorder
+ *                for its 64 queries together with a wave-uniform node index; per query the result is that of the
+ *                single-query walk, bit for bit.
+ * No atomics, no LDS, no scratch memory.  Float64 without contraction; only atan2 is not defined to the bit.
+ * Host-side refusals (no launch): NULL buffers, cell <= 0 or not finite, a grid axis outside [1, 2^21], a non-finite
+ * origin, n_query, n_faces, n_verts, n or md_n_refs >= 2^31, an unknown md_mode or n_query != n_faces (wn_faces), no
+ * nodes or no faces (wn_nodes, winding), beta * beta < 1 or NaN (winding).  Empty descriptors (n_query <= 0) return 0.
+ * ---------------------------------------------------------------------------------- */
+int nudf_pc_wn_faces(const NudfPointCloud* args, void* stream);      /* one thread per face (or point) */
+int nudf_pc_wn_nodes(const NudfPointCloud* args, void* stream);      /* one thread per node of a level */
+int nudf_pc_winding(const NudfPointCloud* args, void* stream);       /* one wavefront per 64 queries   */
+
+/* ------------------------------------------------------------------------------------
  * Mesh topology for the mesh clean-up (neuraludf_amd/meshclean.py): replaces what the reference does with trimesh,
  * networkx, scipy.sparse and cv2 on the CPU -- trimesh's fill_holes (extract_mesh.py:222-223), the border smoothing
  * (extract_mesh.py:238-265), clean_mesh_by_faces_num / clean_outliers (evaluation/clean_dtu_mesh.py:158-191) and

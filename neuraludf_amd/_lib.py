@@ -379,7 +379,7 @@ SIGNATURES = {
                             "isosurface_sparse_vertices")),
         (PointCloud, ("pc_tri_count", "pc_tri_emit", "pc_keys", "pc_cells", "pc_thin_round", "pc_nearest",
                       "pc_tribin_count", "pc_tribin_emit", "pc_closest", "pc_raycast", "pc_isect_count",
-                      "pc_isect_emit")),
+                      "pc_isect_emit", "pc_wn_faces", "pc_wn_nodes", "pc_winding")),
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces", "meshsubdiv_mark", "meshsubdiv_odd", "meshsubdiv_even", "meshsubdiv_count",

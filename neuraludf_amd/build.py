@@ -19,7 +19,7 @@ SOURCES = ["nudf_api.hip", "gemm_f32_mfma.hip", "gemm_tn_f32_mfma.hip", "rays_em
            "blend.hip", "optim.hip", "mlp_chain.hip", "mlp_chain_rows.hip", "raybatch.hip", "meshudf.hip",
            "meshudf_sparse.hip", "isosurface.hip", "pointcloud.hip", "meshtopo.hip", "meshorient.hip", "meshraster.hip",
            "meshsimplify.hip", "meshdist.hip", "meshray.hip", "meshsmooth.hip", "meshsubdiv.hip", "meshhole.hip",
-           "meshintersect.hip"]
+           "meshintersect.hip", "meshwinding.hip"]
 
 
 # the sources that decide what a kernel class reads and writes (bench.py `roofline.traffic_stale`: a PMC traffic file under
@@ -44,6 +44,7 @@ KERNEL_SOURCES = {
     "meshdist": ["csrc/meshdist.hip", *_CELL_INDEX, *_MESH_COMMON],
     "meshray": ["csrc/meshray.hip", *_CELL_INDEX, *_MESH_COMMON],
     "meshintersect": ["csrc/meshintersect.hip", *_CELL_INDEX, *_MESH_COMMON],
+    "meshwinding": ["csrc/meshwinding.hip", *_CELL_INDEX, *_MESH_COMMON],
     "meshsmooth": ["csrc/meshsmooth.hip", *_MESH_COMMON],
     "meshsubdiv": ["csrc/meshsubdiv.hip", *_MESH_COMMON],
     "meshhole": ["csrc/meshhole.hip", *_MESH_COMMON],
