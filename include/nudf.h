@@ -24,7 +24,8 @@ extern "C" {
  *        the same number: the size table below refuses a package and a library that disagree on the struct's size;
  *        nudf_meshsmooth_* and the sm_ fields at the end of NudfMeshOrient likewise, and nudf_meshsubdiv_* with the sp_sd_
  *        fields at the end of NudfMeshTopo, and nudf_meshhole_* with the sp_sd_hf_ fields after those and the new
- *        NUDF_HOLE_ constants: the version stays 111)
+ *        NUDF_HOLE_ constants, and nudf_meshremesh_* with the sp_sd_hf_rm_ fields after those and the NUDF_REMESH_
+ *        constants: the version stays 111)
  *   110: nudf_meshsimplify_* (mesh simplification); NudfMeshTopo grows by the sp_ fields and n_clusters, appended at its end
  *   109: nudf_abi_struct (below) replaces the per-struct size exports and the step-count export that 108 had collected
  *        instead of version steps: the 20 steps of NudfChain (NUDF_CH_MAX_STEPS), NudfMeshUDFSparse, NudfIsoSurface,
@@ -1360,6 +1361,34 @@ typedef struct NudfMeshTopo {
   double sp_sd_hf_max_perimeter;     /* count: > 0; +inf for no bound                                                */
   int32_t sp_sd_hf_round;            /* rank: the round r = 0, 1, ...: the spans read are 2^r states long            */
   int32_t sp_sd_hf_pad_;
+  /* isotropic remeshing (nudf_meshremesh_*, below), appended WITHOUT a version step; the prefix grows to sp_sd_hf_rm_
+   * because the tests of the hole closing pin that every field after the subdivision's is named sp_sd_hf_...  Read too, in
+   * their first meaning: `faces`, `edges`, `he_edge`, `he_id`, `edge_start`, `edge_key`, `pos`, `nbr_off` / `nbr` with
+   * sp_sd_n_border (the border neighbours), sp_sd_ring_off / sp_sd_ring with sp_sd_n_ring (the one-rings), sp_sd_vclass,
+   * n_faces, n_verts, n_edges */
+  const int64_t* sp_sd_hf_rm_corner_off; /* [n_verts + 1] CSR offsets of the corners (collapse_check, vertex_min 2)  */
+  const int64_t* sp_sd_hf_rm_corner;     /* [3 n_faces] the corners 3 f + k by vertex, ascending inside each         */
+  const int64_t* sp_sd_hf_rm_vedge_off;  /* [n_verts + 1] CSR offsets of the incident edges (vertex_min 0, relax)    */
+  const int64_t* sp_sd_hf_rm_vedge;      /* [sp_sd_hf_rm_n_vedge] the rows of `edges` at each vertex                 */
+  uint8_t* sp_sd_hf_rm_status;           /* [n_edges] NUDF_REMESH_ (the checks: written; vertex_min, apply: read)    */
+  int64_t* sp_sd_hf_rm_keep;             /* [n_edges] the end that stays, or -1 (collapse_check; collapse_apply reads) */
+  int64_t* sp_sd_hf_rm_gone;             /* [n_edges] the end that goes, or -1                                       */
+  int32_t* sp_sd_hf_rm_gain;             /* [n_edges] fall of the squared valence deviation (flip_check)             */
+  int64_t* sp_sd_hf_rm_ab;               /* [n_edges, 2] the corners opposite the edge, or -1 (flip_check; flip_apply reads) */
+  const int64_t* sp_sd_hf_rm_rank;       /* [n_edges] place among the candidates, n_edges for none (vertex_min, apply) */
+  const int64_t* sp_sd_hf_rm_best_in;    /* [n_verts] (vertex_min 1; the apply kernels: the last pass's output)      */
+  int64_t* sp_sd_hf_rm_best_out;         /* [n_verts] (vertex_min); not sp_sd_hf_rm_best_in                          */
+  int64_t* sp_sd_hf_rm_remap;            /* [n_verts] preset to the identity (collapse_apply: the rows of the ends that go) */
+  double* sp_sd_hf_rm_pos_out;           /* [n_verts, 3] preset to a copy of pos (collapse_apply: the rows of the ends */
+                                         /* that stay; relax: every row)                                             */
+  int64_t* sp_sd_hf_rm_faces_out;        /* [n_faces, 3] preset to a copy of faces (flip_apply: the winners' two rows) */
+  uint8_t* sp_sd_hf_rm_win;              /* [n_edges] 1: the edge was collapsed / flipped (the apply kernels)        */
+  int64_t sp_sd_hf_rm_n_vedge;
+  double sp_sd_hf_rm_low;                /* collapse_check: an edge shorter than this is collapsed; > 0 and finite   */
+  double sp_sd_hf_rm_high;               /* collapse_check: no edge longer than this is made; > 0 and finite         */
+  double sp_sd_hf_rm_cos_border;         /* collapse_check: cosine of the largest turn of the border that is removed */
+  int32_t sp_sd_hf_rm_mode;              /* vertex_min: 0 edges at the vertex, 1 the one-ring, 2 edges of the faces  */
+  int32_t sp_sd_hf_rm_pad_;
 } NudfMeshTopo;
 int nudf_meshtopo_edges(const NudfMeshTopo* args, void* stream);       /* one thread per unique edge      */
 int nudf_meshtopo_fill_count(const NudfMeshTopo* args, void* stream);  /* one thread per boundary vertex  */
@@ -1503,6 +1532,97 @@ int nudf_meshhole_link(const NudfMeshTopo* args, void* stream);        /* one th
 int nudf_meshhole_rank(const NudfMeshTopo* args, void* stream);        /* one thread per directed state     */
 int nudf_meshhole_count(const NudfMeshTopo* args, void* stream);       /* one thread per loop               */
 int nudf_meshhole_triangulate(const NudfMeshTopo* args, void* stream); /* one wavefront per loop            */
+
+/* ------------------------------------------------------------------------------------
+ * Isotropic remeshing (neuraludf_amd/meshclean.py remesh_isotropic): the loop of Botsch and Kobbelt, "A remeshing approach
+ * to multiresolution modeling" (2004) -- split the long edges (nudf_meshsubdiv_*), collapse the short ones, flip towards
+ * valence 6, relax tangentially, project (nudf_pc_closest).  The reference has no such step: its users take the mesh to
+ * pymeshlab, CGAL or trimesh.remesh on the CPU.  The entry points take NudfMeshTopo and read the sp_sd_hf_rm_ fields at
+ * its end (no version step, as for the subdivision).  The caller sorts, ranks and compacts between the launches; float64
+ * without contracted multiply-adds, every sum in list order inside one thread, no atomics: every result is identical
+ * from run to run and equals tests/meshremesh_ref.py bit for bit.
+ * An edge is a row (u, v, count, ...) of `edges`, u < v.  The class of a vertex is sp_sd_vclass (0 smooth, 1 border with
+ * exactly two border edges, 2 stays), its valence the length of its one-ring, its target valence 6 (class 0) or 4 (class
+ * 1).  A face's normal is (p1 - p0) x (p2 - p0) with the corners rotated so that the smallest vertex index comes first:
+ * no bit of it depends on where the face's list starts, and reversing the face negates it exactly.  A status is the first
+ * NUDF_REMESH_ code that applies, in the order of the text.
+ *   collapse_check  one thread per edge: sp_sd_hf_rm_status, _keep, _gone (-1 unless a candidate).  _COUNT: count is
+ *                   neither 1 nor 2, or u = v.  _LONG: not (dx dx + dy dy) + dz dz < low low (a NaN fails).  _CLASS: an
+ *                   end of class 2.  Then for count 2: _BORDER when both ends are of class 1; with one such end it is
+ *                   kept and stays where it is, with none u is kept and moves to (p_u + p_v) 0.5.  For count 1 the ends
+ *                   are tried in the order (keep u, remove v), (keep v, remove u); the removed end g with its other
+ *                   border neighbour o (from `nbr`) must have cos_border < 1 and (p_g - p_o) . (p_k - p_g) >
+ *                   (cos_border |p_g - p_o|) |p_k - p_g| (the corners of the border stay; a cosine of 1 keeps every
+ *                   border vertex), and o must not be the corner opposite the edge (an ear would take a second border
+ *                   edge with it); the kept end stays where it is; _BORDER when neither order passes.  _LINK: the merge
+ *                   of the two ascending one-rings does not find exactly `count` common vertices.  _CLASS again: the
+ *                   one-ring of the removed end holds a vertex of class 2 (such a vertex keeps its faces).  _REACH: a vertex x of
+ *                   either one-ring other than u and v with not |p_x - p_new|^2 <= high high.  _FOLD: a face at u or v
+ *                   (corner lists) that does not hold both ends with not n_old . n_new > 0, n_new with both ends at
+ *                   p_new (independent of the winding; a NaN fails).  _DUPLICATE (count 2): with a, b the corners
+ *                   opposite the edge, the faces (u, a, b) and (v, a, b) both exist and would become one.  For count 1
+ *                   the order that first passes _CLASS, _REACH, _FOLD is taken; if none does the status is that of the first
+ *                   order whose border test passed;
+ *   vertex_min      one thread per vertex w, into sp_sd_hf_rm_best_out.  Mode 0: the smallest sp_sd_hf_rm_rank among the
+ *                   candidate edges (status 0) in w's list of sp_sd_hf_rm_vedge.  Mode 1: the minimum of
+ *                   sp_sd_hf_rm_best_in over w and its one-ring.  Mode 2: the smallest rank among the candidate edges
+ *                   that are one of the three edges (he_edge) of a face at w: the edges at w and those opposite it.
+ *                   "None" is n_edges.  The ranks are the caller's, a stable sort over the candidates: squared length
+ *                   ascending, then edge index (collapse); gain descending, then edge index (flip);
+ *   collapse_apply  one thread per edge: a candidate wins exactly when rank[e] = min(best_in[u], best_in[v]); it writes
+ *                   remap[gone] = keep, row keep of pos_out and win[e] = 1 (0 for every other edge).  With best_in =
+ *                   mode 0 followed by k passes of mode 1, best_in[u] is the smallest rank of a candidate with an end
+ *                   within k edges of u, so a winner e = (u, v) has the smallest rank of all candidates with an end
+ *                   within k edges of u or v.  If a second winner e' had an end x within k edges of u, then rank[e] <=
+ *                   rank[e'], and as u is within k edges of x also rank[e'] <= rank[e]: e' = e.  A collapse reads the
+ *                   one-rings of u and v and reads and changes only the faces at u and v; with k = 1 no winner has an
+ *                   end in N[u] + N[v] of another (closed neighbourhoods), so no face is at the ends of two winners and
+ *                   no vertex a winner reads moves; with k = 2, which the driver uses, N[u] + N[v] of two winners share
+ *                   no vertex at all.  The caller maps `faces` through remap and drops the faces with two equal corners;
+ *   flip_check      one thread per edge: status, sp_sd_hf_rm_gain, sp_sd_hf_rm_ab.  _COUNT: count is not 2, or u = v.
+ *                   With h0 = he_id[edge_start[e]], h1 the next, a and b the corners opposite h0 and h1 -- _SAME: a = b,
+ *                   or one of them is u or v.  _CLASS: one of u, v, a, b is of class 2.  _EXISTS: min(a, b) n_verts +
+ *                   max(a, b) is in edge_key.  _GAIN: not gain > 0, gain = the sum of (valence - target)^2 over the four
+ *                   minus the same with u and v one lower and a and b one higher.  _FOLD: child 0 is face(h0) with v
+ *                   replaced by b, child 1 face(h1) with u replaced by a (each keeps its parent's winding; the two
+ *                   children do not depend on the winding of either parent); with n0, n1 the parents' normals, m0, m1 the
+ *                   children's and c = +1 when h0 and h1 run against each other (the faces are wound alike), else -1,
+ *                   all of m0 . n0, m1 . n1, c (m0 . n1), c (m1 . n0) must be > 0;
+ *   flip_apply      one thread per edge: a candidate wins when rank[e] = best_in[x] (mode 2) for all four of u, v, a, b:
+ *                   e is an edge of a face at each of the four, so two winners share no vertex, hence no face and no new
+ *                   edge.  A winner writes its children into the parents' rows of faces_out and win[e] = 1;
+ *   relax           one thread per vertex: row w of pos_out.  Class 0 with a one-ring of n > 0 moves, everything else is
+ *                   copied.  q = (the sum of the ring in list order from its first entry) / n.  N is summed over the
+ *                   edges (w, x) of w's list of sp_sd_hf_rm_vedge in order and, per edge, over its first and second face
+ *                   in the order of their third vertices y: n = (p_x - p_w) x (p_y - p_w); the first n of finite
+ *                   non-zero length is taken as it is, each later one is added when its dot product with that first one
+ *                   is >= 0 and subtracted otherwise (the mesher's output is not consistently wound; nothing here
+ *                   depends on the winding or on the order of the faces).  With nh = N / |N| (correctly rounded square
+ *                   root and divisions) p' = q + ((p - q) . nh) nh; if |N| is 0 or not finite the vertex stays.
+ * An index read from a table that is out of range makes its item a no-op (a status other than 0, "none", no winner, a
+ * copy); nothing is addressed outside the buffers.  Host-side refusals (no launch): negative counts, NULL buffers, an
+ * unknown mode, equal best buffers, low / high not positive and finite, a cosine outside [-1, 1].  Empty jobs return 0.
+ * ---------------------------------------------------------------------------------- */
+enum {
+  NUDF_REMESH_CANDIDATE = 0,
+  NUDF_REMESH_COUNT = 1,
+  NUDF_REMESH_LONG = 2,
+  NUDF_REMESH_CLASS = 3,
+  NUDF_REMESH_BORDER = 4,
+  NUDF_REMESH_LINK = 5,
+  NUDF_REMESH_REACH = 6,
+  NUDF_REMESH_FOLD = 7,
+  NUDF_REMESH_DUPLICATE = 8,
+  NUDF_REMESH_SAME = 9,
+  NUDF_REMESH_EXISTS = 10,
+  NUDF_REMESH_GAIN = 11
+};
+int nudf_meshremesh_collapse_check(const NudfMeshTopo* args, void* stream); /* one thread per unique edge */
+int nudf_meshremesh_vertex_min(const NudfMeshTopo* args, void* stream);     /* one thread per vertex      */
+int nudf_meshremesh_collapse_apply(const NudfMeshTopo* args, void* stream); /* one thread per unique edge */
+int nudf_meshremesh_flip_check(const NudfMeshTopo* args, void* stream);     /* one thread per unique edge */
+int nudf_meshremesh_flip_apply(const NudfMeshTopo* args, void* stream);     /* one thread per unique edge */
+int nudf_meshremesh_relax(const NudfMeshTopo* args, void* stream);          /* one thread per vertex      */
 
 /* ------------------------------------------------------------------------------------
  * Consistent face orientation and vertex normals (neuraludf_amd/meshclean.py orient_faces, vertex_normals): the step the

@@ -261,7 +261,15 @@ class MeshTopo(C.Structure):
                 ("sp_sd_hf_loop_edge", c_fp), ("sp_sd_hf_closed", c_fp), ("sp_sd_hf_perimeter", c_fp),
                 ("sp_sd_hf_status", c_fp), ("sp_sd_hf_n_border", C.c_int64), ("sp_sd_hf_n_loops", C.c_int64),
                 ("sp_sd_hf_n_items", C.c_int64), ("sp_sd_hf_max_perimeter", C.c_double), ("sp_sd_hf_round", i32),
-                ("sp_sd_hf_pad_", i32)]
+                ("sp_sd_hf_pad_", i32),
+                ("sp_sd_hf_rm_corner_off", c_fp), ("sp_sd_hf_rm_corner", c_fp), ("sp_sd_hf_rm_vedge_off", c_fp),
+                ("sp_sd_hf_rm_vedge", c_fp), ("sp_sd_hf_rm_status", c_fp), ("sp_sd_hf_rm_keep", c_fp),
+                ("sp_sd_hf_rm_gone", c_fp), ("sp_sd_hf_rm_gain", c_fp), ("sp_sd_hf_rm_ab", c_fp),
+                ("sp_sd_hf_rm_rank", c_fp), ("sp_sd_hf_rm_best_in", c_fp), ("sp_sd_hf_rm_best_out", c_fp),
+                ("sp_sd_hf_rm_remap", c_fp), ("sp_sd_hf_rm_pos_out", c_fp), ("sp_sd_hf_rm_faces_out", c_fp),
+                ("sp_sd_hf_rm_win", c_fp), ("sp_sd_hf_rm_n_vedge", C.c_int64), ("sp_sd_hf_rm_low", C.c_double),
+                ("sp_sd_hf_rm_high", C.c_double), ("sp_sd_hf_rm_cos_border", C.c_double), ("sp_sd_hf_rm_mode", i32),
+                ("sp_sd_hf_rm_pad_", i32)]
 
 
 class MeshOrient(C.Structure):
@@ -294,6 +302,9 @@ EPI = dict(NONE=0, SOFTPLUS=1, RELU=2, MUL=3, MULMASK=4, TANGENT=5, BWD=6, SIGMO
 HOLE = dict(FILLED=0, OPEN_CHAIN=1, TOO_MANY_EDGES=2, PERIMETER=3, NONFINITE=4, DUPLICATE=5, REPEATED_VERTEX=6)
 HOLE_MAX_EDGES = 64
 HOLE_FAN_CAP = 4096
+# why an edge is not collapsed / flipped (include/nudf.h NUDF_REMESH_*, csrc/meshremesh.hip); 0: it is a candidate
+REMESH = dict(CANDIDATE=0, COUNT=1, LONG=2, CLASS=3, BORDER=4, LINK=5, REACH=6, FOLD=7, DUPLICATE=8, SAME=9, EXISTS=10,
+              GAIN=11)
 # the kind of a reported pair of faces (include/nudf.h NUDF_ISECT_*, csrc/meshintersect.hip)
 ISECT = dict(CROSSING=1, COPLANAR=2, UNCERTAIN=3)
 
@@ -383,7 +394,9 @@ SIGNATURES = {
         (MeshTopo, ("meshtopo_edges", "meshtopo_fill_count", "meshtopo_fill_emit", "meshtopo_smooth", "meshtopo_cc_hook",
                     "meshtopo_cc_jump", "meshtopo_views", "meshsimplify_keys", "meshsimplify_place",
                     "meshsimplify_faces", "meshsubdiv_mark", "meshsubdiv_odd", "meshsubdiv_even", "meshsubdiv_count",
-                    "meshsubdiv_emit", "meshhole_link", "meshhole_rank", "meshhole_count", "meshhole_triangulate")),
+                    "meshsubdiv_emit", "meshhole_link", "meshhole_rank", "meshhole_count", "meshhole_triangulate",
+                    "meshremesh_collapse_check", "meshremesh_vertex_min", "meshremesh_collapse_apply",
+                    "meshremesh_flip_check", "meshremesh_flip_apply", "meshremesh_relax")),
         (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals",
                       "meshsmooth_laplace", "meshsmooth_frames", "meshsmooth_normals", "meshsmooth_update")),
         (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",

@@ -26,6 +26,8 @@ reference takes from trimesh, networkx, scipy.sparse and cv2.
     subdivide    subdivide_mesh, subdivide_to_edge    Loop and midpoint subdivision, and midpoint splits of the edges above
                                      a length (csrc/meshsubdiv.hip; trimesh.remesh.subdivide / subdivide_loop /
                                      subdivide_to_size on the CPU)
+    remesh       remesh_isotropic    split, collapse, flip, relax and project towards well-shaped triangles of a requested
+                                     edge length (csrc/meshremesh.hip; pymeshlab, CGAL or trimesh.remesh on the CPU)
     views        clean_by_views, clean_dtu_mesh         clean_dtu_mesh.py:36-154 (mask and visual-hull cleaning)
     masks        ellipse_footprint, dilate_masks, load_dtu_views
 
@@ -1448,6 +1450,249 @@ def subdivide_to_edge(verts, faces, max_edge, max_rounds=32, attributes=None, _i
     max_edge = _finite(max_edge, "max_edge", positive=True)
     max_rounds = _count(max_rounds, "max_rounds")
     return _subdivide(verts, faces, attributes, 0, max_edge, max_rounds, _info)
+
+
+class Remeshed(NamedTuple):
+    """verts [V', 3] in the input's dtype; faces [F', 3] int64; attributes [V', k] in their input's dtype, or None;
+    iterations: the iterations run; collapsed / flipped / split: per iteration the edges collapsed, flipped and split"""
+    verts: torch.Tensor
+    faces: torch.Tensor
+    attributes: torch.Tensor | None
+    iterations: int
+    collapsed: tuple
+    flipped: tuple
+    split: tuple
+
+
+REMESH_STATUS_NAMES = {v: k.lower() for k, v in _lib.REMESH.items()}
+_REMESH_RING_PASSES = 2      # passes over the one-rings after the pass over the edges: two winning collapses then share no
+                             # vertex of the closed neighbourhoods of their ends (include/nudf.h, collapse_apply)
+
+
+class _RemeshTables(NamedTuple):
+    """what one sub-round reads besides the mesh; the descriptor keeps pointers into all of it: the caller holds it"""
+    d: _lib.MeshTopo
+    table: EdgeTable
+    vclass: torch.Tensor
+    ring_off: torch.Tensor
+    held: tuple
+
+
+def _remesh_tables(pos, faces):
+    """the edge table, one-rings, border CSR, vertex classes, corner lists and the CSR of the edges at each vertex (both
+    ends of the table's rows under one stable sort) of a mesh, and a descriptor that points at them"""
+    n_verts, dev = pos.shape[0], pos.device
+    table = _mesh_edges(faces, n_verts)
+    n_edges = table.edges.shape[0]
+    ring_off, ring = _vertex_adjacency(faces, n_verts, table)
+    boundary = _boundary(table, n_verts)
+    vclass = _loop_classes(table, boundary, n_verts)
+    corner_off, corner = _corner_lists(faces, n_verts)
+    ends = torch.cat([table.edges[:, 0], table.edges[:, 1]])
+    vedge = (torch.sort(ends, stable=True).indices % max(n_edges, 1)).contiguous()
+    vedge_off = torch.zeros(n_verts + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(ends, minlength=n_verts), 0, out=vedge_off[1:])
+    d = _topo(faces, n_verts, table)
+    d.pos = ptr(pos)
+    d.sp_sd_ring_off, d.sp_sd_ring, d.sp_sd_n_ring = ptr(ring_off), ptr(ring), ring.numel()
+    d.nbr_off, d.nbr, d.sp_sd_n_border = ptr(boundary.nbr_off), ptr(boundary.nbr), boundary.nbr.numel()
+    d.sp_sd_vclass = ptr(vclass)
+    d.sp_sd_hf_rm_corner_off, d.sp_sd_hf_rm_corner = ptr(corner_off), ptr(corner)
+    d.sp_sd_hf_rm_vedge_off, d.sp_sd_hf_rm_vedge, d.sp_sd_hf_rm_n_vedge = ptr(vedge_off), ptr(vedge), vedge.numel()
+    return _RemeshTables(d, table, vclass, ring_off, (pos, faces, ring, boundary, corner_off, corner, vedge_off, vedge))
+
+
+def _remesh_ranks(status, key):
+    """-> [E] the place of each candidate (status 0) in a stable sort by `key`, ties by edge index; E for the others"""
+    n_edges = status.numel()
+    cand = torch.nonzero(status == 0).reshape(-1)
+    rank = torch.full((n_edges,), n_edges, dtype=torch.int64, device=status.device)
+    rank[cand[torch.sort(key[cand], stable=True).indices]] = torch.arange(cand.numel(), dtype=torch.int64, device=status.device)
+    return rank
+
+
+def _remesh_best(t, status, rank, passes):
+    """the minimum passes of one sub-round -> best [V]; `passes`: (mode, ...) in order"""
+    d, dev = t.d, status.device
+    n_verts = t.vclass.numel()
+    d.sp_sd_hf_rm_status, d.sp_sd_hf_rm_rank = ptr(status), ptr(rank)
+    best = None
+    for mode in passes:
+        out = torch.empty(n_verts, dtype=torch.int64, device=dev)
+        d.sp_sd_hf_rm_mode, d.sp_sd_hf_rm_best_in, d.sp_sd_hf_rm_best_out = mode, ptr(best), ptr(out)
+        call("nudf_meshremesh_vertex_min", d)
+        best = out
+    d.sp_sd_hf_rm_best_in = ptr(best)
+    return best
+
+
+def _repeats(faces):
+    """-> [F] bool: two corners of the face are the same vertex"""
+    return (faces[:, 0] == faces[:, 1]) | (faces[:, 1] == faces[:, 2]) | (faces[:, 0] == faces[:, 2])
+
+
+def _collapse_round(pos, faces, low, high, cos_border, counts=None):
+    """one sub-round of collapses -> (winners, pos', faces'); the vertices that went stay in pos' unused"""
+    t = _remesh_tables(pos, faces)
+    d, dev = t.d, pos.device
+    n_edges = t.table.edges.shape[0]
+    status = torch.empty(n_edges, dtype=torch.uint8, device=dev)
+    keep = torch.empty(n_edges, dtype=torch.int64, device=dev)
+    gone = torch.empty(n_edges, dtype=torch.int64, device=dev)
+    d.sp_sd_hf_rm_status, d.sp_sd_hf_rm_keep, d.sp_sd_hf_rm_gone = ptr(status), ptr(keep), ptr(gone)
+    d.sp_sd_hf_rm_low, d.sp_sd_hf_rm_high, d.sp_sd_hf_rm_cos_border = low, high, cos_border
+    call("nudf_meshremesh_collapse_check", d)
+    n_cand = int((status == 0).sum())
+    n_win = 0
+    if n_cand:
+        e = t.table.edges
+        diff = pos[e[:, 0]] - pos[e[:, 1]]
+        d2 = diff * diff
+        rank = _remesh_ranks(status, (d2[:, 0] + d2[:, 1]) + d2[:, 2])
+        best = _remesh_best(t, status, rank, (0,) + (1,) * _REMESH_RING_PASSES)
+        remap = torch.arange(pos.shape[0], dtype=torch.int64, device=dev)
+        pos_out = pos.clone()
+        win = torch.empty(n_edges, dtype=torch.uint8, device=dev)
+        d.sp_sd_hf_rm_remap, d.sp_sd_hf_rm_pos_out, d.sp_sd_hf_rm_win = ptr(remap), ptr(pos_out), ptr(win)
+        call("nudf_meshremesh_collapse_apply", d)
+        n_win = int(win.sum())
+        if n_win:
+            mapped = remap[faces]                       # a face that came with a repeated vertex stays
+            pos, faces = pos_out, mapped[~_repeats(mapped) | _repeats(faces)].contiguous()
+    if counts is not None:
+        counts.append(dict(candidates=n_cand, winners=n_win))
+    return n_win, pos, faces
+
+
+def _flip_round(pos, faces, counts=None):
+    """one sub-round of flips -> (winners, faces')"""
+    t = _remesh_tables(pos, faces)
+    d, dev = t.d, pos.device
+    n_edges = t.table.edges.shape[0]
+    status = torch.empty(n_edges, dtype=torch.uint8, device=dev)
+    gain = torch.empty(n_edges, dtype=torch.int32, device=dev)
+    ab = torch.empty((n_edges, 2), dtype=torch.int64, device=dev)
+    d.sp_sd_hf_rm_status, d.sp_sd_hf_rm_gain, d.sp_sd_hf_rm_ab = ptr(status), ptr(gain), ptr(ab)
+    call("nudf_meshremesh_flip_check", d)
+    n_cand = int((status == 0).sum())
+    n_win = 0
+    if n_cand:
+        rank = _remesh_ranks(status, -gain.to(torch.int64))
+        best = _remesh_best(t, status, rank, (2,))
+        out = faces.clone()
+        win = torch.empty(n_edges, dtype=torch.uint8, device=dev)
+        d.sp_sd_hf_rm_faces_out, d.sp_sd_hf_rm_win = ptr(out), ptr(win)
+        call("nudf_meshremesh_flip_apply", d)
+        n_win = int(win.sum())
+        if n_win:
+            faces = out
+        del best
+    if counts is not None:
+        counts.append(dict(candidates=n_cand, winners=n_win))
+    return n_win, faces
+
+
+def _relax(pos, faces):
+    """-> (pos', moving [V] bool: the smooth vertices with a one-ring, which relax moves)"""
+    t = _remesh_tables(pos, faces)
+    out = torch.empty_like(pos)
+    t.d.sp_sd_hf_rm_pos_out = ptr(out)
+    call("nudf_meshremesh_relax", t.d)
+    return out, (t.vclass == 0) & (t.ring_off[1:] > t.ring_off[:-1])
+
+
+def remesh_isotropic(verts, faces, target_edge, iterations=5, project=True, border_angle=30.0, attributes=None,
+                     max_subrounds=16, _info=None):
+    """isotropic remeshing towards edges of length `target_edge` (csrc/meshremesh.hip; pymeshlab, CGAL or trimesh.remesh on
+    the CPU) -> Remeshed: the loop of Botsch and Kobbelt, "A remeshing approach to multiresolution modeling" (2004).
+    With low = 0.8 target_edge and high = 4/3 target_edge an iteration
+      1. splits the edges longer than high (subdivide_to_edge);
+      2. collapses edges shorter than low in sub-rounds, until one has no winner or after `max_subrounds`, then drops the
+         vertices that went (compact_mesh).  An edge with two faces between two smooth vertices goes to its midpoint; a
+         border vertex is kept where it is; an edge between two border vertices that is not a border edge stays; a
+         border edge is collapsed only where the border turns by less than `border_angle` degrees at the end that goes
+         (0: the border keeps all its vertices).  No collapse changes the topology (link condition), makes an edge longer
+         than high, turns a face over or merges two faces; vertices on an edge with three or more faces, those whose
+         border is not a simple curve (_loop_classes' class 2) and the faces at them are left alone;
+      3. flips edges with two faces in sub-rounds, stopped the same way, where that brings the valences of the four
+         vertices nearer 6 (4 on the border) without a fold and the new edge does not exist;
+      4. moves every smooth vertex to the mean of its one-ring, taken back into its tangent plane, and with `project`
+         then to its closest point on the input mesh (one evaluation.MeshIndex, built once).  Border vertices stay.
+    A sub-round takes an independent set of the candidates: each gets a rank (collapses: shorter first; flips: larger
+    gain first; ties by edge index) and wins when it holds the smallest rank of its neighbourhood, found by per-vertex
+    minimum passes -- no atomics, identical from run to run, and nothing depends on the winding or the order of the faces.
+    `attributes` [V, k] are carried at the end from the input by transfer_attributes.  float64 inside, cast at the end.
+    Not done: feature or crease preservation (a cube's edges are rounded), adaptive sizing, area-weighted relaxation.
+    (`_info`: receives per iteration the sub-rounds' candidate and winner counts and, with an "events" dict in it, a pair
+    of events per stage.)"""
+    target_edge = _finite(target_edge, "target_edge", positive=True)
+    iterations = _count(iterations, "iterations")
+    max_subrounds = _count(max_subrounds, "max_subrounds")
+    border_angle = _finite(border_angle, "border_angle")
+    if not 0.0 <= border_angle <= 180.0:
+        raise ValueError(f"border_angle must be in [0, 180] degrees (got {border_angle!r})")
+    verts, faces = _check_mesh(verts, faces)
+    attributes = _check_attributes(attributes, verts)
+    if verts.shape[0] == 0 or faces.shape[0] == 0 or iterations == 0:
+        return Remeshed(verts, faces, attributes, iterations, (0,) * iterations, (0,) * iterations, (0,) * iterations)
+    low, high = 0.8 * target_edge, target_edge * 4 / 3
+    cos_border = math.cos(math.radians(border_angle))
+    events = None if _info is None else _info.get("events")
+    pos, out_faces = verts.double().contiguous(), faces
+    index = None
+    if project:
+        from . import evaluation
+        index = evaluation.MeshIndex(pos, faces)
+    collapsed, flipped, split, rounds = [], [], [], []
+    for it in range(iterations):
+        stages = None if events is None else events.setdefault(f"iteration{it}", {})
+        state, log = {}, dict(collapse=[], flip=[])
+        rounds.append(log)
+        if out_faces.shape[0] == 0:
+            collapsed.append(0), flipped.append(0), split.append(0)
+            continue
+        _stage(stages, state, "split")
+        s = subdivide_to_edge(pos, out_faces, high)
+        split.append(s.verts.shape[0] - pos.shape[0])
+        pos, out_faces = s.verts, s.faces
+        _stage(stages, state, "collapse")
+        total = 0
+        for _ in range(max_subrounds):
+            n, pos, out_faces = _collapse_round(pos, out_faces, low, high, cos_border, log["collapse"])
+            if n == 0:
+                break
+            total += n
+        collapsed.append(total)
+        pos, out_faces = compact_mesh(pos, out_faces)
+        pos, out_faces = pos.contiguous(), out_faces.contiguous()
+        _stage(stages, state, "flip")
+        total = 0
+        for _ in range(max_subrounds):
+            if out_faces.shape[0] == 0:
+                break
+            n, out_faces = _flip_round(pos, out_faces, log["flip"])
+            if n == 0:
+                break
+            total += n
+        flipped.append(total)
+        if out_faces.shape[0]:
+            _stage(stages, state, "relax")
+            new, moving = _relax(pos, out_faces)
+            if index is not None:
+                _stage(stages, state, "project")
+                rows = torch.nonzero(moving).reshape(-1)
+                if rows.numel():
+                    c = index.closest(new[rows])
+                    hit = c.face >= 0
+                    new[rows[hit]] = c.point[hit]
+            pos = new
+        _stage(stages, state, None)
+    attr = None
+    if attributes is not None:
+        attr = transfer_attributes(verts, faces, attributes, pos)
+    if _info is not None:
+        _info["rounds"] = rounds
+    return Remeshed(pos.to(verts.dtype), out_faces, attr, iterations, tuple(collapsed), tuple(flipped), tuple(split))
 
 def ellipse_footprint(ksize):
     """OpenCV's MORPH_ELLIPSE structuring element of size ksize x ksize -> np.uint8 [ksize, ksize], restated from the

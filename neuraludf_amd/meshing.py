@@ -24,6 +24,8 @@ and its serial Cython mesher.
     subdivide subdivide_mesh, subdivide_to_edge (meshclean, csrc/meshsubdiv.hip): Loop and midpoint subdivision, and
                                   midpoint splits of the edges above a length, after the simplification: vertex density
                                   is the resolution of vertex colours
+    remesh    remesh_isotropic (meshclean, csrc/meshremesh.hip): split, collapse, flip, relax and project towards
+                                  well-shaped triangles of a requested edge length
     crossings close_holes_checked, drop_self_intersections (meshclean; evaluation.self_intersections,
               csrc/meshintersect.hip): patches that cut through the surface taken back, crossing and folded faces dropped
     holes     border_loops, close_holes (meshclean, csrc/meshhole.hip): the border as canonical loops and chains, and the
@@ -41,6 +43,7 @@ and its serial Cython mesher.
                                     [--denoise [--sigma-s S]] [--smooth N [--smooth-weights uniform|cotangent]]
                                     [--free-boundary]
                                     [--simplify CELL | --simplify-to FACES | --simplify-max-error E]
+                                    [--remesh L [--remesh-iterations N]]
                                     [--max-edge H] [--subdivide N [--subdivide-scheme loop|midpoint]]
                                     [--orient | --outward-from X Y Z] [--normals] [--colour] [--render DIR]
 
@@ -65,6 +68,7 @@ from .meshclean import (EdgeTable, Orientation, Simplified, boundary_degree, cle
                         simplify_to_faces, smooth_borders, smooth_mesh, transfer_attributes, vertex_adjacency,
                         vertex_normals, view_counts)
 from .meshclean import Subdivided, subdivide_mesh, subdivide_to_edge  # noqa: F401
+from .meshclean import Remeshed, remesh_isotropic  # noqa: F401
 from .meshclean import BorderLoops, ClosedHoles, border_loops, close_holes  # noqa: F401
 from .meshclean import close_holes_checked, drop_self_intersections  # noqa: F401
 from .models import udf_renderer_blending as rb
@@ -683,7 +687,8 @@ def extract_udf_mesh(udf_network, resolution=256, bound_min=(-1.0, -1.0, -1.0), 
                      min_component_faces=0, keep_largest=False, sparse=False, block=8, lipschitz=2.0, orient=False,
                      outward_from=None, color_from=None, simplify_cell=None, simplify_max_error=None, smooth=None,
                      denoise=False, subdivide_max_edge=None, subdivide=None, close_holes=None,
-                     close_holes_perimeter=None, close_holes_check=False, drop_self_intersections=False):
+                     close_holes_perimeter=None, close_holes_check=False, drop_self_intersections=False,
+                     remesh_edge=None, remesh_iterations=5):
     """open-surface mesh of `udf_network`'s zero level (the reference's get_mesh_udf_fast, without its differentiable
     refinement): udf_grid -> udf_marching_cubes -> filter_mesh with the network's UDF at the vertices and
     max_udf = dist_threshold_ratio * h.  The clean-up the reference takes from trimesh is off by default and follows in
@@ -706,6 +711,9 @@ def extract_udf_mesh(udf_network, resolution=256, bound_min=(-1.0, -1.0, -1.0), 
     meshclean.smooth_mesh's arguments) the mesher's grid noise is filtered after the component filter and before the
     simplification, which would freeze it into larger triangles: the bilateral normal filter first, then the Taubin
     smoothing, when both are given.
+    With remesh_edge = L, in the coordinates of the box, the mesh is remeshed isotropically after the simplification and
+    before the subdivision, in remesh_iterations iterations, towards well-shaped triangles with edges of length L, its
+    vertices kept on the surface as it was before the step (meshclean.remesh_isotropic).
     With subdivide_max_edge = h, in the coordinates of the box, the edges longer than h are split at their midpoints after
     the simplification until none is left (meshclean.subdivide_to_edge; the surface does not change), and with subdivide =
     a level count (or a dict of meshclean.subdivide_mesh's arguments) the mesh is then subdivided uniformly, by Loop's
@@ -759,6 +767,8 @@ def extract_udf_mesh(udf_network, resolution=256, bound_min=(-1.0, -1.0, -1.0), 
         verts, faces = meshclean.simplify_mesh(verts, faces, simplify_cell)[:2]
     if simplify_max_error is not None and faces.shape[0]:
         verts, faces = meshclean.simplify_to_error(verts, faces, simplify_max_error)[0][:2]
+    if remesh_edge is not None:
+        verts, faces = meshclean.remesh_isotropic(verts, faces, remesh_edge, remesh_iterations)[:2]
     if subdivide_max_edge is not None:
         verts, faces = meshclean.subdivide_to_edge(verts, faces, subdivide_max_edge)[:2]
     if subdivide is not None:
@@ -989,7 +999,8 @@ def _write_renders(out_dir, verts, faces, normals, world_mats, H, W, view_chunk=
 def main(argv=None):
     """python -m neuraludf_amd.meshing IN.ply OUT.ply ...: the clean-up steps on a mesh file, in the reference's order
     (holes, borders, components, then the DTU mask and visual-hull cleaning), then the denoising and the smoothing (the
-    file's colours pass through them untouched), the simplification, the subdivision (edges above --max-edge first, then
+    file's colours pass through them untouched), the simplification, the isotropic remeshing (--remesh; the file's colours
+    are carried from the closest points of the mesh before it), the subdivision (edges above --max-edge first, then
     --subdivide levels; the file's colours go through the weights of the positions), the orientation of the faces, the
     vertex normals and, last of all, the vertex colours and the renders from the scan's cameras; `python -m
     neuraludf_amd.evaluation` scores the result"""
@@ -1026,6 +1037,9 @@ def main(argv=None):
     ap.add_argument("--smooth", type=int, metavar="N", help="N rounds of Taubin smoothing (smooth_mesh)")
     ap.add_argument("--smooth-weights", choices=("uniform", "cotangent"), default="uniform")
     ap.add_argument("--free-boundary", action="store_true", help="let border vertices move under --smooth and --denoise")
+    ap.add_argument("--remesh", type=float, metavar="L",
+                    help="after the simplification, remesh isotropically towards edges of length L (remesh_isotropic)")
+    ap.add_argument("--remesh-iterations", type=int, default=5, metavar="N", help="iterations of --remesh")
     ap.add_argument("--max-edge", type=float, metavar="H",
                     help="after the simplification, split edges at their midpoints until none is longer than H")
     ap.add_argument("--subdivide", type=int, metavar="N", help="N levels of uniform subdivision (subdivide_mesh)")
@@ -1112,12 +1126,26 @@ def main(argv=None):
             carried = s.attributes.cpu().numpy()
             if file_colors.dtype == np.uint8:                # a mean of 0..255 values is one
                 carried = np.rint(carried).astype(np.uint8)
+    simplified = a.simplify is not None or a.simplify_to is not None or a.simplify_max_error is not None
+    if a.remesh is not None:
+        attrs = None
+        if carried is not None:                              # colours that came through the steps above
+            attrs = torch.from_numpy(np.asarray(carried, dtype=np.float64)).to(dev)
+        elif file_colors is not None and not a.colour and len(file_colors) == verts.shape[0] and not simplified:
+            attrs = torch.from_numpy(np.asarray(file_colors, dtype=np.float64)).to(dev)
+        r = meshclean.remesh_isotropic(verts, faces, a.remesh, a.remesh_iterations, attributes=attrs)
+        print(f"remesh: split {list(r.split)}, collapsed {list(r.collapsed)}, flipped {list(r.flipped)}")
+        verts, faces, carried = r.verts, r.faces, None
+        if r.attributes is not None:
+            carried = r.attributes.cpu().numpy()
+            if file_colors.dtype == np.uint8:                # a convex combination of 0..255 values is one
+                carried = np.rint(np.clip(carried, 0.0, 255.0)).astype(np.uint8)
     if a.max_edge is not None or a.subdivide is not None:
         attrs = None
         if carried is not None:                              # colours that came through the steps above
             attrs = torch.from_numpy(np.asarray(carried, dtype=np.float64)).to(dev)
         elif (file_colors is not None and not a.colour and len(file_colors) == verts.shape[0]
-              and a.simplify is None and a.simplify_to is None and a.simplify_max_error is None):
+              and not simplified and a.remesh is None):
             attrs = torch.from_numpy(np.asarray(file_colors, dtype=np.float64)).to(dev)
         if a.max_edge is not None:
             s = meshclean.subdivide_to_edge(verts, faces, a.max_edge, attributes=attrs)
