@@ -543,6 +543,13 @@ int nudf_adam_chunk(void);                         /* elements one block updates
  * ROW PADDING: the kernel stores whole 64-point tiles, so every buffer it writes (C1, C2, G0) or reads in
  * an epilogue (X1, X2, r1_row) must hold roundup(P, 64) rows; rows >= P are scratch.  x, v, A0 of
  * INIT_LOAD and seed_sign are read with clamped row indices and need only P rows.  P * ld < 2^31.
+ * SCRATCH ROWS: rows >= P may hold ANY bit pattern on entry (NaN, Inf, huge finite values: the buffers are
+ * allocated, not cleared), and no live output, no reported maximum (absmax_out, tile_amax_out) and no status
+ * bit may depend on them.  A launch therefore computes the points >= P of its last tile from row P - 1
+ * (clamped reads of x, v, A0 and seed_sign; r1_row is written for all padded rows by its producer) and STORES every row of every tile it runs into C1 / C2 / G0,
+ * so that a later launch, which reads whole tiles of those arrays as X1 / X2 / X3, finds defined values there.
+ * Rows of tiles no workgroup runs (roundup(P, tile) .. roundup(P, 64)) are never read.
+ * tests/test_gpu_scratch_poison.py holds this with poisoned allocations.
  * ---------------------------------------------------------------------------------- */
 enum {
   NUDF_CH_NONE = 0,      /* out = (acc + bias) * scale                                            */

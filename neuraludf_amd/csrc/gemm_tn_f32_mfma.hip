@@ -1300,7 +1300,8 @@ __global__ __launch_bounds__(256, TN3_WGS) void gemm_tn3_group_kernel(TnPlan g) 
 // Each side of a group therefore carries a power-of-two scale taken from a device scalar, max |x| over that side's operands
 // (written by the chain sweeps that produce them, NudfChain.absmax_out): sigma = 2^(10 - floor(log2 max)), so the largest
 // element lands in [1024, 2048), elements down to 2^-25 of it keep all 22 bits, and C is multiplied by 1 / (sigma_a sigma_b)
-// on its way out -- exact.  A scaled element beyond +-60 000 (a producer that did not report its maximum) is clamped, not inf.
+// on its way out -- exact.  A FINITE scaled element beyond +-60 000 (a producer that did not report its maximum) is clamped, not
+// inf; a NaN or infinite element goes through as it is and makes every dW element it feeds non-finite, as in the other kernels.
 // Same tiles, image layout (two planes instead of three: 32 KB), k-steps, workspace slots and reduce as the bf16x3 kernel;
 // the staging is its plain form (split + LDS stores between the barriers): two accumulator sets leave no registers for the
 // interleaved one.
@@ -1308,12 +1309,21 @@ __global__ __launch_bounds__(256, TN3_WGS) void gemm_tn3_group_kernel(TnPlan g) 
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void tn_split2_pair(float x0, float x1, float sc, unsigned& p0, unsigned& p1) {
-  x0 = __builtin_fminf(__builtin_fmaxf(x0 * sc, -60000.0f), 60000.0f);
-  x1 = __builtin_fminf(__builtin_fmaxf(x1 * sc, -60000.0f), 60000.0f);
-  const f16x2_t h = __builtin_convertvector(f32x2{x0, x1}, f16x2_t);
+  // a FINITE element beyond fp16's range after scaling is clamped; a non-finite one stays what it is (IEEE min / max would
+  // drop a NaN operand and return the bound: a NaN adjoint would reach dW as a finite number with no status bit set)
+  // One FMA: x * 0 is a zero with the sign of x for a finite x -- adding it leaves the clamped value as it is, bit for bit, a
+  // zero included -- and NaN for a NaN or an infinite x.  (The UNSCALED x, sc > 0: a finite x whose product with sc overflows
+  // is still clamped.)  The pair is kept as a two-element vector so that the scaling and the FMA can be one packed
+  // instruction each: the staging of this kernel is what binds it, and the card clocks it against the power limit.
+  const f32x2 xin = {x0, x1};
+  const f32x2 t = xin * sc;
+  const f32x2 c = {__builtin_fminf(__builtin_fmaxf(t[0], -60000.0f), 60000.0f),
+                   __builtin_fminf(__builtin_fmaxf(t[1], -60000.0f), 60000.0f)};
+  const f32x2 x = __builtin_elementwise_fma(xin, f32x2{0.0f, 0.0f}, c);
+  const f16x2_t h = __builtin_convertvector(x, f16x2_t);
   p0 = __builtin_bit_cast(unsigned, h);
-  const float r0 = (x0 - (float)h[0]) * 2048.0f, r1 = (x1 - (float)h[1]) * 2048.0f;
-  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, f16x2_t));
+  const f32x2 r = (x - __builtin_convertvector(h, f32x2)) * 2048.0f;
+  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, f16x2_t));
 }
 // 2^(10 - floor(log2 m)) and its reciprocal from the operand maximum (1 for NULL, 0, denormal or non-finite maxima)
 __device__ __forceinline__ void tn_scale_of(const float* amax, float& sc, float& inv) {

@@ -571,7 +571,9 @@ __device__ __forceinline__ void ch_p4_store(float* C, int ld, unsigned q0, unsig
 // epilogue of one step for this wave's tiles: new activations -> LDS (+ HBM where a later sweep needs them)
 // One 32x32 accumulator tile of a step's epilogue.  Branch-free per element: uniform options are tested once
 // around whole 16-element loops, the column predicate (N may end inside the tile) is one exec region, rows
-// need no predicate because every output / operand buffer is row-padded to the tile size (see nudf.h).
+// need no predicate because every output / operand buffer is row-padded to the tile size (see nudf.h, SCRATCH ROWS: the
+// rows >= P of a tile are computed from row P - 1 and stored like live ones, so that the operands X1 / X2 / X3 a later sweep
+// reads there -- and the maxima it forms over whole tiles -- never depend on what the allocation held).
 // Global addresses are <uniform row pointer> + <per-lane 32-bit offset>.
 // S16: the step's stored-state arrays (X1, X2, C1, and the TANGENT mirror C2) hold bf16 (config-5 mode, NUDF_CH_STATE16)
 // RT16: ReLU-family step in the 16-bit instantiation -- X1 / C1 are bf16 (packed) where the step's layout bits say so
@@ -1289,14 +1291,24 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? CH_T16_WGS : 2) void mlp_
       // bytes per wave instruction).  The element-wise form below moved the same 134 MB at config 5's size as 2-byte accesses
       // 8 bytes apart -- a quarter of every 32-byte sector used -- and cost the input-gradient sweep ~250 us against the
       // tangent sweep's identical steps (round 6, profiles/r06_bench_cfg5_1024x256_mixed16.json).  Buffers are row-padded to
-      // the tile (nudf.h), so the quads of a ragged last tile exist; points >= P compute on clamped rows as everywhere.
+      // the tile (nudf.h), so the quads of a ragged last tile exist and are STORED; what is READ for a point >= P is row
+      // P - 1, sign and stored activation alike: the quad is clamped to the one that holds row P - 1, and the points of that
+      // quad behind P take its element (P - 1) % 4 (scratch rows of A0 may hold anything).
       const uint2* A4 = reinterpret_cast<const uint2*>(p.A0);
       uint2* G4 = reinterpret_cast<uint2*>(p.G0);
+      const unsigned qlast = (unsigned)(p.P - 1) >> 2;
+      const int klast = (p.P - 1) & 3;
       for (int e = tid; e < (TM / 4) * C; e += CH_THREADS) {
         const int q = e / C, c = e - q * C;
         const unsigned gq = (unsigned)(m0 >> 2) + (unsigned)q;
         float hst[4], val[4];
-        ch_p4_widen(A4[(size_t)gq * p.lda0 + c], hst);
+        ch_p4_widen(A4[(size_t)min(gq, qlast) * p.lda0 + c], hst);
+        if (gq >= qlast) {        // the last live quad and the scratch quads behind it (at most one tile per launch)
+          const float hl = klast == 0 ? hst[0] : klast == 1 ? hst[1] : klast == 2 ? hst[2] : hst[3];
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (gq > qlast || k > klast) hst[k] = hl;
+        }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           int gr = m0 + 4 * q + k;
@@ -1316,9 +1328,8 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? CH_T16_WGS : 2) void mlp_
     } else
     for (int e = tid; e < TM * C; e += CH_THREADS) {
       const int r = e / C, c = e - r * C;
-      int gr = m0 + r;
-      const bool live = gr < p.P;
-      if (!live) gr = p.P - 1;
+      const int sr = m0 + r;                       // the row stored; points >= P take their values from row P - 1
+      const int gr = sr < p.P ? sr : p.P - 1;
       float s, om;
       const float hst = (p.init_state16 & 1) ? ch_bf2f(reinterpret_cast<const unsigned short*>(p.A0)[ch_p4_off(gr, c, p.lda0)])
                                              : p.A0[(size_t)gr * p.lda0 + c];
@@ -1326,9 +1337,11 @@ __global__ __launch_bounds__(CH_THREADS, (MODE == 3) ? CH_T16_WGS : 2) void mlp_
       const float val = p.seed_sign[gr] * p.seed_wrow[c] * p.seed_scale * s;
       if constexpr (T16) sm.act[r * CH_LD16 + c] = tile_bf ? ch_f2bf(val) : ch_f2h(val);
       else act_f[r * CH_LD + c] = val;
-      if (p.G0 && live) {
-        if (p.init_state16 & 2) reinterpret_cast<unsigned short*>(p.G0)[ch_p4_off(gr, c, p.ldg0)] = ch_f2bf(val);
-        else p.G0[(size_t)gr * p.ldg0 + c] = val;
+      // (all TM rows, like the in-place SEED step and every step's C1: G0 is row-padded, and the adjoint sweep reads whole
+      // tiles of it as X3 -- a scratch row left unwritten would reach that tile's maximum and the weight-gradient GEMM's scale)
+      if (p.G0) {
+        if (p.init_state16 & 2) reinterpret_cast<unsigned short*>(p.G0)[ch_p4_off(sr, c, p.ldg0)] = ch_f2bf(val);
+        else p.G0[(size_t)sr * p.ldg0 + c] = val;
       }
     }
   }

@@ -364,14 +364,13 @@ __global__ __launch_bounds__(CHR_WAVES * 64, 1) void mlp_chain_rows_kernel(NudfC
     const int C = p.k0;
     for (int e = lane; e < CHR_ROWS * C; e += 64) {
       const int r = e / C, c = e - r * C;
-      int gr = m0 + r;
-      const bool live = gr < p.P;
-      if (!live) gr = p.P - 1;
+      const int sr = m0 + r;                       // the row stored; points >= P take their values from row P - 1
+      const int gr = sr < p.P ? sr : p.P - 1;
       float s, om;
       ch_sp_derivs(p.A0[(size_t)gr * p.lda0 + c], p.seed_xscale, s, om);
       const float val = p.seed_sign[gr] * p.seed_wrow[c] * p.seed_scale * s;
       act[r * CH_LD + c] = val;
-      if (p.G0 && live) p.G0[(size_t)gr * p.ldg0 + c] = val;
+      if (p.G0) p.G0[(size_t)sr * p.ldg0 + c] = val;      // (all rows of the tile, as in mlp_chain_kernel: G0 is row-padded)
     }
   }
   chr_wave_sync();
@@ -718,17 +717,16 @@ __global__ __launch_bounds__(256, 2) void mlp_chain_tq_kernel(NudfChain p_arg) {
     const int C = p.k0;
     for (int e = tid; e < 64 * C; e += 256) {
       const int r = e / C, c = e - r * C;
-      int gr = m0 + r;
-      const bool live = gr < p.P;
-      if (!live) gr = p.P - 1;
+      const int sr = m0 + r;                       // the row stored; points >= P take their values from row P - 1
+      const int gr = sr < p.P ? sr : p.P - 1;
       float s, om;
       const float hst = (p.init_state16 & 4) ? p.A0[ch_blk_off(gr, c, p.lda0)] : p.A0[(size_t)gr * p.lda0 + c];
       ch_sp_derivs(hst, p.seed_xscale, s, om);
       const float val = p.seed_sign[gr] * p.seed_wrow[c] * p.seed_scale * s;
       sm.act[r * CH_LD + c] = val;
-      if (p.G0 && live) {
-        if (p.init_state16 & 8) p.G0[ch_blk_off(gr, c, p.ldg0)] = val;
-        else p.G0[(size_t)gr * p.ldg0 + c] = val;
+      if (p.G0) {                                  // (all 64 rows of the tile, as in mlp_chain_kernel: G0 is row-padded)
+        if (p.init_state16 & 8) p.G0[ch_blk_off(sr, c, p.ldg0)] = val;
+        else p.G0[(size_t)sr * p.ldg0 + c] = val;
       }
     }
   }

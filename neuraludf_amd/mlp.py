@@ -41,7 +41,9 @@ def pad_rows(P: int) -> int:
 
 
 def _buf(P, width, dev, zero=None, dtype=torch.float32, blocked=False):
-    """[pad_rows(P), pad32(width)] fp32 (rows >= P are scratch for the tile kernels); pad columns zeroed (default),
+    """[pad_rows(P), pad32(width)] fp32 (rows >= P are scratch for the tile kernels: they may hold anything when a kernel
+    first sees them, and no live result, reported maximum or status bit may depend on that -- include/nudf.h, SCRATCH ROWS;
+    tests/test_gpu_scratch_poison.py); pad columns zeroed (default),
     everything zeroed (zero=True) or nothing (zero=False).  dtype = bfloat16: stored state of the 16-bit mode, which is
     4-POINT PACKED (include/nudf.h, NUDF_CH_STATE16: element (r, c) at ((r // 4) ld + c) 4 + r % 4; `unpack16` gives the
     plain view) -- only the chain kernels and the grouped weight-gradient GEMM address it.

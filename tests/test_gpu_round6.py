@@ -144,6 +144,57 @@ def test_f16x2_weight_gradient_gemm_against_float64(dev, M):
         assert fl and cl < 1.0            # clamped operands: wrong by construction, but finite
 
 
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+@pytest.mark.parametrize("kernel", ["f16x2", "fp32", "bf16x3"])
+def test_non_finite_adjoint_reaches_every_weight_gradient_it_feeds(dev, kernel, bad):
+    """One NaN / +Inf in a live row of the adjoint operand A (C = A^T B, db = column sums of A): row i of C and db[i], which
+    that element feeds, are non-finite; every other element is bit-equal to the run without it.  NudfGemmTNGroup.prec 4
+    (gemm_tn2_group_kernel, maxima reported) clamps FINITE operands beyond fp16's range (the test above) -- a clamp written
+    with IEEE min / max would also turn the NaN into +-60 000 and hand a finite dW to the optimizer with no status bit set.
+    prec 0 and 3 are the reference behaviour.
+    Before the clamp let non-finite values through, [f16x2-nan] and [f16x2-inf] failed here: all of row i of C finite."""
+    from neuraludf_amd import mlp
+    M = 333
+    g = torch.Generator().manual_seed(12)
+    shapes = [(256, 256), (217, 256), (3, 128), (129, 72), (1, 256)]
+    ops = []
+    for NA, NB in shapes:
+        lda, ldb = (NA + 3) // 4 * 4, (NB + 3) // 4 * 4
+        A = torch.randn(M, lda, generator=g) * torch.exp(torch.randn(1, lda, generator=g)) * 1e-7
+        B = torch.randn(M, ldb, generator=g).abs() * 0.3 + 0.01
+        ops.append((A, B, NA, NB))
+    amax = torch.stack([A.abs().max() for A, _, _, _ in ops]).max().reshape(1).to(dev)
+    hit = [(171 + 13 * k, NA // 2) for k, (_, _, NA, _) in enumerate(ops)]          # (row m < M, column i < NA) per problem
+
+    def run(poison):
+        mlp.set_precision("fp32" if kernel == "fp32" else "bf16x3")
+        jobs = []
+        for (A, B, NA, NB), (m, i) in zip(ops, hit):
+            A = A.clone()
+            if poison:
+                A[m, i] = bad
+            jobs.append((A.to(dev), NA, B.to(dev), NB, torch.zeros(mlp.pad32(NA), B.shape[1], device=dev),
+                         torch.zeros(mlp.pad32(NA), device=dev)))
+        kw = dict(f16x2=True, amax_a=amax) if kernel == "f16x2" else {}
+        mlp.gemm_tn_grouped(jobs, M, **kw)
+        torch.cuda.synchronize()
+        return [(j[4][:NA, :NB].clone(), j[5][:NA].clone()) for j, (_, _, NA, NB) in zip(jobs, ops)]
+
+    try:
+        clean, dirty = run(False), run(True)
+    finally:
+        mlp.set_precision("bf16x3")
+    for k, ((C0, b0), (C1, b1), (m, i)) in enumerate(zip(clean, dirty, hit)):
+        assert bool(torch.isfinite(C0).all()) and bool(torch.isfinite(b0).all()), k
+        fed = ~torch.isfinite(C1[i])
+        assert bool(fed.all()), (kernel, k, "finite elements in the row the element feeds", int((~fed).sum()), C1[i][~fed][:4])
+        assert not bool(torch.isfinite(b1[i])), (kernel, k, "db", float(b1[i]))
+        keep = torch.ones(C0.shape[0], dtype=torch.bool, device=dev)
+        keep[i] = False
+        assert torch.equal(C1[keep], C0[keep]), (kernel, k, "rows the element does not feed changed")
+        assert torch.equal(b1[keep], b0[keep]), (kernel, k, "bias sums the element does not feed changed")
+
+
 def _err(a, ref):
     a, ref = a.detach().double().cpu(), ref.detach().double().cpu()
     return float((a - ref).abs().max() / ref.abs().max().clamp(min=1e-300))
