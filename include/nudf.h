@@ -550,6 +550,13 @@ int nudf_adam_chunk(void);                         /* elements one block updates
  * so that a later launch, which reads whole tiles of those arrays as X1 / X2 / X3, finds defined values there.
  * Rows of tiles no workgroup runs (roundup(P, tile) .. roundup(P, 64)) are never read.
  * tests/test_gpu_scratch_poison.py holds this with poisoned allocations.
+ * OUTPUTS IN GENERAL, of every entry point of this header: an output buffer may hold ANY bit pattern on entry, and
+ * every element of it is written on every path -- with the documented value where there is no result: +inf for a
+ * depth nothing was drawn into or a distance beyond `bound`, -1 for its face, NaN for its point and barycentrics, 0
+ * for a mask, a weight sum or the normal of a face without area, `fill` for a colour no view gives, the cluster's
+ * mean for a minimiser that is not accepted.  No result depends on what a float buffer held before the call.
+ * tests/test_gpu_blend_poison.py (blending, ray batches) and tests/test_gpu_mesh_poison.py (the mesh, meshing and
+ * evaluation tools) hold this the same way, bit pattern for bit pattern.
  * ---------------------------------------------------------------------------------- */
 enum {
   NUDF_CH_NONE = 0,      /* out = (acc + bias) * scale                                            */

@@ -12,10 +12,12 @@ tests/arch_cases.py, which keeps "identical" from meaning "identically wrong".  
     random-weighted sum of all outputs, at P = 1, 33, 97 (ragged against the 32-point tile) and 349 (tile forced to 64) -- all
     with P % 4 == 1, for the 4-point packed quads -- in five arithmetic modes, with the two UDF sweeps fused and unfused, and
     once per entry on the per-layer path;
-  * one whole render with gradients (37 rays x 27 + 8 samples: the point counts are ragged against 64, 32 and 4) and the
-    5-ray minimum-sample case of test_gpu_edges.py;
+  * one whole render with gradients (37 rays x 27 + 8 samples: the point counts are ragged against 64, 32 and 4), the same
+    render through its blending branch (3 source views, rays_uv, 7 x 7 patches) and the 5-ray minimum-sample case of
+    test_gpu_edges.py;
   * the colour-loss, step-loss and blend-loss autograd functions at 37 rays, with and without a mask;
-  * three eager train steps at the same ragged batch.
+  * three eager train steps at the same ragged batch, without and with the blending branch (pixel and patch colour terms).
+The blend kernels alone, ray batching and the mesh tools: tests/test_gpu_blend_poison.py, tests/test_gpu_mesh_poison.py.
 
 If a combination is not bit-repeatable even clean against clean, the test says so on stdout and holds each poisoned leg to one
 of two clean runs instead.
@@ -94,8 +96,10 @@ def _same(a, b):
     return [k for k in a if not (a[k].shape == b[k].shape and torch.equal(a[k], b[k]))]
 
 
-def _legs(run, dev, engines, tag):
-    """the clean leg twice and one leg per poison -> (clean result, [failure strings]).  `run()` -> {name: tensor}"""
+def _legs(run, dev, engines, tag, differ=_same, equal=torch.equal):
+    """the clean leg twice and one leg per poison -> (clean result, [failure strings]).  `run()` -> {name: tensor}.
+    differ(a, b) names the tensors of two results that differ and equal(x, y) compares two tensors: _same / torch.equal here,
+    the bit comparison of scratch_poison.same_bits where a result may legitimately hold NaN."""
     res = {}
     _status(dev, clear=True)
     bits = {}
@@ -108,14 +112,14 @@ def _legs(run, dev, engines, tag):
         bits[key] = _status(dev, clear=True)
     clean, again = res[SP.label(SP.CLEAN)], res[SP.label(SP.CLEAN) + " (again)"]
     bad = []
-    unstable = _same(clean, again)
+    unstable = differ(clean, again)
     if unstable:
         print(f"scratch poison [{tag}]: NOT bit-repeatable clean against clean: {unstable}")
     for v in SP.POISONS:
         r = res[SP.label(v)]
-        d = _same(r, clean)
+        d = differ(r, clean)
         if d and unstable:
-            d = [k for k in d if not torch.equal(r[k], again[k])]
+            d = [k for k in d if not equal(r[k], again[k])]
         if d:
             bad.append(f"{tag} poison {SP.label(v)}: differs from the clean leg in {d}")
     for k, b in bits.items():
@@ -225,6 +229,9 @@ RENDERS = {
     "ragged": (37, dict(n_samples=17, n_importance=10, n_outside=8, up_sample_steps=2, perturb=0.0)),
     # the minimum sample counts of test_gpu_edges.py
     "minimum": (5, dict(n_samples=2, n_importance=3, n_outside=0, up_sample_steps=3, perturb=0.0)),
+    # the ragged case through the blending branch: 3 source views (channel-interleaved, as the dataset hands them over) and
+    # rays_uv, so that pixel_blend, pixel_composite and patch_blend (7 x 7 patches) run forward and backward
+    "ragged_blend": (37, dict(n_samples=17, n_importance=10, n_outside=8, up_sample_steps=2, perturb=0.0, h_patch_size=3)),
 }
 
 
@@ -241,12 +248,19 @@ def test_render_and_its_backward_do_not_depend_on_unwritten_memory(dev, nets, ca
     r = {k: v[:n_rays].to(dev) for k, v in r.items()}
     gen = torch.Generator().manual_seed(n_rays)
     weights = {}
+    src = None
+    if case.endswith("_blend"):
+        src = {k: v.to(dev) for k, v in synth.make_source_views(synth.make_scene("tiny"), 0, 3, hwc=True).items()}
 
     def run():
         for m in nets.values():
             m.zero_grad()
+        kw_blend = {}
+        if src is not None:          # (the patch launch rescales rays_uv in place: a fresh copy per run)
+            kw_blend = dict(color_maps=src["color_maps"], w2cs=src["w2cs"], intrinsics=src["intrinsics"],
+                            query_c2w=src["query_c2w"], rays_uv=r["rays_uv"].clone())
         out = rend.render(r["rays_o"], r["rays_d"], r["near"], r["far"], cos_anneal_ratio=0.5, flip_saturation=0.5,
-                          perturb_overwrite=0)
+                          perturb_overwrite=0, **kw_blend)
         loss = 0.0
         for k in sorted(out):
             v = out[k]
@@ -267,6 +281,9 @@ def test_render_and_its_backward_do_not_depend_on_unwritten_memory(dev, nets, ca
     with _mode(fuse=fuse):
         clean, bad = _legs(run, dev, engines, f"render {case} {'fused' if fuse else 'unfused'}")
     assert len([k for k in clean if k.startswith("gradient ")]) > 50 and "out color" in clean and "out z_vals" in clean
+    if src is not None:
+        assert {"out color_pixel", "out patch_colors", "out patch_mask"} <= set(clean)
+        assert clean["out patch_colors"].shape == (n_rays, 49, 3) and float(clean["out color_pixel"].abs().max()) > 0
     assert all(bool(torch.isfinite(v.float()).all()) for v in clean.values()), [k for k, v in clean.items()
                                                                                   if not bool(torch.isfinite(v.float()).all())]
     assert not bad, "\n".join(bad)
@@ -326,23 +343,30 @@ def test_loss_functions_do_not_depend_on_unwritten_memory(dev, loss_setup, which
     assert not bad, "\n".join(bad)
 
 
-def test_train_steps_do_not_depend_on_unwritten_memory(dev):
-    """three eager steps (render, loss, backward, Adam) at a ragged batch: losses and every parameter after step 3.  No graph
-    capture: a captured fill would change what is replayed."""
+def _train_steps(dev, rconf, loss_conf, with_views):
+    """three eager steps (render, loss, backward, Adam) at a ragged batch: losses and every parameter after step 3, clean
+    against the poisons -1e30 and NaN"""
     from neuraludf_amd import synth
     from neuraludf_amd.train import Trainer
-    rconf = dict(n_samples=17, n_importance=10, n_outside=8, up_sample_steps=2, perturb=1.0)
     scene = synth.make_scene("tiny")
     batches = [{k: v.to(dev) for k, v in synth.make_rays(scene, i % 3, 37, seed=60 + i).items()} for i in range(3)]
+    blends = [None] * 3
+    if with_views:
+        g = torch.Generator().manual_seed(61)
+        for i, batch in enumerate(batches):
+            batch["gt_patch_colors"] = torch.rand(37, 49, 3, generator=g).to(dev)
+            blends[i] = {k: v.to(dev) for k, v in synth.make_source_views(scene, i % 3, 3, hwc=True).items()}
 
     def run(value):
         _status(dev, clear=True)
         with SP.poisoned(value):
-            tr = Trainer(dev, rconf, seed=0, fused_adam=True)
+            tr = Trainer(dev, rconf, color_loss_conf=loss_conf, seed=0, fused_adam=True)
             torch.manual_seed(77)
             losses = []
             for i, batch in enumerate(batches):
-                loss, _ = tr.step(batch, cos_anneal_ratio=0.5 + 0.1 * i, flip_saturation=0.3 * i, perturb_overwrite=0)
+                loss, out = tr.step(batch, cos_anneal_ratio=0.5 + 0.1 * i, flip_saturation=0.3 * i, perturb_overwrite=0,
+                                    blend=blends[i])
+                assert (out.get("patch_colors") is not None) == with_views
                 losses.append(loss.detach().clone())
             torch.cuda.synchronize()
             res = {f"loss {i}": l for i, l in enumerate(losses)}
@@ -364,3 +388,16 @@ def test_train_steps_do_not_depend_on_unwritten_memory(dev):
         if b:
             bad.append(f"train steps, poison {SP.label(v)}: status word {b}")
     assert not bad, "\n".join(bad)
+
+
+def test_train_steps_do_not_depend_on_unwritten_memory(dev):
+    """three eager steps (render, loss, backward, Adam) at a ragged batch: losses and every parameter after step 3.  No graph
+    capture: a captured fill would change what is replayed."""
+    _train_steps(dev, dict(n_samples=17, n_importance=10, n_outside=8, up_sample_steps=2, perturb=1.0), None, False)
+
+
+def test_train_steps_with_blending_do_not_depend_on_unwritten_memory(dev):
+    """the same three steps through the blending branch: 7 x 7 patches, pixel and patch colour terms in the loss, batches
+    with 3 source views and ground-truth patches.  Eager only, for the same reason."""
+    _train_steps(dev, dict(n_samples=17, n_importance=10, n_outside=8, up_sample_steps=2, perturb=1.0, h_patch_size=3),
+                 dict(color_pixel_weight=0.5, color_patch_weight=0.1), True)

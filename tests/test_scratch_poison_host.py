@@ -146,3 +146,67 @@ def test_canary_a_partly_written_buffer_is_detected_a_fully_written_one_is_not()
         assert not torch.equal(part, clean_part), (SP.label(v), float(part))
         assert torch.equal(full, clean_full), (SP.label(v), float(full))
     assert not torch.equal(res[SP.label(-1e30)][0], res[SP.label(1e5)][0])
+
+
+def test_same_bits_compares_shape_dtype_and_bit_pattern():
+    nan = torch.tensor([1.0, math.nan, math.inf, -math.inf])
+    assert SP.same_bits(nan, nan.clone()) and not torch.equal(nan, nan.clone())          # NaN against the same NaN
+    for dt in (torch.float64, torch.float16, torch.bfloat16):
+        assert SP.same_bits(nan.to(dt), nan.to(dt).clone()), dt
+    assert not SP.same_bits(torch.tensor([0.0]), torch.tensor([-0.0]))                    # torch.equal calls these equal
+    assert torch.equal(torch.tensor([0.0]), torch.tensor([-0.0]))
+    other_nan = nan.clone().view(torch.int32)
+    other_nan[1] ^= 1                                                                     # another payload: other bits
+    assert not SP.same_bits(nan, other_nan.view(torch.float32))
+    assert not SP.same_bits(torch.zeros(2, 3), torch.zeros(3, 2))
+    assert not SP.same_bits(torch.zeros(3), torch.zeros(3, dtype=torch.float64))
+    assert not SP.same_bits(torch.zeros(3), torch.zeros(3, dtype=torch.int32))
+    assert not SP.same_bits(torch.tensor([1.0, 2.0]), torch.tensor([1.0, 2.0000002]))
+    # integer, bool and empty tensors; views that are not contiguous; None
+    assert SP.same_bits(torch.arange(5), torch.arange(5)) and not SP.same_bits(torch.arange(5), torch.arange(5) + 1)
+    assert SP.same_bits(torch.tensor([True, False]), torch.tensor([True, False]))
+    assert SP.same_bits(torch.zeros(0, 3), torch.zeros(0, 3)) and not SP.same_bits(torch.zeros(0, 3), torch.zeros(0, 2))
+    m = torch.arange(12.0).reshape(3, 4)
+    assert SP.same_bits(m.t(), m.t().contiguous())
+    assert SP.same_bits(None, None) and not SP.same_bits(None, torch.zeros(1)) and not SP.same_bits(torch.zeros(1), None)
+
+
+def test_same_bits_names_lists_the_tensors_that_differ():
+    a = dict(x=torch.tensor([math.nan, 1.0]), y=torch.arange(3), z=torch.tensor([0.0]))
+    b = dict(x=torch.tensor([math.nan, 1.0]), y=torch.arange(3), z=torch.tensor([-0.0]))
+    assert SP.same_bits_names(a, b) == ["z"] and SP.same_bits_names(a, a) == []
+    with pytest.raises(AssertionError):
+        SP.same_bits_names(a, dict(x=a["x"]))
+
+
+class _FakeModule:
+    def __init__(self):
+        self.cache = {"k": torch.ones(2)}
+        self.other = {"kept": 1}
+
+
+def test_the_listed_caches_are_dropped_on_entry_and_on_exit():
+    fake, fake2 = _FakeModule(), _FakeModule()
+    held = fake.cache
+    with SP.poisoned(1.0, device_type="cpu", caches=[(fake, "cache"), (fake2, "cache")]):
+        assert fake.cache is held and not held and not fake2.cache          # cleared in place, on entry
+        fake.cache["made inside"] = torch.empty(3)
+        assert _all_are(fake.cache["made inside"], 1.0)
+    assert not fake.cache and fake.other == {"kept": 1} and fake2.other == {"kept": 1}      # the poisoned copy does not outlive the block
+    with pytest.raises(KeyError):
+        with SP.poisoned(1.0, device_type="cpu", caches=[(fake, "cache")]):
+            fake.cache["x"] = 1
+            raise KeyError("boom")
+    assert not fake.cache
+    # caches=False touches nothing
+    fake.cache["stays"] = 1
+    with _cpu(1.0):
+        pass
+    assert fake.cache == {"stays": 1}
+
+
+def test_module_caches_lists_every_module_level_cache_that_holds_device_tensors():
+    """the list drop_caches clears by default; every entry is a dict of its module (no library is loaded by the imports)"""
+    got = {(m.__name__.split(".")[-1], n) for m, n in SP.module_caches()}
+    assert got == {("mlp", "_TN_WS"), ("mlp", "_CHAIN_MEMO"), ("blend", "_uv_scale"), ("patch_metric", "_win_cache")}
+    assert all(isinstance(getattr(m, n), dict) for m, n in SP.module_caches())
