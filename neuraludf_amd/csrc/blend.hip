@@ -646,24 +646,32 @@ __global__ __launch_bounds__(256) void patch_metric_kernel(const float* __restri
   }
   float total = 0.f;
   for (int c = 0; c < 3; ++c) {
-    float m1 = 0, m2 = 0, e11 = 0, e22 = 0, e12 = 0;
+    float m1 = 0, m2 = 0, e11 = 0, e22 = 0;
     for (int i = l; i < Npx; i += 64) {
       const float w = win[i];
       const float a = pred[(base + i) * 3 + c], b = gt[(base + i) * 3 + c];
-      m1 += w * a; m2 += w * b; e11 += w * a * a; e22 += w * b * b; e12 += w * a * b;
+      m1 += w * a; m2 += w * b; e11 += w * a * a; e22 += w * b * b;
     }
-    m1 = wave_sum(m1); m2 = wave_sum(m2); e11 = wave_sum(e11); e22 = wave_sum(e22); e12 = wave_sum(e12);
+    m1 = wave_sum(m1); m2 = wave_sum(m2); e11 = wave_sum(e11); e22 = wave_sum(e22);
     const float s1 = sqrtf(e11 - m1 * m1 + 1e-4f), s2 = sqrtf(e22 - m2 * m2 + 1e-4f);
     const float d1 = s1 + 1e-8f, d2 = s2 + 1e-8f;
-    const float cov = e12 - m1 * m2;
+    // the CENTRED covariance of the reference (loss/patch_metric.py:60-66): E[ab] - mu1 mu2 loses 1e-3 on a bright flat patch;
+    // r2 = sum w (b - mu2) is the remainder of that centring, all there is of b_i - mu2 on a flat target (backward)
+    float cov = 0.f, r2 = 0.f;
+    for (int i = l; i < Npx; i += 64) {
+      const float w = win[i], cb = gt[(base + i) * 3 + c] - m2;
+      cov += w * (pred[(base + i) * 3 + c] - m1) * cb;
+      r2 += w * cb;
+    }
+    cov = wave_sum(cov); r2 = wave_sum(r2);
     total += cov / (d1 * d2);
     if (d_pred) {
-      // d cov / d a_i = w_i (b_i - mu2); d s1 / d a_i = w_i (a_i - mu1) / s1
+      // d cov / d a_i = w_i ((b_i - mu2) - r2); d s1 / d a_i = w_i (a_i - mu1) / s1
       const float k1 = 1.0f / (d1 * d2), k2 = cov / (d1 * d1 * d2 * s1);
       for (int i = l; i < Npx; i += 64) {
         const float w = win[i];
         const float a = pred[(base + i) * 3 + c], b = gt[(base + i) * 3 + c];
-        d_pred[(base + i) * 3 + c] = -(w * (b - m2) * k1 - w * (a - m1) * k2) * (dout * (1.0f / 3.0f));
+        d_pred[(base + i) * 3 + c] = -(w * ((b - m2) - r2) * k1 - w * (a - m1) * k2) * (dout * (1.0f / 3.0f));
       }
     }
   }

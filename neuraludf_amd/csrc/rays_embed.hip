@@ -1234,7 +1234,8 @@ __global__ void blend_loss_bwd_kernel(NudfBlendLoss p) {
   if (i < p.N) {      // position i of the sorted list -> ray order[i]: d err = d Lpatch * keep / keep_sum (* m)
     const long long r = p.order[i];
     const float keep = (p.m[r] > 0.f && (float)i >= p.out[10]) ? 1.0f : 0.0f;
-    p.d_err[r] = g * w[NUDF_LW_COLOR_PATCH] * keep / p.out[11];
+    // (a trimmed ray gets 0, not 0 / count: without a valid ray count is 0 and the reference's gradient still is 0)
+    p.d_err[r] = (keep > 0.f) ? g * w[NUDF_LW_COLOR_PATCH] / p.out[11] : 0.0f;
   }
 }
 extern "C" int nudf_blend_loss_bwd(const NudfBlendLoss* args, void* stream) {
