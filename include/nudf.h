@@ -1805,6 +1805,21 @@ typedef struct NudfMeshRaster {
   int32_t H;
   int32_t W;
   int32_t image_f32;         /* colour: 1 = float32 images, 0 = uint8                                                */
+  /* texture atlases (nudf_meshtexture_*, below) */
+  const double* tx_uv;       /* [n_faces, 3, 2] texel-centre coordinates of the corners of every face's chart       */
+  const int64_t* tx_cell_face; /* [tx_n_cells, 2] the faces of the lower and the upper chart of a cell, -1 = none (bake) */
+  const float* tx_fallback;  /* [n_verts, 3] colours mixed into texels no view contributes to, or NULL: fill (bake)  */
+  float* tx_colors;          /* [tx_H, tx_W, 3] the texture (bake: written; shade: read)                             */
+  int32_t* tx_n_seen;        /* [tx_H, tx_W] (bake)                                                                  */
+  float* tx_out;             /* [n_views, H, W, 3] (shade)                                                           */
+  int64_t tx_n_cells;
+  int64_t tx_class_off[11];  /* Morton offset of every size class, and the end of the last, ascending (bake)         */
+  int64_t tx_class_cell[11]; /* index of the first cell of every size class in tx_cell_face (bake)                   */
+  int32_t tx_class_k[10];    /* log2 of the cell side of every size class, descending, each in [3, 12] (bake)        */
+  int32_t tx_n_classes;      /* <= 10                                                                                */
+  int32_t tx_W;              /* atlas width, a power of two                                                          */
+  int32_t tx_H;              /* atlas height, tx_W or tx_W / 2                                                       */
+  float tx_background[3];    /* shade: the colour of a pixel nothing was drawn into                                  */
 } NudfMeshRaster;
 int nudf_meshraster_project(const NudfMeshRaster* args, void* stream);     /* one thread per (view, vertex)   */
 int nudf_meshraster_bounds(const NudfMeshRaster* args, void* stream);      /* one thread per (view, face)     */
@@ -1813,6 +1828,57 @@ int nudf_meshraster_draw_large(const NudfMeshRaster* args, void* stream);  /* on
 int nudf_meshraster_resolve(const NudfMeshRaster* args, void* stream);     /* one thread per pixel            */
 int nudf_meshraster_visible(const NudfMeshRaster* args, void* stream);     /* one thread per (view, vertex)   */
 int nudf_meshraster_colour(const NudfMeshRaster* args, void* stream);      /* one thread per vertex           */
+
+/* ------------------------------------------------------------------------------------
+ * Texture atlases (neuraludf_amd/meshrender.py texture_atlas, bake_texture, shade_textured; csrc/meshtexture.hip): one
+ * chart per face, a right isosceles triangle of texels, two charts to a square cell whose side s = 2^k is a power of two,
+ * the cells packed by a prefix sum in Morton order; a bake that evaluates, per texel, what nudf_meshraster_colour evaluates
+ * per vertex; and a textured draw of a raster.  NudfMeshRaster grew at its end by the tx_ fields WITHOUT a version step, as
+ * NudfMeshOrient did for the sm_ fields: the size table of nudf_abi_struct refuses a package and a library that disagree.
+ * Texel (i, j) of the atlas has its centre at (i, j): tx_uv is in those coordinates, and the texture is stored row-major,
+ * texel (i, j) at [j, i].  float64 without contraction, no atomics, every sum inside one thread.
+ * The layout (texture_atlas; torch on the device, restated by tests/meshtexture_ref.py):
+ *   side     k_f = the smallest k in [3, 12] with 2^k - 6 >= L_f * density, 12 when there is none; L_f = the square root of
+ *            the largest of the three squared edge lengths ((dx dx + dy dy) + dz dz, float64).  k_f = 3 for a face with a
+ *            vertex index out of range, a repeated vertex or a squared edge length that is not finite;
+ *   order    faces sorted by (k descending, face index ascending); the classes are the values of k that occur, descending;
+ *            class c with n faces holds ceil(n / 2) cells, cell e of it the class's faces 2 e (lower chart) and 2 e + 1
+ *            (upper chart, -1 when there is none); tx_class_cell[c] = the number of cells of the classes before c;
+ *   place    tx_class_off[c] = the sum of cells 4^k over the classes before c, tx_class_off[n_classes] = the total T; cell e
+ *            of class c covers the Morton indices [tx_class_off[c] + e 4^k, + 4^k): its corner (X, Y) is the even bits
+ *            (X) and the odd bits (Y) of the first of them;
+ *   size     tx_W = the smallest power of two with W^2 >= T (1 for T = 0), tx_H = W / 2 when 0 < T <= W^2 / 2, else W: the
+ *            atlas is the Morton range [0, W H), the first half of a square's Morton range being its lower half;
+ *   charts   in a cell of side s, local texel (i, j): the lower chart has its corners at (1, 1), (s - 4, 1), (1, s - 4), the
+ *            upper one at (s - 2, s - 2), (4, s - 2), (s - 2, 4), both counter-clockwise; the lower face owns the texels
+ *            with i + j <= s - 1, the upper face the others;
+ *   corners  the face's corner opposite its longest edge (edge c joins the two corners other than c; squared lengths, the
+ *            first maximum) sits at the right angle, the first corner listed above; the next two follow cyclically.
+ *   bake     one thread per Morton index m of [0, tx_W tx_H): (i, j) = its even and odd bits.  c = the last class with
+ *            tx_class_off[c] <= m; r = m - tx_class_off[c]; cell = tx_class_cell[c] + (r >> 2 k); the local (li, lj) = the
+ *            even and odd bits of r mod 4^k; face = tx_cell_face[cell][li + lj <= s - 1 ? 0 : 1].  No owner (m >= T, cell >=
+ *            tx_n_cells, face outside [0, n_faces)): tx_colors = fill, tx_n_seen = -1.  Otherwise, with (x_i, y_i) =
+ *            tx_uv[face][i]: w0 = (x1 - i)(y2 - j) - (x2 - i)(y1 - j), w1 = (x2 - i)(y0 - j) - (x0 - i)(y2 - j), w2 =
+ *            (x0 - i)(y1 - j) - (x1 - i)(y0 - j), b_i = w_i / ((w0 + w1) + w2), not clamped (the gutter extrapolates);
+ *            p = (b0 p0 + b1 p1) + b2 p2 per coordinate.  Over the views in ascending order: s = the projection of p as in
+ *            `project`; the view counts when s passes the test of `visible` (against depth[view], which holds every view);
+ *            then the sample, the weight and the sums S, C of `colour`, the weight's normal being
+ *            n = m t, m = (b0 n0 + b1 n1) + b2 n2 the mix of the corners' normals, t = l / |m| when |m| > 0, else 0,
+ *            l = (b0 |n0| + b1 |n1|) + b2 |n2| (the mix rescaled to the length the corners' normals have: at a corner t is
+ *            exactly 1 and the texel evaluates exactly the vertex).  tx_colors = float32(C / S), tx_n_seen = the number of
+ *            such views; where S is not finite or not > 0, or the face has a vertex index out of range: tx_n_seen = 0 and
+ *            tx_colors = fill, or with tx_fallback float32((b0 c0 + b1 c1) + b2 c2) of the corners' fallback colours in
+ *            float64 (fill for a face with a vertex index out of range);
+ *   shade    one thread per pixel of [n_views, H, W]: face[pixel] outside [0, n_faces) -> tx_out = tx_background; else
+ *            (u, w) = (b0 uv0 + b1 uv1) + b2 uv2 with the float32 bary[pixel] taken in float64, and the bilinear sample of
+ *            `colour` (x0 = floor(u), taps clamped to the atlas) of tx_colors, per channel, cast to float32.
+ * Host-side refusals (no launch): the size checks of the rasteriser, tx_W or tx_H < 1, tx_W tx_H >= 2^31, tx_n_cells < 0,
+ * tx_n_classes outside [0, 10], a tx_class_k outside [3, 12], tx_class_off or tx_class_cell not ascending from 0, NULL
+ * buffers, a power that is not finite (bake, with normals).  Empty descriptors return 0 (bake: tx_W tx_H = 0; shade: no
+ * pixels).
+ * ---------------------------------------------------------------------------------- */
+int nudf_meshtexture_bake(const NudfMeshRaster* args, void* stream);       /* one thread per Morton index     */
+int nudf_meshtexture_shade(const NudfMeshRaster* args, void* stream);      /* one thread per pixel            */
 
 #ifdef __cplusplus
 }

@@ -288,7 +288,11 @@ class MeshRaster(C.Structure):
                 ("zbuf", c_fp), ("depth", c_fp), ("face", c_fp), ("bary", c_fp), ("vis", c_fp), ("images", c_fp),
                 ("normals", c_fp), ("cam_pos", c_fp), ("colors", c_fp), ("n_seen", c_fp), ("n_faces", C.c_int64),
                 ("n_verts", C.c_int64), ("n_entries", C.c_int64), ("power", C.c_double), ("fill", f32 * 3),
-                ("min_gap", f32), ("n_views", i32), ("H", i32), ("W", i32), ("image_f32", i32)]
+                ("min_gap", f32), ("n_views", i32), ("H", i32), ("W", i32), ("image_f32", i32),
+                ("tx_uv", c_fp), ("tx_cell_face", c_fp), ("tx_fallback", c_fp), ("tx_colors", c_fp), ("tx_n_seen", c_fp),
+                ("tx_out", c_fp), ("tx_n_cells", C.c_int64), ("tx_class_off", C.c_int64 * 11),
+                ("tx_class_cell", C.c_int64 * 11), ("tx_class_k", i32 * 10), ("tx_n_classes", i32), ("tx_W", i32),
+                ("tx_H", i32), ("tx_background", f32 * 3)]
 
 
 # float offsets of the device loss-weight vector (include/nudf.h NUDF_LW_*)
@@ -400,7 +404,8 @@ SIGNATURES = {
         (MeshOrient, ("meshorient_hook", "meshorient_jump", "meshorient_check", "meshorient_outward", "meshorient_normals",
                       "meshsmooth_laplace", "meshsmooth_frames", "meshsmooth_normals", "meshsmooth_update")),
         (MeshRaster, ("meshraster_project", "meshraster_bounds", "meshraster_draw_small", "meshraster_draw_large",
-                      "meshraster_resolve", "meshraster_visible", "meshraster_colour")),
+                      "meshraster_resolve", "meshraster_visible", "meshraster_colour", "meshtexture_bake",
+                      "meshtexture_shade")),
     ) for n in names},
 }
 SYMBOLS = list(SIGNATURES)

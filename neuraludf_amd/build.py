@@ -19,7 +19,7 @@ SOURCES = ["nudf_api.hip", "gemm_f32_mfma.hip", "gemm_tn_f32_mfma.hip", "rays_em
            "blend.hip", "optim.hip", "mlp_chain.hip", "mlp_chain_rows.hip", "raybatch.hip", "meshudf.hip",
            "meshudf_sparse.hip", "isosurface.hip", "pointcloud.hip", "meshtopo.hip", "meshorient.hip", "meshraster.hip",
            "meshsimplify.hip", "meshdist.hip", "meshray.hip", "meshsmooth.hip", "meshsubdiv.hip", "meshhole.hip",
-           "meshintersect.hip", "meshwinding.hip", "meshremesh.hip"]
+           "meshintersect.hip", "meshwinding.hip", "meshremesh.hip", "meshtexture.hip"]
 
 
 # the sources that decide what a kernel class reads and writes (bench.py `roofline.traffic_stale`: a PMC traffic file under
@@ -50,6 +50,7 @@ KERNEL_SOURCES = {
     "meshhole": ["csrc/meshhole.hip", *_MESH_COMMON],
     "meshremesh": ["csrc/meshremesh.hip", *_MESH_COMMON],
     "meshraster": ["csrc/meshraster.hip", "csrc/meshraster_pixel.h", *_MESH_COMMON],
+    "meshtexture": ["csrc/meshtexture.hip", "csrc/meshraster_pixel.h", *_MESH_COMMON],
 }
 
 

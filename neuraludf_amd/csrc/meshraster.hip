@@ -99,30 +99,10 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_visible_kernel(NudfMeshRaster a) 
   const int64_t i = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
   if (i >= (int64_t)a.n_views * a.n_verts) return;
   const int64_t view = i / a.n_verts;
-  const double* s = a.scr + 3 * i;
-  uint8_t seen = 0;
-  if (mr_valid(s) && fabs(s[0]) < 0x1p52 && fabs(s[1]) < 0x1p52) {
-    const double px = rint(s[0]), py = rint(s[1]);   // rint: half to even, as np.round
-    if (px >= 0.0 && px <= (double)(a.W - 1) && py >= 0.0 && py <= (double)(a.H - 1)) {
-      const int32_t ix = (int32_t)px, iy = (int32_t)py;
-      const int32_t xa = ix > 0 ? ix - 1 : 0, xb = ix < a.W - 1 ? ix + 1 : a.W - 1;
-      const int32_t ya = iy > 0 ? iy - 1 : 0, yb = iy < a.H - 1 ? iy + 1 : a.H - 1;
-      const float* d = a.depth + view * a.H * (int64_t)a.W;
-      float m = d[(int64_t)ya * a.W + xa];
-      for (int32_t y = ya; y <= yb; ++y)
-        for (int32_t x = xa; x <= xb; ++x) m = fmaxf(m, d[(int64_t)y * a.W + x]);
-      seen = (float)s[2] <= m + a.min_gap;
-    }
-  }
-  a.vis[i] = seen;
+  a.vis[i] = mr_seen(a, view, a.scr + 3 * i);
 }
 
 // ---- (e) vertex colours ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double mr_tap(const NudfMeshRaster& a, int64_t pixel, int c) {
-  if (a.image_f32) return (double)((const float*)a.images)[3 * pixel + c];
-  return __ddiv_rn((double)((const uint8_t*)a.images)[3 * pixel + c], 255.0);
-}
-
 __global__ __launch_bounds__(MR_BLOCK) void mr_colour_kernel(NudfMeshRaster a) {
   const int64_t v = (int64_t)blockIdx.x * MR_BLOCK + threadIdx.x;
   if (v >= a.n_verts) return;
@@ -133,33 +113,8 @@ __global__ __launch_bounds__(MR_BLOCK) void mr_colour_kernel(NudfMeshRaster a) {
     if (!a.vis[view * a.n_verts + v]) continue;
     double s[3];
     mr_project(a.proj + 12 * view, p, s);
-    const double fx0 = floor(s[0]), fy0 = floor(s[1]);
-    // (vis is the caller's: the clamps below keep every tap inside the image whatever the projection is, NaN included)
-    const double fx = sub(s[0], fx0), fy = sub(s[1], fy0);
-    const double wmax = (double)(a.W - 1), hmax = (double)(a.H - 1);
-    const int64_t xa = (int64_t)fmin(fmax(fx0, 0.0), wmax), xb = (int64_t)fmin(fmax(add(fx0, 1.0), 0.0), wmax);
-    const int64_t ya = (int64_t)fmin(fmax(fy0, 0.0), hmax), yb = (int64_t)fmin(fmax(add(fy0, 1.0), 0.0), hmax);
-    const int64_t base = view * a.H * (int64_t)a.W;
-    const int64_t p00 = base + ya * a.W + xa, p10 = base + ya * a.W + xb;
-    const int64_t p01 = base + yb * a.W + xa, p11 = base + yb * a.W + xb;
-    const double gx = sub(1.0, fx), gy = sub(1.0, fy);
-    const double w00 = mul(gx, gy), w10 = mul(fx, gy), w01 = mul(gx, fy), w11 = mul(fx, fy);
-    double g = 1.0;
-    if (a.normals) {
-      const double* cam = a.cam_pos + 3 * view;
-      const double* nv = a.normals + 3 * v;
-      const double dx = sub(cam[0], p[0]), dy = sub(cam[1], p[1]), dz = sub(cam[2], p[2]);
-      const double len = __dsqrt_rn(add(add(mul(dx, dx), mul(dy, dy)), mul(dz, dz)));
-      const double dot = add(add(mul(nv[0], __ddiv_rn(dx, len)), mul(nv[1], __ddiv_rn(dy, len))),
-                                mul(nv[2], __ddiv_rn(dz, len)));
-      g = pow(fabs(dot), a.power);
-    }
-    for (int c = 0; c < 3; ++c) {
-      const double col = add(add(mul(w00, mr_tap(a, p00, c)), mul(w10, mr_tap(a, p10, c))),
-                                add(mul(w01, mr_tap(a, p01, c)), mul(w11, mr_tap(a, p11, c))));
-      sc[c] = add(sc[c], mul(g, col));
-    }
-    sw = add(sw, g);
+    // (vis is the caller's: mr_taps keeps every tap inside the image whatever the projection is, NaN included)
+    mr_accumulate(a, view, p, s, a.normals ? a.normals + 3 * v : nullptr, &sw, sc);
     ++n;
   }
   const bool ok = sw > 0.0 && sw < HUGE_VAL;

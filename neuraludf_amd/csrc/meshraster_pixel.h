@@ -1,6 +1,8 @@
 // The per-face and per-pixel functions of the rasteriser (csrc/meshraster.hip), shared by draw_small, draw_large and
 // resolve so that the three evaluate the same float64 expressions in the same order (include/nudf.h NudfMeshRaster,
-// tests/meshraster_ref.py).  The including translation unit switches contraction off (f64_exact.h).
+// tests/meshraster_ref.py), and the per-point functions -- the depth test of `visible`, the bilinear sample and the view
+// weight of `colour` -- that the texture bake (csrc/meshtexture.hip) shares with them, so that a texel at a vertex gets the
+// bits the vertex gets.  The including translation unit switches contraction off (f64_exact.h).
 #pragma once
 #include "f64_exact.h"
 #include "nudf_common.h"
@@ -84,4 +86,72 @@ __device__ __forceinline__ void mr_draw(const NudfMeshRaster& a, const MrFace& t
   unsigned long long* cell = (unsigned long long*)a.zbuf + (view * a.H + py) * (int64_t)a.W + px;
   // the cell only ever falls: a key that does not beat what a plain load sees cannot beat the cell either
   if (key < __atomic_load_n(cell, __ATOMIC_RELAXED)) atomicMin(cell, key);
+}
+
+// ---- a point in a view: what `visible` and `colour` evaluate, and `bake` (csrc/meshtexture.hip) per texel ---------------
+// the depth test of `visible` on the projection s of a point: see include/nudf.h
+__device__ __forceinline__ bool mr_seen(const NudfMeshRaster& a, int64_t view, const double* s) {
+  if (!(mr_valid(s) && fabs(s[0]) < 0x1p52 && fabs(s[1]) < 0x1p52)) return false;
+  const double px = rint(s[0]), py = rint(s[1]);     // rint: half to even, as np.round
+  if (!(px >= 0.0 && px <= (double)(a.W - 1) && py >= 0.0 && py <= (double)(a.H - 1))) return false;
+  const int32_t ix = (int32_t)px, iy = (int32_t)py;
+  const int32_t xa = ix > 0 ? ix - 1 : 0, xb = ix < a.W - 1 ? ix + 1 : a.W - 1;
+  const int32_t ya = iy > 0 ? iy - 1 : 0, yb = iy < a.H - 1 ? iy + 1 : a.H - 1;
+  const float* d = a.depth + view * a.H * (int64_t)a.W;
+  float m = d[(int64_t)ya * a.W + xa];
+  for (int32_t y = ya; y <= yb; ++y)
+    for (int32_t x = xa; x <= xb; ++x) m = fmaxf(m, d[(int64_t)y * a.W + x]);
+  return (float)s[2] <= m + a.min_gap;
+}
+
+// the four taps of a bilinear sample at (u, w) in a [H, W] image that starts at element `base`: clamped to the image
+// whatever u and w are, NaN included
+struct MrTaps {
+  int64_t p00, p10, p01, p11;
+  double w00, w10, w01, w11;
+};
+
+__device__ __forceinline__ void mr_taps(double u, double w, int32_t H, int32_t W, int64_t base, MrTaps* t) {
+  const double fx0 = floor(u), fy0 = floor(w);
+  const double fx = sub(u, fx0), fy = sub(w, fy0);
+  const double wmax = (double)(W - 1), hmax = (double)(H - 1);
+  const int64_t xa = (int64_t)fmin(fmax(fx0, 0.0), wmax), xb = (int64_t)fmin(fmax(add(fx0, 1.0), 0.0), wmax);
+  const int64_t ya = (int64_t)fmin(fmax(fy0, 0.0), hmax), yb = (int64_t)fmin(fmax(add(fy0, 1.0), 0.0), hmax);
+  t->p00 = base + ya * W + xa, t->p10 = base + ya * W + xb;
+  t->p01 = base + yb * W + xa, t->p11 = base + yb * W + xb;
+  const double gx = sub(1.0, fx), gy = sub(1.0, fy);
+  t->w00 = mul(gx, gy), t->w10 = mul(fx, gy), t->w01 = mul(gx, fy), t->w11 = mul(fx, fy);
+}
+
+__device__ __forceinline__ double mr_mix(const MrTaps& t, double c00, double c10, double c01, double c11) {
+  return add(add(mul(t.w00, c00), mul(t.w10, c10)), add(mul(t.w01, c01), mul(t.w11, c11)));
+}
+
+// channel c of pixel `pixel` of the source images, in [0, 1] for uint8
+__device__ __forceinline__ double mr_tap(const NudfMeshRaster& a, int64_t pixel, int c) {
+  if (a.image_f32) return (double)((const float*)a.images)[3 * pixel + c];
+  return __ddiv_rn((double)((const uint8_t*)a.images)[3 * pixel + c], 255.0);
+}
+
+// pow(|n . d|, power), d the unit direction from p to the camera centre of the view
+__device__ __forceinline__ double mr_view_weight(const NudfMeshRaster& a, int64_t view, const double* p, const double* nv) {
+  const double* cam = a.cam_pos + 3 * view;
+  const double dx = sub(cam[0], p[0]), dy = sub(cam[1], p[1]), dz = sub(cam[2], p[2]);
+  const double len = __dsqrt_rn(add(add(mul(dx, dx), mul(dy, dy)), mul(dz, dz)));
+  const double dot = add(add(mul(nv[0], __ddiv_rn(dx, len)), mul(nv[1], __ddiv_rn(dy, len))),
+                            mul(nv[2], __ddiv_rn(dz, len)));
+  return pow(fabs(dot), a.power);
+}
+
+// one view's term of the weighted mean at the point p whose projection is s: S += g, C += g c
+__device__ __forceinline__ void mr_accumulate(const NudfMeshRaster& a, int64_t view, const double* p, const double* s,
+                                              const double* nv, double* sw, double* sc) {
+  MrTaps t;
+  mr_taps(s[0], s[1], a.H, a.W, view * a.H * (int64_t)a.W, &t);
+  const double g = nv ? mr_view_weight(a, view, p, nv) : 1.0;
+  for (int c = 0; c < 3; ++c) {
+    const double col = mr_mix(t, mr_tap(a, t.p00, c), mr_tap(a, t.p10, c), mr_tap(a, t.p01, c), mr_tap(a, t.p11, c));
+    sc[c] = add(sc[c], mul(g, col));
+  }
+  *sw = add(*sw, g);
 }

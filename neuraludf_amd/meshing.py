@@ -34,8 +34,10 @@ and its serial Cython mesher.
     winding   orient_faces, vertex_normals (meshclean, csrc/meshorient.hip): consistent winding per component and
                                   angle-weighted normals; the mesher's own winding is decided cell by cell
     file      write_ply           binary little-endian PLY, with normals and colours when given
+              write_obj, read_obj OBJ / MTL / PNG of a textured mesh
     drawing   neuraludf_amd.meshrender: depth / face / normal maps from the dataset cameras, depth-tested visibility and
-                                  vertex colours from the source images (csrc/meshraster.hip)
+                                  vertex colours from the source images (csrc/meshraster.hip); texture atlases baked
+                                  from them (csrc/meshtexture.hip)
 
     python -m neuraludf_amd.meshing IN.ply OUT.ply [--fill-holes] [--smooth-borders] [--min-faces N | --keep-largest]
                                     [--border-loops] [--close-holes N [--close-holes-perimeter P]]
@@ -46,6 +48,7 @@ and its serial Cython mesher.
                                     [--remesh L [--remesh-iterations N]]
                                     [--max-edge H] [--subdivide N [--subdivide-scheme loop|midpoint]]
                                     [--orient | --outward-from X Y Z] [--normals] [--colour] [--render DIR]
+                                    [--texture OUT.obj [--texture-size N | --texture-density D]]
 
 The signs of a cell's corners are chosen inside the cell alone (no propagation between cells): the corner of largest U
 is `+`, every other corner is `+` iff its gradient has a non-negative float64 dot product with that corner's.  A cell is
@@ -688,7 +691,7 @@ def extract_udf_mesh(udf_network, resolution=256, bound_min=(-1.0, -1.0, -1.0), 
                      outward_from=None, color_from=None, simplify_cell=None, simplify_max_error=None, smooth=None,
                      denoise=False, subdivide_max_edge=None, subdivide=None, close_holes=None,
                      close_holes_perimeter=None, close_holes_check=False, drop_self_intersections=False,
-                     remesh_edge=None, remesh_iterations=5):
+                     remesh_edge=None, remesh_iterations=5, texture_from=None, texture_density=None, texture_size=None):
     """open-surface mesh of `udf_network`'s zero level (the reference's get_mesh_udf_fast, without its differentiable
     refinement): udf_grid -> udf_marching_cubes -> filter_mesh with the network's UDF at the vertices and
     max_udf = dist_threshold_ratio * h.  The clean-up the reference takes from trimesh is off by default and follows in
@@ -730,8 +733,22 @@ def extract_udf_mesh(udf_network, resolution=256, bound_min=(-1.0, -1.0, -1.0), 
     `color_from` = (world_mats [n, 4, 4], images [n, H, W, 3] uint8 or float32 on the GPU), in the coordinates of the box
     (meshrender.dataset_views gives the pair of a training source), colours the vertices from the images as the last
     step, weighted by the vertex normals of the mesh as it then is (meshrender.color_vertices), and adds a third value.
-    -> (vertices np.float32 [V, 3], faces np.int64 [F, 3]), with color_from also colors np.float32 [V, 3].  Raises
-    RuntimeError when no surface is found."""
+    `texture_from` = the same pair, in place of color_from (giving both is a ValueError), bakes a texture as the last
+    step instead: an atlas with one chart per face (meshrender.texture_atlas with texture_density texels per unit length
+    of the box, or the largest density whose atlas is at most texture_size texels wide; 4096 when neither is given) is
+    coloured texel by texel as color_from colours vertices (meshrender.bake_texture), and the texels no view sees take
+    the mix of the vertex colours, which are computed for that purpose only.  The colour resolution no longer hangs on
+    the vertex count: simplify first.  It adds two values, uv np.float32 [F, 3, 2], normalised ((u + 0.5) / W, (v + 0.5)
+    / H of the texel-centre coordinates, v downwards as the texture's rows run: write_obj flips it), and texture np.uint8
+    [H, W, 3].
+    -> (vertices np.float32 [V, 3], faces np.int64 [F, 3]), with color_from also colors np.float32 [V, 3], with
+    texture_from also uv and texture.  Raises RuntimeError when no surface is found."""
+    if texture_from is not None and color_from is not None:
+        raise ValueError("texture_from and color_from exclude each other")
+    if texture_from is None and (texture_density is not None or texture_size is not None):
+        raise ValueError("texture_density and texture_size need texture_from")
+    if texture_density is not None and texture_size is not None:
+        raise ValueError("texture_density and texture_size exclude each other")
     n = int(resolution)
     if sparse:
         verts, faces = udf_marching_cubes_sparse(udf_sparse_grid(udf_network, n, bound_min, bound_max, block, lipschitz))
@@ -785,7 +802,25 @@ def extract_udf_mesh(udf_network, resolution=256, bound_min=(-1.0, -1.0, -1.0), 
         colors, _ = meshrender.color_vertices(verts, faces, mats, images.to(verts.device),
                                               normals=meshclean.vertex_normals(verts, faces, torch.float64))
         return _to_host(verts, faces, scale_mat) + (colors.cpu().numpy(),)
+    if texture_from is not None:
+        mats, images = texture_from
+        uv, texture = _bake(verts, faces, mats, images.to(verts.device), texture_density,
+                            4096 if texture_density is None and texture_size is None else texture_size)[:2]
+        return _to_host(verts, faces, scale_mat) + (uv, texture)
     return _to_host(verts, faces, scale_mat)
+
+
+def _bake(verts, faces, mats, images, density, size):
+    """atlas, vertex colours as the fallback, bake -> (uv np.float32 [F, 3, 2] normalised, texture np.uint8 [H, W, 3],
+    Atlas, Texture)"""
+    normals = meshclean.vertex_normals(verts, faces, torch.float64)
+    atlas = meshrender.texture_atlas(verts, faces, density=density, size=size)
+    fallback, _ = meshrender.color_vertices(verts, faces, mats, images, normals=normals)
+    tex = meshrender.bake_texture(verts, faces, atlas, mats, images, normals=normals, fallback=fallback)
+    wh = torch.tensor([atlas.W, atlas.H], dtype=torch.float64, device=verts.device)
+    uv = ((atlas.uv + 0.5) / wh).float().cpu().numpy()
+    texture = _uchar_colors(tex.colors.cpu().numpy()).reshape(atlas.H, atlas.W, 3)
+    return uv, texture, atlas, tex
 
 
 def _uchar_colors(colors):
@@ -833,6 +868,86 @@ def write_ply(path, vertices, faces, normals=None, colors=None):
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
               "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
               "double": "f8", "float64": "f8"}
+
+
+def write_obj(path, vertices, faces, uv, texture):
+    """a textured mesh as Wavefront OBJ: NAME.obj with `v` lines, three `vt` lines per face and `f a/ta b/tb c/tc` lines,
+    NAME.mtl with one material whose map_Kd is NAME.png, and the texture as NAME.png, all next to each other (`path` is
+    NAME.obj).  uv [F, 3, 2]: normalised, ((i + 0.5) / W, (j + 0.5) / H) for the texel-centre coordinates (i, j) of
+    meshrender.Atlas.uv, v downwards as the texture's rows run; OBJ's v runs upwards, so vt = (u, 1 - v).  texture
+    [H, W, 3]: uint8, or floats in [0, 1], rounded as write_ply rounds colours.  Numbers are written with the fewest digits
+    that read back to the same float32 or float64; the atlas's UVs are odd multiples of 1 / 2 W and 1 / 2 H, for which 1 -
+    v is exact."""
+    import os
+    from PIL import Image
+    path = str(path)
+    stem = path[:-4] if path.lower().endswith(".obj") else path
+    name = os.path.basename(stem)
+    v, f = np.asarray(vertices), np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    v = v.reshape(-1, 3)
+    uv = np.asarray(uv)
+    if uv.shape != (len(f), 3, 2):
+        raise ValueError(f"uv must be [{len(f)}, 3, 2] (got {uv.shape})")
+    tex = np.asarray(texture)
+    if tex.ndim != 3 or tex.shape[2] != 3:
+        raise ValueError(f"texture must be [H, W, 3] (got {tex.shape})")
+    tex = _uchar_colors(tex).reshape(tex.shape)
+    lines = [f"mtllib {name}.mtl", f"usemtl {name}"]
+    lines += ["v %s %s %s" % tuple(p) for p in v]                              # str of a numpy float: the shortest that reads back
+    lines += ["vt %s %s" % (t[0], 1 - t[1]) for t in uv.reshape(-1, 2)]
+    lines += ["f %d/%d %d/%d %d/%d" % (a + 1, 3 * i + 1, b + 1, 3 * i + 2, c + 1, 3 * i + 3) for i, (a, b, c) in enumerate(f)]
+    with open(stem + ".obj", "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(stem + ".mtl", "w") as fh:
+        fh.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    Image.fromarray(tex).save(stem + ".png")
+
+
+def read_obj(path):
+    """what write_obj writes -> (vertices np.float64 [V, 3], faces np.int64 [F, 3], uv np.float64 [F, 3, 2] with v
+    downwards again (1 - vt.v), texture np.uint8 [H, W, 3] or None): `v`, `vt`, triangular `f v/vt` (a normal index
+    after a second slash is ignored), and the map_Kd of the mtllib, both resolved next to the file.  Not a general OBJ
+    reader: anything else on a line that it needs is a ValueError, other lines are skipped."""
+    import os
+    from PIL import Image
+    path = str(path)
+    v, vt, fv, ft, mtl = [], [], [], [], None
+    with open(path) as fh:
+        for n, line in enumerate(fh, 1):
+            w = line.split()
+            if not w or w[0].startswith("#"):
+                continue
+            try:
+                if w[0] == "v":
+                    v.append([float(x) for x in w[1:4]])
+                elif w[0] == "vt":
+                    vt.append([float(x) for x in w[1:3]])
+                elif w[0] == "f":
+                    if len(w) != 4:
+                        raise ValueError("not a triangle")
+                    idx = [x.split("/") for x in w[1:]]
+                    fv.append([int(x[0]) - 1 for x in idx])
+                    ft.append([int(x[1]) - 1 for x in idx])
+                elif w[0] == "mtllib":
+                    mtl = line.split(None, 1)[1].strip()
+            except (ValueError, IndexError) as e:
+                raise ValueError(f"{path}:{n}: {line.strip()!r}: {e}") from None
+    v = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    vt = np.asarray(vt, dtype=np.float64).reshape(-1, 2)
+    fv, ft = np.asarray(fv, dtype=np.int64).reshape(-1, 3), np.asarray(ft, dtype=np.int64).reshape(-1, 3)
+    if fv.size and (fv.min() < 0 or fv.max() >= len(v) or ft.min() < 0 or ft.max() >= len(vt)):
+        raise ValueError(f"{path}: a face index is out of range")
+    uv = vt[ft]
+    uv[..., 1] = 1.0 - uv[..., 1]
+    texture, here = None, os.path.dirname(path)
+    if mtl is not None and os.path.exists(os.path.join(here, mtl)):
+        with open(os.path.join(here, mtl)) as fh:
+            for line in fh:
+                w = line.split(None, 1)
+                if len(w) == 2 and w[0] == "map_Kd":
+                    texture = np.ascontiguousarray(np.asarray(Image.open(os.path.join(here, w[1].strip())).convert("RGB"),
+                                                              dtype=np.uint8))
+    return v, fv, uv, texture
 
 
 def _ply_header(fh):
@@ -979,9 +1094,11 @@ def load_dtu_images(dataset_dir, scan):
     return np.stack([np.ascontiguousarray(np.asarray(Image.open(f).convert("RGB"), dtype=np.uint8)) for f in files])
 
 
-def _write_renders(out_dir, verts, faces, normals, world_mats, H, W, view_chunk=8):
+def _write_renders(out_dir, verts, faces, normals, world_mats, H, W, view_chunk=8, textured=None):
     """normal_<i>.png (world-space normals, (n + 1) / 2 as 8-bit red, green, blue; black where nothing was drawn) and
-    depth_<i>.npy (float32 [H, W], +inf where nothing was drawn) of the mesh from every view"""
+    depth_<i>.npy (float32 [H, W], +inf where nothing was drawn) of the mesh from every view; with textured = (Atlas,
+    Texture) also texture_<i>.png, the mesh drawn with its texture (meshrender.shade_textured; black where nothing was
+    drawn)"""
     import os
     from PIL import Image
     os.makedirs(out_dir, exist_ok=True)
@@ -991,7 +1108,12 @@ def _write_renders(out_dir, verts, faces, normals, world_mats, H, W, view_chunk=
         img = torch.where((r.face >= 0)[..., None], (nm + 1.0) * 0.5, torch.zeros_like(nm))
         img = (img.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).cpu().numpy()
         depth = r.depth.cpu().numpy()
+        if textured is not None:
+            shaded = meshrender.shade_textured(r, *textured)
+            shaded = (shaded.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8).cpu().numpy()
         for k in range(len(depth)):
+            if textured is not None:
+                Image.fromarray(shaded[k]).save(os.path.join(out_dir, f"texture_{s + k}.png"))
             Image.fromarray(img[k]).save(os.path.join(out_dir, f"normal_{s + k}.png"))
             np.save(os.path.join(out_dir, f"depth_{s + k}.npy"), depth[k])
 
@@ -1052,8 +1174,19 @@ def main(argv=None):
                     help="colour the vertices from scan<N>/image/*.png (needs --dtu-dir and --scan; red, green, blue)")
     ap.add_argument("--render", metavar="DIR",
                     help="write normal_<i>.png and depth_<i>.npy of the mesh from every camera of the scan into DIR")
+    ap.add_argument("--texture", metavar="OUT.obj",
+                    help="bake a texture atlas from scan<N>/image/*.png and write OUT.obj, OUT.mtl and OUT.png (needs "
+                         "--dtu-dir and --scan); --render then also writes texture_<i>.png")
+    grp = ap.add_mutually_exclusive_group()
+    grp.add_argument("--texture-size", type=int, metavar="N",
+                     help="the largest atlas width: the densest atlas that fits is used (default 4096)")
+    grp.add_argument("--texture-density", type=float, metavar="D", help="texels per unit length instead")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.texture and a.dtu_dir is None:
+        ap.error("--texture needs --dtu-dir and --scan")
+    if (a.texture_size is not None or a.texture_density is not None) and not a.texture:
+        ap.error("--texture-size and --texture-density need --texture")
     if (a.dtu_dir is None) != (a.scan is None):
         ap.error("--dtu-dir and --scan go together")
     if (a.colour or a.render) and a.dtu_dir is None:
@@ -1173,17 +1306,27 @@ def main(argv=None):
               f"{info['flipped']} faces flipped")
     normals = meshclean.vertex_normals(verts, faces).cpu().numpy() if a.normals else None
     colors = carried
-    if a.colour or a.render:
+    textured = None
+    if a.colour or a.render or a.texture:
         unit = meshclean.vertex_normals(verts, faces, torch.float64)
-        if a.colour:
+        if a.colour or a.texture:
             images = torch.from_numpy(load_dtu_images(a.dtu_dir, a.scan)).to(dev)
             if images.shape[0] != mats.shape[0]:
                 ap.error(f"{images.shape[0]} images for {mats.shape[0]} cameras")
+        if a.texture:
+            size = a.texture_size if a.texture_size is not None or a.texture_density is not None else 4096
+            uv, texture, atlas, tex = _bake(verts, faces, mats, images, a.texture_density, size)
+            write_obj(a.texture, verts.cpu().numpy(), faces.cpu().numpy(), uv, texture)
+            owned = int((tex.n_seen >= 0).sum())
+            print(f"texture: {atlas.W} x {atlas.H} texels at density {atlas.density:.6g}, {owned} owned, "
+                  f"{int((tex.n_seen > 0).sum())} seen by a view -> {a.texture}")
+            textured = (atlas, tex)
+        if a.colour:
             colors, seen = meshrender.color_vertices(verts, faces, mats, images, normals=unit)
             print(f"colour: {int((seen > 0).sum())} of {verts.shape[0]} vertices seen by a view")
             colors = colors.cpu().numpy()
         if a.render:
-            _write_renders(a.render, verts, faces, unit, mats, masks.shape[1], masks.shape[2])
+            _write_renders(a.render, verts, faces, unit, mats, masks.shape[1], masks.shape[2], textured=textured)
     write_ply(a.output, verts.cpu().numpy(), faces.cpu().numpy(), normals, colors)
     print(f"{a.input}: {n0[0]} vertices, {n0[1]} faces -> {a.output}: {verts.shape[0]} vertices, {faces.shape[0]} faces")
     return 0

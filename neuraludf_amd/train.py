@@ -516,7 +516,8 @@ class Trainer:
         orient=True / outward_from=(x, y, z) in the box's coordinates (wind the faces of every orientable component
         consistently as the last step, away from that point when given), and color_from=(world_mats, images) -- the pair
         meshrender.dataset_views gives for the training source --, which colours the vertices from the images and adds the
-        colours, np.float32 [V, 3], as a third value; the filtering, simplification and subdivision switches (smooth,
+        colours, np.float32 [V, 3], as a third value, or texture_from=(world_mats, images) with texture_density or
+        texture_size, which bakes a texture atlas instead and adds uv [F, 3, 2] and texture uint8 [H, W, 3]; the filtering, simplification and subdivision switches (smooth,
         denoise, simplify_cell, simplify_max_error, subdivide_max_edge, subdivide) pass through as well."""
         from . import meshing
         if world_space and scale_mat is None:
